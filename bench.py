@@ -4,6 +4,12 @@
 integration) with all input planes resident in HBM.
 
     python bench.py [--gpus N --steps K --warmup W] [--config 1|2|3|4] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every other measurement and check:
+the cold launches, the repeat blocks and clocks, the per-rank split and the bit-identity checks of a sharded run, the
+live PMC traffic passes, the copy ceiling and steady state, the batched / secondary / product companions and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float64).
 
 One process per GPU.  `python bench.py --gpus N` starts its own N ranks (spawn_ranks below: plain
 subprocesses, each with RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR / MASTER_PORT and a random job token in its
@@ -80,8 +86,8 @@ def live_traffic(kernel_tag="k_reflected_toa<5", timeout_s=150.0):
     exe = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if not exe:
         return None, "rocprofv3 not found"
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--prewarm-ms", "0",
-             "--cpu-sample", "0", "--steady-steps", "0", "--secondary", "0", "--product", "0", "--traffic", "off"]
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--prewarm-ms",
+             "0", "--cpu-sample", "0", "--steady-steps", "0", "--secondary", "0", "--product", "0", "--traffic", "off"]
     env = dict(os.environ, TMPDIR="/tmp")
     means = {}
     t0 = time.perf_counter()
@@ -201,7 +207,7 @@ def workload_reflected(ctx, args, lo, hi, seed, nwno_total, scene=None):
         return launch, albs, singles
 
     return dict(solve=solve, oracle=oracle, nloc=n, scene=scene, solve_batch=solve_batch,
-                solve_batch_distinct=solve_batch_distinct,
+                solve_batch_distinct=solve_batch_distinct, result="albedo", outputs={"xint_at_top": xint},
                 abytes=8 * n * (9 * nlayer + 2 * nlevel + 2 + ng + 1),
                 # launches of at most one 64-column block per CU (256 CUs) run the cooperative kernel (api.hip)
                 kernel=("k_reflected_coop<true>" if n <= 16384 and ng <= 5 and not os.environ.get("PICASO_AMD_REFL_NO_COOP")
@@ -268,6 +274,7 @@ def workload_thermal(ctx, args, lo, hi, seed, nwno_total, scene=None):
         return launch, dk
 
     return dict(solve=solve, oracle=oracle, nloc=n, abytes=8 * n * (3 * nlayer + 3 + ng + 1), solve_batch=solve_batch,
+                result="thermal", outputs={"flux_at_top": flux},
                 kernel=("k_thermal_coop<%d>" if n <= 32768 else "k_thermal_toa<%d, false>") % ng,
                 workload="BASELINE configs[1]: thermal emission (get_thermal_1d + compress_thermal), "
                          "Planck per level, 5 Gauss angles",
@@ -311,11 +318,12 @@ def workload_sh4(ctx, args, lo, hi, seed, nwno_total, scene=None, clear=False, t
 
     if clear:
         return dict(solve=solve, oracle=oracle, nloc=n, abytes=8 * n * (2 * nlayer + 2 + ng + 1), kernel="k_sh4_clear<2>",
+                    result="albedo", outputs={"xint_at_top": xint},
                     workload="configs[3] on a cloud-free atmosphere: SH4 reflected light from dtau and w0 only (the other "
                              "nine planes are constants, copies and running sums), angle-independent half of each layer "
                              "shared between two disk angles of a lane",
                     metric="spectra/sec (%d wave x %d layer SH4 reflected, cloud-free)" % (nwno_total, nlayer))
-    return dict(solve=solve, oracle=oracle, nloc=n,
+    return dict(solve=solve, oracle=oracle, nloc=n, result="albedo", outputs={"xint_at_top": xint},
                 abytes=8 * n * (9 * nlayer + 2 * nlevel + 2 + ng + 1),
                 kernel=("k_sh_refl<2, true%s>" % ("" if levels else ", true")) if not top else
                        "k_sh4_clear<2> (layers 0-%d) + k_sh_refl<2, true%s>" % (top - 1, "" if levels else ", true"),
@@ -367,7 +375,7 @@ def workload_3d(ctx, args, lo, hi, seed, nwno_total, scene=None, single_phase=0)
         xo = xo[0] if isinstance(xo, tuple) else xo
         return orc.compress_disco(ns, float(ct), xo, gw, tw, np.ones(ns))
 
-    return dict(solve=solve, oracle=oracle, nloc=n, oracle_sample=256,
+    return dict(solve=solve, oracle=oracle, nloc=n, oracle_sample=256, result="albedo", outputs={"xint_at_top": xint},
                 abytes=8 * n * (ng * nt * (9 * nlayer + 2 * nlevel + 1) + 2 + 1),
                 kernel="k_reflected_toa<1, true, false, false, false, 0>",
                 workload="BASELINE configs[4]: 3-D reflected light, 8x8 facets at phase pi/3 (get_reflected_3d + "
@@ -459,6 +467,23 @@ def orc_flags():
         return orc.build_flags()
     except Exception as exc:
         return "unknown (%s)" % exc
+
+
+DUMP_BYTES = 64 * 10 ** 6 - 64 * 1024     # --dump-outputs: 64 MB in all, .npy headers included
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  When they would exceed DUMP_BYTES together, each keeps
+    the same fixed, seeded sample of its wavelength columns (last axis), sorted, in proportion to its size."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            n = a.shape[-1]
+            cols = np.sort(np.random.default_rng(0).choice(n, max(1, n * DUMP_BYTES // total), replace=False))
+            a = a[..., cols]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def steady_ms(ctx, launch, steps, prewarm_ms=60.0):
@@ -976,21 +1001,29 @@ def main():
     ap.add_argument("--ngauss", type=int, default=5, help="disk Gauss angles (5..8)")
     ap.add_argument("--prewarm-ms", type=float, default=400.0,
                     help="untimed launches of the same step before the W warm-up steps (clock ramp)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other measurement and check of the benchmark (the "
+                         "options below marked --full); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample "
+                         "of the wavelength columns when the arrays would exceed 64 MB together)")
     ap.add_argument("--cpu-sample", type=int, default=100000,
-                    help="wavelengths of the same workload timed on the CPU oracle (0 = skip)")
+                    help="--full: wavelengths of the same workload timed on the CPU oracle (0 = skip)")
     ap.add_argument("--steady-steps", type=int, default=2000,
-                    help="N = 1: steps of an extra untimed run after the timed region, reported as steady_state")
+                    help="--full, N = 1: steps of an extra untimed run after the timed region, reported as steady_state")
     ap.add_argument("--repeats", type=int, default=9,
-                    help="further K-step blocks after the timed one (N = 1): their median / min / max go into the line")
+                    help="--full: further K-step blocks after the timed one (N = 1): their median / min / max go into "
+                         "the line")
     ap.add_argument("--secondary", type=int, default=1,
-                    help="N = 1, default workload: after the timed region also time the batched launch of the same "
-                         "workload (throughput_batched) and the other BASELINE configurations (secondary); 0 = skip")
+                    help="--full, N = 1, default workload: after the timed region also time the batched launch of the "
+                         "same workload (throughput_batched) and the other BASELINE configurations (secondary); 0 = skip")
     ap.add_argument("--batch", type=int, default=4, help="spectra per launch of the throughput_batched companion")
     ap.add_argument("--product", type=int, default=1,
                     help="with --secondary: also time inputs.spectrum() and spectrum_batch() end to end (product); 0 = skip")
-    ap.add_argument("--traffic", default="live", choices=("live", "committed", "off"),
-                    help="roofline.traffic: 'live' = two rocprofv3 --pmc passes of a short child run, now (falls back to the "
-                         "committed profiles/traffic.json when the profiler is not usable); 'committed' = that file only")
+    ap.add_argument("--traffic", default=None, choices=("live", "committed", "off"),
+                    help="roofline.traffic: 'live' (the default with --full) = two rocprofv3 --pmc passes of a short "
+                         "child run, now (falls back to the committed profiles/traffic.json when the profiler is not "
+                         "usable); 'committed' (the default otherwise) = that file only")
     ap.add_argument("--spawn", action="store_true",
                     help="start the ranks as subprocesses also for --gpus 1 (the N > 1 code path -- rendezvous, RCCL "
                          "communicator, gather in the timed region, checks -- with one rank, on a 1-GPU box)")
@@ -998,6 +1031,8 @@ def main():
                     help="start the ranks, let them find each other (HostGroup) and exit: checks the launch path "
                          "of a node without touching a GPU")
     args = ap.parse_args()
+    if args.traffic is None:
+        args.traffic = "live" if args.full else "committed"
 
     launched = "RANK" in os.environ
     if (args.gpus > 1 or args.spawn) and not launched:
@@ -1087,9 +1122,9 @@ def main():
             step(gather)
         return device.timer_stop(ctx) / nsteps
 
-    # ---- the first launches of a cold process (reported, not the metric): what ONE interactive call sees ----
+    # ---- --full: the first launches of a cold process (reported, not the metric): what ONE interactive call sees ----
     device.sync(ctx)
-    cold_ms = timed(20, gather=False)
+    cold_ms = timed(20, gather=False) if args.full else None
     nstep[0] = 0
     # ---- clock ramp (untimed), warm-up, timed region ----
     # The time-based part launches the solve only (no collective: the ranks may run different numbers
@@ -1106,7 +1141,8 @@ def main():
         for _ in range(20):
             step()
         nprewarm += 20
-    clocks_before = gpu_clocks(local_rank) if not comm else None      # behind the ramp, in front of the W warm-up steps
+    # behind the ramp, in front of the W warm-up steps
+    clocks_before = gpu_clocks(local_rank) if args.full and not comm else None
     for _ in range(args.warmup):
         step()
     barrier()
@@ -1120,11 +1156,21 @@ def main():
     stream_ms = device.timer_stop(ctx) / args.steps       # HIP events on the kernel's stream (solve [+ last gathers])
     barrier()
     elapsed = time.perf_counter() - t0
-    # ---- untimed: the spread of the same K-step block on this box (nine more blocks, each bracketed like the timed
-    # one) and the clocks the GPU reports while a block is still on the stream -- what makes `value` comparable across
-    # boxes (the timed block above is the metric; these only say where it sits) ----
+    last = (nstep[0] - 1) % (2 * G)
+    res_local = loc[last].to_host()
+    res_full = full[last].to_host() if comm else res_local
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller: the spectrum (gathered when sharded) and, when this rank holds
+        # the whole grid, the per-angle array it was integrated from
+        dumped = {wl["result"]: res_full}
+        if lo == 0 and hi == nwno_total:
+            dumped.update({k: v.to_host() for k, v in wl["outputs"].items()})
+        dump_outputs(args.dump_outputs, dumped)
+    # ---- --full, untimed: the spread of the same K-step block on this box (nine more blocks, each bracketed like the
+    # timed one) and the clocks the GPU reports while a block is still on the stream -- what makes `value` comparable
+    # across boxes (the timed block above is the metric; these only say where it sits) ----
     repeats = None
-    if not comm and args.repeats > 0:
+    if args.full and not comm and args.repeats > 0:
         blocks, clk = [], []
         for _ in range(args.repeats):
             device.sync(ctx)
@@ -1144,14 +1190,11 @@ def main():
         repeats["clocks_idle_after"] = gpu_clocks(local_rank)
     if comm:
         elapsed = comm.max(elapsed)
-    last = (nstep[0] - 1) % (2 * G)
-    res_local = loc[last].to_host()
-    res_full = full[last].to_host() if comm else res_local
 
-    # ---- untimed: per-rank split of the step into solve and gather ----
+    # ---- --full, untimed: per-rank split of the step into solve and gather ----
     kernel_ms = stream_ms
     per_rank = None
-    if comm:
+    if args.full and comm:
         for _ in range(200):                # the copies above idled the GPU: back to steady clocks first
             step()
         kernel_ms = timed(args.steps, gather=False)
@@ -1167,10 +1210,10 @@ def main():
 
     out = None
     if rank == 0:
-        # ---- parity: the gathered spectrum holds this rank's shard bit-exactly, and (strong scaling)
+        # ---- --full, parity: the gathered spectrum holds this rank's shard bit-exactly, and (strong scaling)
         # equals the spectrum solved unsharded on this GPU bit for bit (SURVEY 7 test (v)) ----
         checks = {}
-        if comm:
+        if args.full and comm:
             # recorded in the JSON line (and on stderr when false) rather than asserted: a failed check must
             # not cost the run its measurement
             checks["gathered_contains_local_shard"] = bool(np.array_equal(res_full[lo:hi], res_local))
@@ -1241,7 +1284,7 @@ def main():
         if per_rank:
             out["per_rank"] = per_rank
             out["checks"] = checks
-        if world == 1 and args.steady_steps > 0:
+        if args.full and world == 1 and args.steady_steps > 0:
             # the HBM ceiling this box reaches with a plain copy ("peak = vendor 8 TB/s and a measured
             # hipMemcpyDtoD ceiling on the same box, both stated"): 1 GiB device-to-device, read + write counted
             try:
@@ -1275,7 +1318,7 @@ def main():
             for _ in range(50):
                 step()
             out["steady_state"] = {"steps": nst, "ms_per_step": timed(nst)}
-        if world == 1 and args.config == 2 and args.secondary and args.scaling == "strong":
+        if args.full and world == 1 and args.config == 2 and args.secondary and args.scaling == "strong":
             try:      # reported extras: never worth the measurement above
                 out.update(companions(ctx, args, wl, res_local, nwno_total))
             except Exception as exc:
@@ -1295,7 +1338,7 @@ def main():
             peak = 1024 * 64 / 2.47e-9 / 1e12
             out["fp64_issue"] = {"achieved": rate, "peak_measured": peak, "unit": "T lane-instr/s",
                                  "frac": rate / peak, "valu_wave_insts_per_launch": valu}
-        if world == 1 and args.cpu_sample > 0 and wl["oracle"] is not None:
+        if args.full and world == 1 and args.cpu_sample > 0 and wl["oracle"] is not None:
             ns = min(args.cpu_sample, nloc, wl.get("oracle_sample", nloc))
             # ~10 s of CPU work: whole passes over the sample until that much has been timed (at most five)
             t1 = time.perf_counter()

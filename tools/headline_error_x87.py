@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Where the 7e-10 of the headline scene comes from (run on the GPU box).
 
-bench.py reports max |albedo_GPU - albedo_oracle| / albedo over all 1e5 columns of BASELINE configs[2] (7.2e-10 in
+bench.py --full reports max |albedo_GPU - albedo_oracle| / albedo over all 1e5 columns of BASELINE configs[2] (7.2e-10 in
 round 4) while the golden scenes sit at <= 1e-10.  This tool solves the same scene three ways -- the HIP kernel, the fp64
 CPU restatement of the reference's algorithm (setup_tri_diag + tri_diag_solve, two sweeps) and the SAME restatement
 compiled with long double (x87 80-bit: the reference's expressions with 11 more mantissa bits) -- and prints, for the

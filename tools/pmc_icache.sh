@@ -4,7 +4,7 @@ TAG=${1:-ic}
 OUT=$PWD/gpurun_out/pmci_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $PWD/bench.py --steps 5 --warmup 1 --cpu-sample 0"
+CMD="python $PWD/bench.py --full --steps 5 --warmup 1 --cpu-sample 0"
 cd /tmp
 for pass in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_IFETCH" "SQC_DCACHE_REQ SQC_DCACHE_HITS SQC_DCACHE_MISSES SQ_INST_CYCLES_SMEM" "SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU"; do
   n=$(echo $pass | cut -c1-20 | tr ' ' '_')

@@ -4,7 +4,7 @@ TAG=${1:-q}; shift
 OUT=$PWD/gpurun_out/pmcq_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-CMD="python $PWD/bench.py --steps 5 --warmup 1 --cpu-sample 0 $@"
+CMD="python $PWD/bench.py --full --steps 5 --warmup 1 --cpu-sample 0 $@"
 cd /tmp
 rocprofv3 --kernel-trace --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES -d $OUT/pmc -o pmc -- $CMD > $OUT/pmc.log 2>&1
 cd - > /dev/null
