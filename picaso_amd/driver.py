@@ -12,16 +12,12 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from . import planes as _planes
 from .device import DeviceArray, PinnedArray
 
 _dp = ctypes.POINTER(ctypes.c_double)
 _dpp = ctypes.POINTER(_dp)
 _ip = ctypes.POINTER(ctypes.c_int)
-
-OUT_NAMES = ("dtau", "tau", "w0", "cosb", "ftau_cld", "ftau_ray", "gcos2", "dtau_og", "tau_og", "w0_og", "cosb_og",
-             "w0_no_raman", "f_deltaM")                                 # order of picaso_compute_opacity_ck_dev
-REFL_NAMES = ("dtau", "tau", "w0", "cosb", "gcos2", "ftau_cld", "ftau_ray", "dtau_og", "tau_og", "w0_og", "cosb_og")
-SH_NAMES = ("dtau", "tau", "w0", "cosb", "ftau_cld", "ftau_ray", "f_deltaM", "dtau_og", "tau_og", "w0_og", "cosb_og")
 
 
 class Block(ctypes.Structure):
@@ -82,12 +78,14 @@ class BlockTable:
     layer count, legs, which planes are written.  Workspaces are allocated once and reused by every later spectrum
     of the same signature: every access is ordered on the blocks' streams."""
 
-    def __init__(self, subs, nlayer, ng, nt, mol_names, cia_pairs, ray_names, linear, want, lean, host_cloud,
-                 do_reflected, do_thermal, const_planes, derive=False, sh=False, facets=0, th3=None, ngauss=1):
+    def __init__(self, subs, nlayer, ng, nt, mol_names, cia_pairs, ray_names, linear, choice, host_cloud,
+                 do_reflected, do_thermal, const_planes, sh=False, facets=0, ngauss=1):
+        """``choice``: the ``planes.Choice`` of the call -- which planes the blocks' workspaces hold, and what the legs
+        read (``planes.views``)."""
         self.subs, self.n = subs, len(subs)
         self.blocks = (Block * self.n)()
         self.keep = []                                   # DeviceArrays and pointer tables the structs point into
-        self.want = tuple(want)
+        self.want = tuple(_planes.OUT_NAMES if choice.want is None else choice.want)
         for b, (lo, hi, sub) in enumerate(subs):
             k = self.blocks[b]
             ctx, nw = sub.ctx, hi - lo
@@ -104,73 +102,40 @@ class BlockTable:
             if facets:
                 # a 3-D block (Job.nfacets): facet-major planes (nfacets, nlayer, nw) from the fused launch over the tall
                 # atmosphere; no TAUGAS / TAURAY workspace (that launch keeps the sums in registers), no level planes
-                self._facet_block(k, ctx, nw, nlayer, ng, nt, facets, want, do_reflected, do_thermal, th3)
-                continue
-            tg, tr = DeviceArray((nlayer, ncolg), ctx), DeviceArray((nlayer, nw), ctx)
-            self.keep += [tg, tr]
-            k.taugas, k.tauray = _dev(tg), _dev(tr)
-            pl = {}
-            for i, name in enumerate(OUT_NAMES):
-                if name in want:
-                    pl[name] = DeviceArray((nlayer + 1 if name in ("tau", "tau_og") else nlayer, ncolg), ctx)
-                    self.keep.append(pl[name])
-                    k.planes[i] = _dev(pl[name])
-            rpl = pl
-            if sh and lean:                              # SH, no cloud: the launch reads dtau and w0 (thermal: + cosb_og = 0)
-                zero, one, half = const_planes(sub, nlayer, nw)
-                rpl = {"dtau": pl["dtau"], "w0": pl["w0"]}
-                pl = dict(pl, cosb_og=zero)
-            elif sh:
-                pass                                     # the planes as written (level planes may be left out: derived)
-            elif lean and derive:                        # the reflected kernel re-derives all but dtau and w0
-                zero, one, half = const_planes(sub, nlayer, nw)
-                rpl = {"dtau": pl["dtau"], "w0": pl.get("w0")}
-                pl.update(dtau_og=pl["dtau"], cosb_og=zero)
-                if "w0_no_raman" not in pl and "w0" in pl:
-                    pl["w0_no_raman"] = pl["w0"]
-            elif lean:                                   # justdoit.picaso: aliases and constants of a cloud-free atmosphere
-                zero, one, half = const_planes(sub, nlayer, nw)
-                pl.update(dtau_og=pl["dtau"], cosb=zero, cosb_og=zero, ftau_cld=zero, ftau_ray=one, gcos2=half)
-                if "tau" in pl:
-                    pl.update(tau_og=pl["tau"], w0_og=pl["w0"])
-                if "w0_no_raman" not in pl and "w0" in pl:
-                    pl["w0_no_raman"] = pl["w0"]
+                if {"tau", "tau_og"} & set(self.want):
+                    raise ValueError("3-D blocks: the level planes are running sums inside the solvers")
+                pl = self._alloc_planes(k, self.want, (facets, nlayer, nw), (facets, nlayer, nw), ctx)
+                legs = refl = pl
+            else:
+                tg, tr = DeviceArray((nlayer, ncolg), ctx), DeviceArray((nlayer, nw), ctx)
+                self.keep += [tg, tr]
+                k.taugas, k.tauray = _dev(tg), _dev(tr)
+                pl = self._alloc_planes(k, self.want, (nlayer, ncolg), (nlayer + 1, ncolg), ctx)
+                legs, refl = _planes.views(choice, pl, lambda: const_planes(sub, nlayer, nw))
             if do_reflected:
-                for i, name in enumerate(SH_NAMES if sh else REFL_NAMES):
-                    k.refl_planes[i] = _dev(rpl.get(name))       # None: left out, re-derived in the kernel
+                for i, name in enumerate(_planes.SH_PLANES if sh else _planes.REFLECTED_PLANES):
+                    k.refl_planes[i] = _dev(refl.get(name))       # None: left out, re-derived in the kernel
                 x, a = DeviceArray((ng, nt, nw), ctx), DeviceArray((nw + 1,), ctx)     # [nw]: the Bond-albedo integral
                 pin = PinnedArray((nw + 1,), ctx)           # the result copy is enqueued with the launches
                 self.keep += [x, a, pin]
                 k.xint, k.albedo, k.albedo_pin = _dev(x), _dev(a), ctypes.cast(ctypes.c_void_p(pin.addr), _dp)
-            if do_thermal and sh:                        # get_thermal_SH reads dtau, w0 and cosb_og (spectrum._thermal_sh)
-                k.th_dtau, k.th_w0, k.th_cosb = _dev(pl["dtau"]), _dev(pl["w0"]), _dev(pl["cosb_og"])
-            elif do_thermal:
-                k.th_dtau, k.th_w0, k.th_cosb = _dev(pl["dtau_og"]), _dev(pl["w0_no_raman"]), _dev(pl["cosb_og"])
+            if do_thermal:                               # (3-D: no cosb plane without cloud)
+                k.th_dtau, k.th_w0, k.th_cosb = (_dev(legs[n]) if n else None for n in choice.thermal)
             if host_cloud:
                 cw = [DeviceArray((nlayer, nw), ctx) for _ in range(3)]
                 self.keep += cw
                 k.cld_work_opd, k.cld_work_w0, k.cld_work_g0 = (_dev(c) for c in cw)
         self.thermal_ws = {}                              # thermal outputs live on the thermal leg's context
 
-    def _facet_block(self, k, ctx, nw, nlayer, ng, nt, facets, want, do_reflected, do_thermal, th3):
-        if {"tau", "tau_og"} & set(want):
-            raise ValueError("3-D blocks: the level planes are running sums inside the solvers")
+    def _alloc_planes(self, k, want, shape, level_shape, ctx):
+        """The block's workspace for the planes compute_opacity writes (``level_shape``: tau, tau_og)."""
         pl = {}
-        for i, name in enumerate(OUT_NAMES):
+        for i, name in enumerate(_planes.OUT_NAMES):
             if name in want:
-                pl[name] = DeviceArray((facets, nlayer, nw), ctx)
+                pl[name] = DeviceArray(level_shape if name in ("tau", "tau_og") else shape, ctx)
                 self.keep.append(pl[name])
                 k.planes[i] = _dev(pl[name])
-        if do_reflected:
-            for i, name in enumerate(REFL_NAMES):
-                k.refl_planes[i] = _dev(pl.get(name))
-            x, a = DeviceArray((ng, nt, nw), ctx), DeviceArray((nw + 1,), ctx)
-            pin = PinnedArray((nw + 1,), ctx)
-            self.keep += [x, a, pin]
-            k.xint, k.albedo, k.albedo_pin = _dev(x), _dev(a), ctypes.cast(ctypes.c_void_p(pin.addr), _dp)
-        if do_thermal:
-            k.th_dtau, k.th_w0 = _dev(pl[th3[0]]), _dev(pl[th3[1]])
-            k.th_cosb = _dev(pl[th3[2]]) if th3[2] else None
+        return pl
 
     def thermal_workspace(self, b, tctx, ng, nt):
         """flux / disk of block b on the context the thermal leg runs on (allocated once per context)."""

@@ -22,7 +22,8 @@ from . import _lib, disco, optics, resident
 from . import options as _options
 from .device import DeviceArray
 from .options import Options                                                        # noqa: F401  (jdi.Options)
-from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _cloud_free_top, _constant_planes,   # noqa: F401
+from .planes import cloud_free_top as _cloud_free_top                               # noqa: F401  (jdi._cloud_free_top)
+from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
                        _fetch, _interp_axis, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
                        _reflected, _resident_vector, _setup_atmosphere, _trapz_resident)
 

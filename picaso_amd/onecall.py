@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, device, optics, resident
+from . import _lib, device, optics, planes
 from . import driver as drv
 from .atmsetup import CloudTables
 from .device import DeviceArray
@@ -56,54 +56,6 @@ def _in_scope(inp, opa, legs, nblocks, opt):
     if is_sh and inp["approx"]["rt_params"]["SH"]["calculate_fluxes"]:
         return False                # the layer moment fluxes (flx = 1) are a per-call output of the call-by-call path
     return not (inp["approx"]["rt_params"]["common"]["raman"] == 0 and nblocks != 1)
-
-
-_SH_READS = ("dtau", "w0", "cosb_og", "ftau_cld", "ftau_ray", "f_deltaM", "dtau_og", "w0_og")
-
-
-def _plane_set_sh(inp, atm, nwno, common, frac_c, opt):
-    """``_plane_set`` for the SH solvers: ``(want, lean, sh_top)`` as ``Spectrum._want_1d`` chooses them -- dtau and w0
-    for a cloud-free atmosphere with the default options, the eight planes the launch reads when the level planes may be
-    derived, all thirteen otherwise; ``sh_top`` = the cloud-free layers above the deck."""
-    from .spectrum import _cloud_free_top
-    sh = inp["approx"]["rt_params"]["SH"]
-    forms = (sh["w_single_form"], sh["w_multi_form"], sh["psingle_form"], sh["w_single_rayleigh"], sh["w_multi_rayleigh"],
-             sh["psingle_rayleigh"], frac_c, sh["single_form"], 0)
-    rayleigh = len(getattr(atm, "rayleigh_molecules", [])) > 0
-    lean = (bool(getattr(atm, "cloud_free", False)) and rayleigh and not opt.all_planes
-            and resident.reflected_SH_can_derive(common["stream"], *forms))
-    if lean:
-        return {"dtau", "w0"}, True, 0
-    sh_top = _cloud_free_top(inp, atm.c.nlayer) if (rayleigh and not opt.all_planes) else 0
-    if not opt.all_planes and resident.reflected_SH_can_derive_levels(atm.c.nlevel, nwno, common["stream"], *forms):
-        return set(_SH_READS), False, sh_top
-    return set(drv.OUT_NAMES), False, sh_top
-
-
-def _plane_set(atm, geom, toon, frac_c, nwno, raman, do_r, do_t, opt):
-    """Which planes compute_opacity writes: exactly ``Spectrum._want_1d``'s choice (see there for the cloud-free form and
-    for the planes the reflected kernels re-derive).  Returns ``(want, lean, derive)``."""
-    ng, nt = geom["num_gangle"], geom["num_tangle"]
-    derive = (do_r and not opt.all_planes
-              and resident.reflected_can_derive(atm.c.nlevel, nwno, ng, nt, geom["ubar0"], geom["ubar1"], geom["cos_theta"],
-                                                toon["single_phase"], toon["multi_phase"], frac_c,
-                                                toon["toon_coefficients"], False))
-    lean = (bool(getattr(atm, "cloud_free", False)) and len(getattr(atm, "rayleigh_molecules", [])) > 0
-            and not opt.all_planes)
-    want = set()
-    if lean:
-        if do_r:
-            want |= {"dtau", "w0"} if derive else {"dtau", "tau", "w0"}
-        if do_t:
-            want |= {"dtau", "w0" if (raman == 2 and do_r) else "w0_no_raman"}
-        return want, lean, derive
-    if do_r:
-        want |= set(resident.REFLECTED_PLANES)
-        if derive:
-            want -= {"tau", "tau_og", "gcos2"}
-    if do_t:
-        want |= {"dtau_og", "w0_no_raman", "cosb_og"}
-    return want, lean, derive
 
 
 def _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, hold):
@@ -158,11 +110,11 @@ def _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt):
                 integrals=integrals, denom=None)
 
 
-def _prepared(c, job, keep, signature):
+def _prepared(c, job, keep):
     """The dictionary ``prepare`` / ``prepare_3d`` return (``finish`` reads it; ``keep`` holds what the job points into)."""
     return dict(table=c["table"], job=job, keep=(keep, c["hold"]), do_r=c["do_r"], do_t=c["do_t"], full=c["full"],
                 nwno=c["nwno"], integrals=c["integrals"], denom=c["denom"] if (c["integrals"] and c["do_r"]) else None,
-                wno=c["wno"], stellar=c["stellar"], inp=c["inp"], atm=c["atm"], opa=c["opa"], signature=signature)
+                wno=c["wno"], stellar=c["stellar"], inp=c["inp"], atm=c["atm"], opa=c["opa"])
 
 
 def _fill_block(k, sub, lo, hi, c):
@@ -249,6 +201,24 @@ def _fill_block_legs(k, sub, lo, hi, c):
             k.trapz_dr = drv._dev(d_wr)
 
 
+def _block_table(opa, subs, plan, linear, ck, slot, signature, make):
+    """The opacity object's block table for this call (``make()`` builds one on a miss).  A table holds raw table
+    addresses, so the key carries the identity of every table of every block: replaced tables are a new signature.  The
+    cache is cleared past 8 entries (40 with the ``slot`` tables of spectra in flight)."""
+    def table_ids(sub):
+        gas = [sub._kappa] if ck else [(sub._mol_log if linear else sub._mol_raw)[m] for m in plan["molecules"]]
+        return tuple(id(t) for t in gas) + tuple(id(sub._cia[p]) for p in plan["cia_pairs"])
+    key = (tuple((lo, hi, id(sub)) + table_ids(sub) for lo, hi, sub in subs), tuple(plan["molecules"]),
+           tuple(plan["cia_pairs"]), linear) + signature + (slot,)
+    cache = opa.__dict__.setdefault("_driver_tables", {})
+    table = cache.get(key)
+    if table is None:
+        if len(cache) > (8 if slot is None else 40):
+            cache.clear()
+        table = cache[key] = make()
+    return table
+
+
 def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
     """Everything up to the C call: set-up, block table (``slot``: which of several tables of the same signature, for
     spectra that are in flight together), per-call pointers, job.  None: outside the driver's scope.  ``early=True`` (what
@@ -270,7 +240,7 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
     if tables and (np.size(cld.wno) != nwno or opt.host_regrid or opa.ngauss != 1 or
                    (len(subs) != 1 and (opt.unfused_opacity or opt.regrid_planes))):
         return None                 # tables on their own grid: interpolated inside each block's fused opacity launch
-    nlevel, nlayer = atm.c.nlevel, atm.c.nlayer
+    nlayer = atm.c.nlayer
     opa.get_opacities(atm, exclude_mol=inp["atmosphere"]["exclude_mol"])
     plan = opa._plan
     ck = bool(plan.get("premixed"))
@@ -284,35 +254,14 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
     ng, nt = geom["num_gangle"], geom["num_tangle"]
     frac_a, frac_b, frac_c = common["TTHG_params"]["fraction"]
     is_sh = inp["approx"]["rt_method"] == "SH"
-    sh_top = 0
-    if is_sh:
-        want, lean, sh_top = _plane_set_sh(inp, atm, nwno, common, frac_c, opt)
-        derive = False
-    elif ck:                        # k-tables: the full set, as Spectrum._want_1d (no aliases, nothing derived)
-        want, lean, derive = set(), False, False
-        if do_r:
-            want |= set(resident.REFLECTED_PLANES)
-        if do_t:
-            want |= {"dtau_og", "w0_no_raman", "cosb_og"}
-    else:
-        want, lean, derive = _plane_set(atm, geom, toon, frac_c, nwno, raman, do_r, do_t, opt)
-
-    def table_ids(sub):          # a block table holds raw table addresses: replaced tables are a new signature
-        if ck:
-            return (id(sub._kappa),) + tuple(id(sub._cia[p]) for p in plan["cia_pairs"])
-        mt = sub._mol_log if linear else sub._mol_raw
-        return tuple(id(mt[m]) for m in plan["molecules"]) + tuple(id(sub._cia[p]) for p in plan["cia_pairs"])
-    key = (tuple((lo, hi, id(sub)) + table_ids(sub) for lo, hi, sub in subs), nlayer, ng, nt, tuple(plan["molecules"]),
-           tuple(plan["cia_pairs"]), tuple(factors[2]), linear, tuple(sorted(want)), lean, not cloud_free and not tables, do_r, do_t,
-           derive, is_sh, opa.ngauss, slot)
-    cache = opa.__dict__.setdefault("_driver_tables", {})
-    table = cache.get(key)
-    if table is None:
-        if len(cache) > (8 if slot is None else 40):
-            cache.clear()
-        table = cache[key] = drv.BlockTable(subs, nlayer, ng, nt, plan["molecules"], plan["cia_pairs"], factors[2], linear,
-                                            want, lean, not cloud_free and not tables, do_r, do_t, _constant_planes, derive,
-                                            sh=is_sh, ngauss=opa.ngauss)
+    choice = planes.choose_1d(inp, atm, nwno, opa.ngauss, calculation, all_planes=opt.all_planes)
+    host_cloud = not cloud_free and not tables
+    # (sh_top is not part of the table: it goes to the job, so SH spectra whose cloud decks differ share one table)
+    table = _block_table(opa, subs, plan, linear, ck, slot, (nlayer, ng, nt, tuple(factors[2]), choice._replace(sh_top=0),
+                                                             host_cloud, do_r, do_t, is_sh, opa.ngauss),
+                         lambda: drv.BlockTable(subs, nlayer, ng, nt, plan["molecules"], plan["cia_pairs"], factors[2],
+                                                linear, choice, host_cloud, do_r, do_t, _constant_planes, sh=is_sh,
+                                                ngauss=opa.ngauss))
     c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt)
     c["clouds"] = _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, c["hold"])
     # The opacity stage first (round 6): as soon as the table rows / weights / coefficients are in the job and the cloud
@@ -323,18 +272,25 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
     for b, (lo, hi, sub) in enumerate(subs):
         c["b"] = b
         _fill_block_opacity(table.blocks[b], sub, lo, hi, c)
-    job, keep = drv.make_job(nlayer, plan, factors, linear, 0 if raman == 1 else nlayer, common["stream"],
-                             common["delta_eddington"], do_r, do_t, ng, nt, geom["ubar0"], geom["ubar1"], geom["cos_theta"],
-                             geom["gweight"], geom["tweight"], toon["single_phase"], toon["multi_phase"],
-                             toon["toon_coefficients"], frac_a, frac_b, frac_c, common["TTHG_params"]["constant_back"],
-                             common["TTHG_params"]["constant_forward"], 0.0, atm.level["temperature"], atm.level["pressure"],
-                             atm.hard_surface, sh=inp["approx"]["rt_params"]["SH"] if is_sh else None, sh_top=sh_top,
-                             gauss_wts=opa.gauss_wts if ck else None,
-                             after_opacity=(lambda j: drv.enqueue(table, j, phase=1)) if early else None)
-    for b, (lo, hi, sub) in enumerate(subs):
-        c["b"] = b
-        _fill_block_legs(table.blocks[b], sub, lo, hi, c)
-    p = _prepared(c, job, keep, key[1:-1])
+    try:                            # (early: the opacity stage goes on the stream inside make_job)
+        job, keep = drv.make_job(nlayer, plan, factors, linear, 0 if raman == 1 else nlayer, common["stream"],
+                                 common["delta_eddington"], do_r, do_t, ng, nt, geom["ubar0"], geom["ubar1"],
+                                 geom["cos_theta"], geom["gweight"], geom["tweight"], toon["single_phase"],
+                                 toon["multi_phase"], toon["toon_coefficients"], frac_a, frac_b, frac_c,
+                                 common["TTHG_params"]["constant_back"], common["TTHG_params"]["constant_forward"], 0.0,
+                                 atm.level["temperature"], atm.level["pressure"], atm.hard_surface,
+                                 sh=inp["approx"]["rt_params"]["SH"] if is_sh else None, sh_top=choice.sh_top,
+                                 gauss_wts=opa.gauss_wts if ck else None,
+                                 after_opacity=(lambda j: drv.enqueue(table, j, phase=1)) if early else None)
+        for b, (lo, hi, sub) in enumerate(subs):
+            c["b"] = b
+            _fill_block_legs(table.blocks[b], sub, lo, hi, c)
+    except BaseException:
+        # hand the table back like run() does after a failed enqueue: abandon clears uncollected result marks, which only
+        # phase 2 sets -- after phase 1 alone there are none, and the call is a defensive no-op
+        drv.abandon(table)
+        raise
+    p = _prepared(c, job, keep)
     p["phase"] = 2 if early else 0
     return p
 
@@ -390,29 +346,10 @@ def prepare_3d(bundle, opa, subs, calculation, opt, slot=None):
     do_r, do_t = "reflected" in legs, "thermal" in legs
     linear = opa.query_method == "linear"
     frac_a, frac_b, frac_c = common["TTHG_params"]["fraction"]
-    want, th3 = set(), ("dtau_og", "w0_no_raman", "cosb_og")
-    if cld3 is None:                # Spectrum._want_3d(clear3=True)
-        if do_r:
-            want |= {"dtau", "w0"}
-        if do_t:
-            th3 = ("dtau", "w0" if (raman == 2 and do_r) else "w0_no_raman", None)
-    elif do_r:
-        want |= set(resident.REFLECTED_PLANES) - {"tau", "tau_og", "gcos2"}
-    if do_t:
-        want |= {k for k in th3 if k is not None}
-
-    def table_ids(sub):
-        mt = sub._mol_log if linear else sub._mol_raw
-        return tuple(id(mt[m]) for m in plan["molecules"]) + tuple(id(sub._cia[p]) for p in plan["cia_pairs"])
-    key = ("3d", tuple((lo, hi, id(sub)) + table_ids(sub) for lo, hi, sub in subs), nlayer, ng, nt, tuple(plan["molecules"]),
-           tuple(plan["cia_pairs"]), tuple(factors[2]), linear, tuple(sorted(want)), th3, do_r, do_t, slot)
-    cache = opa.__dict__.setdefault("_driver_tables", {})
-    table = cache.get(key)
-    if table is None:
-        if len(cache) > (8 if slot is None else 40):
-            cache.clear()
-        table = cache[key] = drv.BlockTable(subs, nlayer, ng, nt, plan["molecules"], plan["cia_pairs"], factors[2], linear,
-                                            want, False, False, do_r, do_t, _constant_planes, facets=nfac, th3=th3)
+    choice = planes.choose_3d(inp, calculation, opt.all_planes)
+    table = _block_table(opa, subs, plan, linear, False, slot, ("3d", nlayer, ng, nt, tuple(factors[2]), choice, do_r, do_t),
+                         lambda: drv.BlockTable(subs, nlayer, ng, nt, plan["molecules"], plan["cia_pairs"], factors[2],
+                                                linear, choice, False, do_r, do_t, _constant_planes, facets=nfac))
     c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt)
     hold = c["hold"]
     for b, (lo, hi, sub) in enumerate(subs):
@@ -431,7 +368,7 @@ def prepare_3d(bundle, opa, subs, calculation, opt, slot=None):
                              toon["single_phase"], toon["multi_phase"], toon["toon_coefficients"], frac_a, frac_b, frac_c,
                              common["TTHG_params"]["constant_back"], common["TTHG_params"]["constant_forward"], 0.0, tl, pv,
                              atm.hard_surface, nfacets=nfac)
-    return _prepared(c, job, (keep, tabs_sig), key[2:-1])
+    return _prepared(c, job, (keep, tabs_sig))
 
 
 def finish(p):

@@ -28,11 +28,10 @@ from ._lib import check, f64, load, ptr
 from .atmsetup import CloudTables
 from .device import DeviceArray, regrid_rows
 from .options import current as _options
+from .planes import OUT_NAMES
 
 _ci, _cd = ctypes.c_int, ctypes.c_double
 AVOGADRO = 6.02214086e+23
-OUT_NAMES = ("dtau", "tau", "w0", "cosb", "ftau_cld", "ftau_ray", "gcos2", "dtau_og", "tau_og",
-             "w0_og", "cosb_og", "w0_no_raman", "f_deltaM")
 
 
 def _convert_array(text):

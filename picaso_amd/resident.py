@@ -10,10 +10,9 @@ import numpy as np
 
 from ._lib import check, f64, load, ptr
 from .device import DeviceArray
+from .planes import REFLECTED_PLANES, SH_PLANES
 
 _ci, _cd = ctypes.c_int, ctypes.c_double
-REFLECTED_PLANES = ("dtau", "tau", "w0", "cosb", "gcos2", "ftau_cld", "ftau_ray", "dtau_og",
-                    "tau_og", "w0_og", "cosb_og")
 
 
 def _addr(x):
@@ -292,10 +291,6 @@ def compress_thermal(ctx, ninner, flux_at_top, gweight, tweight, flux):
     gw, tw = f64(gweight), f64(tweight)
     check(load().picaso_compress_thermal_dev(ctx, ctypes.c_size_t(ninner), _addr(flux_at_top), ptr(gw),
                                              _ci(gw.size), ptr(tw), _ci(tw.size), _addr(flux)), ctx)
-
-
-SH_PLANES = ("dtau", "tau", "w0", "cosb", "ftau_cld", "ftau_ray", "f_deltaM", "dtau_og", "tau_og", "w0_og",
-             "cosb_og")
 
 
 def reflected_SH_can_derive(stream, w_single_form=0, w_multi_form=0, psingle_form=0, w_single_rayleigh=1,

@@ -10,7 +10,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, device, fastsetup, optics, resident
+from . import _lib, device, fastsetup, optics, planes, resident
 from . import options as _options
 from .atmsetup import ATMSETUP, CloudTables
 from .device import DeviceArray
@@ -79,25 +79,6 @@ def _ones(opa, nwno):
         hit.flags.writeable = False
         opa.__dict__["_ones"] = hit
     return hit
-
-
-def _cloud_free_top(inp, nlayer):
-    """Number of layers above the cloud deck: the first layer whose cloud profile rows hold any optical depth or any
-    asymmetry (COSB is the cloud's g0 itself, optics.py:338, so a g0 without optical depth still delta-scales the layer).
-    Read off the profile AS GIVEN (linear regridding keeps a zero row zero); tables larger than 2e5 numbers are not
-    scanned (0: no statement) -- the scan would cost more than it saves."""
-    prof = inp["clouds"]["profile"]
-    if prof is None:
-        return nlayer
-    busy = np.zeros(nlayer, dtype=bool)
-    for k in ("opd", "g0"):
-        v = np.asarray(prof[k], dtype=np.float64)
-        if v.ndim == 0:
-            return 0 if v != 0 else nlayer
-        if v.size > 200000 or v.size % nlayer:
-            return 0
-        busy |= (v.reshape(nlayer, -1) != 0).any(axis=1)
-    return int(np.argmax(busy)) if busy.any() else nlayer
 
 
 def _constant_planes(opa, nlayer, nwno):
@@ -278,7 +259,7 @@ class Spectrum:
         self.fhole = float(inp["clouds"]["fhole"]) if self.do_holes else None
         self.planes = self.planes_clear = self.rplanes = self.planes3d = None
         self.tlev3 = self.plev3 = None
-        self.th3 = ("dtau_og", "w0_no_raman", "cosb_og")
+        self.th3 = None
         self.sh_top = 0
         self.xint = None
         self.returns = {"wavenumber": self.wno}
@@ -308,28 +289,6 @@ class Spectrum:
             _lib.ctx_wait(self.tctx, self.ctx)                         # (in a batch: every member's, so the last one covers the launch)
         return self
 
-    def _want_3d(self, clear3):
-        """Which planes the 3-D legs read.  Only planes that cannot be re-derived exactly inside the solvers are written
-        (each is nfacets x 9 MB at 12 500 wavelengths x 90 layers): the level optical depths are running sums and gcos2
-        is 0.5 ftau_ray, so the reflected kernel takes 8 planes instead of 11; without cloud (and outside the test modes)
-        cosb = cosb_og = ftau_cld = 0, ftau_ray = 1 and the delta-scaling is the identity, which leaves dtau and w0 --
-        and w0_no_raman equals w0 when the Raman factor is the constant 0.99999 (raman='none').  ``all_planes`` writes
-        and reads the full set (A/B, tests)."""
-        want3 = set()
-        calc = self.calculation
-        if "reflected" in calc:
-            if clear3:
-                want3 |= {"dtau", "w0"}
-            elif not self.opt.all_planes:
-                want3 |= set(resident.REFLECTED_PLANES) - {"tau", "tau_og", "gcos2"}
-            else:
-                want3 |= set(resident.REFLECTED_PLANES)
-        if "thermal" in calc:
-            if clear3:
-                self.th3 = ("dtau", "w0" if (self.common["raman"] == 2 and "reflected" in calc) else "w0_no_raman", None)
-            want3 |= {k for k in self.th3 if k is not None}
-        return want3
-
     def _plan_3d(self):
         """justdoit.py:407-471: one atmosphere per facet and the planes of all facets."""
         inp, opa, wno, opt = self.inp, self.opa, self.wno, self.opt
@@ -345,7 +304,8 @@ class Spectrum:
                                  for k in ("opd", "w0", "g0")})
             cld3.pop("wavenumber")
         clear3 = cld3 is None and inp["test_mode"] is None and not opt.all_planes
-        want3 = self._want_3d(clear3)
+        choice = planes.choose_3d(inp, self.calculation, opt.all_planes)
+        want3, self.th3 = choice.want, choice.thermal
         co3 = dict(stream=common["stream"], delta_eddington=common["delta_eddington"], test_mode=inp["test_mode"],
                    raman=common["raman"], clouds_3d=cld3, exclude_mol=inp["atmosphere"]["exclude_mol"], want=want3)
         if opt.facet_loop and self.ngauss == 1:               # A/B: one ATMSETUP + one gas launch per facet
@@ -387,76 +347,6 @@ class Spectrum:
         else:
             self.planes3d = optics.compute_opacity_facets(atm_f, opa, ng, nt, **co3)
 
-    def _want_1d(self, atm):
-        """Which of compute_opacity's 13 planes the legs of a 1-D spectrum read, and under which names.
-
-        Only the planes the requested legs read are written (Toon: 11 for reflected light, 3 for thermal emission, 1 for
-        transmission; the SH solvers take the whole set).  ``derive``: planes the reflected kernels re-derive exactly are
-        not written at all where the launch can do so (default options; resident.reflected_can_derive): tau, tau_og
-        (running sums), gcos2 (0.5 ftau_ray).  ``lean``: cloud-free atmosphere (no cloud profile, no test mode) -- most of
-        the 13 planes are exact copies of others or constants (cosb = cosb_og = ftau_cld = 0, ftau_ray = 1, gcos2 = 0.5,
-        and with cosb = 0 the delta-scaling is the identity: dtau_og = dtau, tau_og = tau, w0_og = w0), so only dtau, tau
-        and w0 are written (0.26 -> 0.09 ms of mixing at 1e5 x 90) and the solvers get the same buffer under several
-        names plus three constant planes kept on the opacity object: same values, hence the same bits, as the full set.
-        ``sh_lean``: SH4 with the reference's default forms, same atmosphere: dtau and w0 are all the cloud-free SH launch
-        reads.  ``sh_top``: a cloud deck -- the layers above it go through the cloud-free SH kernel; a cloudy SH spectrum with
-        the default options leaves out the level planes (running products in the kernel).  Correlated-k tables (Toon),
-        patchy clouds, test modes and ``all_planes`` take the full set."""
-        inp, opt, calc, common, toon = self.inp, self.opt, self.calculation, self.common, self.toon
-        plain = (self.ngauss == 1 and inp["test_mode"] is None and not self.do_holes and not opt.all_planes)
-        rayleigh = len(getattr(atm, "rayleigh_molecules", [])) > 0
-        cloud_free = bool(getattr(atm, "cloud_free", False))
-        self.derive = (not self.is_sh and plain and "reflected" in calc and not self.full_output
-                       and resident.reflected_can_derive(atm.c.nlevel, self.nwno, self.ng, self.nt, self.ubar0, self.ubar1,
-                                                         self.cos_theta, toon["single_phase"], toon["multi_phase"], self.frac[2],
-                                                         toon["toon_coefficients"], atm.get_lvl_flux))
-        self.lean = not self.is_sh and plain and cloud_free and rayleigh
-        self.sh_lean = False
-        self.th_w0 = "w0_no_raman"
-        want = None
-        if self.is_sh:
-            sh_o = self.sh
-            self.sh_lean = (plain and cloud_free and rayleigh and not self.full_output
-                            and resident.reflected_SH_can_derive(
-                                common["stream"], sh_o["w_single_form"], sh_o["w_multi_form"], sh_o["psingle_form"],
-                                sh_o["w_single_rayleigh"], sh_o["w_multi_rayleigh"], sh_o["psingle_rayleigh"], self.frac[2],
-                                sh_o["single_form"], 1 if sh_o["calculate_fluxes"] else 0))
-            if self.sh_lean:
-                want = {"dtau", "w0"}
-            else:
-                if inp["test_mode"] is None and rayleigh and not opt.all_planes:
-                    # (every wavelength block of a sharded spectrum reads the same profile, hence the same statement)
-                    self.sh_top = _cloud_free_top(inp, atm.c.nlayer)
-                # the level planes tau / tau_og are running sums: the default-options launch carries the beam exponentials
-                # as running products instead of reading them, and cosb, gcos2, w0_no_raman are read by no SH solver
-                if (not opt.all_planes and not self.full_output and resident.reflected_SH_can_derive_levels(
-                        atm.c.nlevel, self.nwno * self.ngauss, common["stream"], sh_o["w_single_form"], sh_o["w_multi_form"],
-                        sh_o["psingle_form"], sh_o["w_single_rayleigh"], sh_o["w_multi_rayleigh"], sh_o["psingle_rayleigh"],
-                        self.frac[2], sh_o["single_form"], 1 if (sh_o["calculate_fluxes"] and self.ngauss == 1) else 0)):
-                    want = {"dtau", "w0", "cosb_og", "ftau_cld", "ftau_ray", "f_deltaM", "dtau_og", "w0_og"}
-        elif self.lean:
-            want = set()
-            if "reflected" in calc:
-                want |= {"dtau", "w0"} if self.derive else {"dtau", "tau", "w0"}
-            if "thermal" in calc:
-                self.th_w0 = "w0" if (common["raman"] == 2 and "reflected" in calc) else "w0_no_raman"
-                want |= {"dtau", self.th_w0}
-            if "transmission" in calc:
-                want |= {"dtau"}
-        else:
-            want = set()
-            if "reflected" in calc:
-                want |= set(resident.REFLECTED_PLANES)
-                if self.derive:
-                    want -= {"tau", "tau_og", "gcos2"}
-            if "thermal" in calc:
-                want |= {"dtau_og", "w0_no_raman", "cosb_og"}
-            if "transmission" in calc:
-                want |= {"dtau_og"}
-        if want is not None and not want:            # (None = the whole set, SH) a calculation string that names no leg (full_output of the set-up alone): one plane, no leg reads it
-            want = {"dtau"} if self.lean else {"dtau_og"}
-        return want
-
     def _plan_1d(self):
         """justdoit.py:180-252: ATMSETUP, get_opacities, compute_opacity (and the thinned-cloud set of patchy clouds)."""
         inp, opa, wno, shared = self.inp, self.opa, self.wno, self.shared
@@ -469,29 +359,13 @@ class Spectrum:
             opa._plan = shared["plan"]         # table rows / weights per layer: the same for every wavelength block
         else:
             opa.get_opacities(atm, exclude_mol=inp["atmosphere"]["exclude_mol"])
-        want = self._want_1d(atm)
+        choice = planes.choose_1d(inp, atm, nwno, self.ngauss, self.calculation, self.full_output, self.opt.all_planes)
+        self.sh_top = choice.sh_top
         co_kw = dict(ngauss=self.ngauss, stream=common["stream"], delta_eddington=common["delta_eddington"],
-                     test_mode=inp["test_mode"], raman=common["raman"], full_output=self.full_output, want=want)
-        self.planes = planes = optics.compute_opacity_resident(atm, opa, **co_kw)
-        if self.lean and self.derive:
-            # the reflected kernel gets dtau and w0 only (everything else re-derived); the thermal one its three names
-            zero, _, _ = _constant_planes(opa, nlayer, nwno)
-            self.rplanes = {"dtau": planes["dtau"], "w0": planes["w0"]}
-            planes.update(dtau_og=planes["dtau"], cosb_og=zero)
-            if self.th_w0 == "w0":
-                planes["w0_no_raman"] = planes["w0"]
-        elif self.sh_lean:
-            zero, _, _ = _constant_planes(opa, nlayer, nwno)
-            self.rplanes = {"dtau": planes["dtau"], "w0": planes["w0"]}
-            # (dtau_og: what the transmission leg reads -- without cloud nothing is delta-scaled, dtau_og IS dtau)
-            self.planes = dict(self.rplanes, cosb_og=zero, dtau_og=planes["dtau"])
-        elif self.lean:
-            zero, one, half = _constant_planes(opa, nlayer, nwno)
-            planes.update(dtau_og=planes["dtau"], cosb=zero, cosb_og=zero, ftau_cld=zero, ftau_ray=one, gcos2=half)
-            if "tau" in planes:
-                planes.update(tau_og=planes["tau"], w0_og=planes["w0"])
-            if self.th_w0 == "w0":
-                planes["w0_no_raman"] = planes["w0"]
+                     test_mode=inp["test_mode"], raman=common["raman"], full_output=self.full_output, want=choice.want)
+        # the planes every leg reads and those of the reflected-light kernel (cloud-free: aliases and constant planes)
+        self.planes, self.rplanes = planes.views(choice, optics.compute_opacity_resident(atm, opa, **co_kw),
+                                                 lambda: _constant_planes(opa, nlayer, nwno))
         if self.do_holes:                      # justdoit.py:139-142, 248-252: a second, thinned-cloud column set
             self.planes_clear = optics.compute_opacity_resident(atm, opa, fthin_cld=inp["clouds"]["fthin_cld"],
                                                                 do_holes=True, **co_kw)
@@ -534,7 +408,7 @@ class Spectrum:
         through the same launch sequence, ``(1 - fhole) cloudy + fhole clear`` on the intensities and on the level fluxes,
         then the disk sum of the blend.  Without holes: one fused launch."""
         if not self.do_holes:
-            solve(self.rplanes if (self.rplanes is not None and out is self.xint) else self.planes, out, lvl, True)
+            solve(self.rplanes if out is self.xint else self.planes, out, lvl, True)
             return
         oc = DeviceArray(out.shape, ctx)
         lvc = [DeviceArray(a_.shape, ctx) for a_ in lvl] if lvl else None
@@ -966,12 +840,10 @@ def _reflected_sh(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta
     u0, u1 = f64(ubar0, (ng, nt)), f64(ubar1, (ng, nt))
     gw, tw = f64(gweight), f64(tweight)
     ci, cd = ctypes.c_int, ctypes.c_double
-    names = ("dtau", "tau", "w0", "cosb", "ftau_cld", "ftau_ray", "f_deltaM", "dtau_og", "tau_og",
-             "w0_og", "cosb_og")
     check(load().picaso_get_reflected_SH_top_dev(
         ctx, ci(nlevel), ci(nwno), ctypes.c_long(nwno), ci(ng), ci(nt),
-        *[ptr(planes[k].addr) if planes.get(k) is not None else None for k in names], ptr(rs.addr), ptr(u0), ptr(u1),
-        cd(cos_theta),
+        *[ptr(planes[k].addr) if planes.get(k) is not None else None for k in resident.SH_PLANES], ptr(rs.addr), ptr(u0),
+        ptr(u1), cd(cos_theta),
         ptr(F0PI.addr), ci(sh["w_single_form"]), ci(sh["w_multi_form"]), ci(sh["psingle_form"]),
         ci(sh["w_single_rayleigh"]), ci(sh["w_multi_rayleigh"]), ci(sh["psingle_rayleigh"]),
         cd(frac_a), cd(frac_b), cd(frac_c), cd(constant_back), cd(constant_forward), ci(stream),
