@@ -728,6 +728,23 @@ int picaso_gas_compute_opacity_dev(picaso_ctx *ctx, int nlayer, int nwno, int mo
  * pair may be NULL */
 int picaso_level_sums_dev(picaso_ctx *ctx, int nlayer, long ncol, const double *dtau, double *tau, const double *dtau_og,
                           double *tau_og);
+/* A contribution run (reference picaso/justdoit.py:1090-1294: get_contribution, find_press, built on compute_opacity's
+ * return_mode, optics.py:123-319), one wavelength column per lane, two launches on the context's stream, no
+ * synchronisation.  The gas-table arguments are those of picaso_opacity_gas_ck_dev with one column per wavelength
+ * (correlated-k: nmol = 0, as the reference keeps no per-molecule term for ngauss > 1, optics.py:256-262).
+ *   taus (nspec, nlayer, nwno), nspec = ncont + nmol + 2: each term on its own plane in the reference's insertion order --
+ *        the continuum pairs, the molecules, TAURAY ("rayleigh"), TAUCLD ("cloud") = the device plane taucld (nlayer,
+ *        nwno; NULL: zeros).  Terms are formed as the reference forms its ADDTAU, without contraction.
+ *   cum  (nspec, nlayer + 1, nwno): cum[0] = 0, cum[i + 1] = cum[i] + taus[i], a sequential sum (numba_cumsum);
+ *   p_at (nspec, nwno): numpy.interp(at_tau, cum[:, w], plevel_bar) bit for bit (find_press); plevel_bar = nlayer + 1
+ *        host values (copied on the stream).
+ * cum, p_at and plevel_bar all NULL: the species planes only (compute_opacity(return_mode=True)). */
+int picaso_opacity_contribution_dev(picaso_ctx *ctx, int nlayer, int nwno, int mol_mode, int nmol,
+                                    const double *const *mol_tables, const int *mol_rows, const double *mol_wts,
+                                    const double *mol_fac, int cont_mode, int ncont, const double *const *cont_tables,
+                                    const int *cont_rows, const double *cont_wts, const double *cont_fac, int nray,
+                                    const double *const *ray_tables, const double *ray_fac, const double *taucld,
+                                    const double *plevel_bar, double at_tau, double *taus, double *cum, double *p_at);
 /* 3-D path (reference picaso/justdoit.py:444-471 fills `DTAU_3d[:,:,g,t,:] = dtau` facet by facet):
  * one launch mixes all facets.  taugas, tauray (and raman_factor when non-NULL) are facet-major
  * (nfacets, nlayer, nwno) -- picaso_opacity_gas_dev is called once per facet on its slice -- the cloud

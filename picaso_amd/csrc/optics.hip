@@ -4,9 +4,12 @@
 //  k_opacity_gas     : RetrieveOpacities.get_opacities[_nearest] interpolation arithmetic
 //                      (reference picaso/optics.py:2277-2294, :2350-2351, :2304-2306) fused with
 //                      the TAUGAS / TAURAY sums of compute_opacity (optics.py:144-277)
+//                      -- or, one plane per species, the terms of compute_opacity(return_mode=True) (optics.py:123-319)
+//  k_contribution_columns : cumulative sums and tau-pressure of a contribution run (justdoit.py:1272-1294)
 //  k_compute_opacity : mixing + delta-Eddington half of compute_opacity (optics.py:327-431)
 #include "common.hpp"
 #include "device_math.hpp"
+#include "interp.hpp"
 
 namespace pz {
 
@@ -97,56 +100,6 @@ __device__ __forceinline__ void mix_layer(const MixArgs &a, long q, long qn, dou
     }
 }
 
-// numpy.interp(x, xp, row) for one x against many rows (reference wavelength.regrid, wavelength.py:46-70): the bracket of x
-// in xp once, then per row the slope form numpy evaluates -- shared by k_regrid_rows and the fused gas + mixing launch, so
-// a cloud table interpolated where it is used carries the bits of the regridded plane.
-struct RegridBracket {
-    int j, j0, j1;
-    bool knot;
-    double xv, x0, x1;
-};
-__device__ __forceinline__ RegridBracket regrid_bracket(const double *xp, int nin, double xv)
-{
-    RegridBracket b;
-    const int last = nin - 1;
-    int j;                       // -1: left of the grid, nin: right of it, else xp[j] <= x (< xp[j+1])
-    if (xv != xv) j = -2;
-    else if (xv > xp[last]) j = nin;
-    else if (xv < xp[0]) j = -1;
-    else {
-        int lo = 0, hi = last;   // xp[lo] <= x <= xp[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (xv >= xp[mid]) lo = mid;
-            else hi = mid;
-        }
-        j = (xv >= xp[hi]) ? hi : lo;
-    }
-    const bool edge = (j < 0) || (j >= last);
-    b.j = j;
-    b.j0 = j < 0 ? 0 : (j >= last ? last : j);
-    b.j1 = edge ? b.j0 : b.j0 + 1;
-    b.xv = xv;
-    b.x0 = xp[b.j0];
-    b.x1 = xp[b.j1];
-    b.knot = edge || (b.x0 == xv);
-    return b;
-}
-__device__ __forceinline__ double regrid_value(const double *row, const RegridBracket &b)
-{
-#pragma clang fp contract(off)
-    const double y0 = row[b.j0], y1 = row[b.j1];
-    if (b.j == -2) return b.xv;
-    if (b.knot) return y0;
-    const double slope = (y1 - y0) / (b.x1 - b.x0);
-    double v = slope * (b.xv - b.x0) + y0;
-    if (v != v) {
-        v = slope * (b.xv - b.x1) + y1;
-        if (v != v && y0 == y1) v = y0;
-    }
-    return v;
-}
-
 struct GasArgs {
     int nlayer, nwno, nmol, ncont, nray;
     int ncolper;      // columns per wavelength of the molecular tables / taugas (correlated-k Gauss points)
@@ -161,6 +114,11 @@ struct GasArgs {
     double *taugas, *tauray;  // not written with fuse
     int fuse;                 // 1: mix_layer on every element straight from the sums (picaso_gas_compute_opacity_dev):
     MixArgs mix;              //    TAUGAS / TAURAY never travel through HBM; mix.tau / mix.tau_og must be NULL (k_level_sums)
+    // fuse 3 (species planes, picaso_opacity_contribution_dev; ncolper 1): every term on its own (nlayer, nwno) plane of
+    // `taus` in the order of compute_opacity(return_mode=True) (optics.py:172-319): the ncont continuum pairs, the nmol
+    // molecules, TAURAY, TAUCLD = `taucld` (NULL: zeros)
+    double *taus;
+    const double *taucld;
 };
 
 // One lane per column, LT consecutive layers per thread: neighbouring layers mostly bracket the
@@ -179,9 +137,9 @@ struct GasArgs {
 #ifndef PZ_GAS_XCD
 #define PZ_GAS_XCD 1
 #endif
-template <int FUSE> struct GasTile { static constexpr int LT = FUSE ? PZ_GAS_LT_FUSED : PZ_GAS_LT; };
+template <int FUSE> struct GasTile { static constexpr int LT = (FUSE == 1 || FUSE == 2) ? PZ_GAS_LT_FUSED : PZ_GAS_LT; };
 
-template <int FUSE>      // 0: TAUGAS / TAURAY out; 1: mixing fused in; 2: the cloud-free form of 1
+template <int FUSE>      // 0: TAUGAS / TAURAY out; 1: mixing fused in; 2: the cloud-free form of 1; 3: species planes
 __global__ __launch_bounds__(256) void k_opacity_gas(const GasArgs a)
 {
     constexpr int GAS_LT = GasTile<FUSE>::LT;
@@ -233,7 +191,12 @@ __global__ __launch_bounds__(256) void k_opacity_gas(const GasArgs a)
                     if (q0 != r0) { r0 = q0; v0 = tab[(long)q0 * nw + w]; }
                     k = v0;
                 }
-                tg[l] += k * a.cont_fac[c * a.nlayer + lay];
+                if constexpr (FUSE == 3) {
+#pragma clang fp contract(off)
+                    a.taus[((long)c * a.nlayer + lay) * nw + w] = k * a.cont_fac[c * a.nlayer + lay];   // ADDTAU, :172-227
+                } else {
+                    tg[l] += k * a.cont_fac[c * a.nlayer + lay];
+                }
             }
         }
     }
@@ -263,7 +226,13 @@ __global__ __launch_bounds__(256) void k_opacity_gas(const GasArgs a)
                     if (rq != r[0]) { r[0] = rq; v[0] = tab[(long)rq * ncol + col]; }
                     cx = v[0];
                 }
-                tg[l] += (cx * 6.02214086e+23) * a.mol_fac[m * a.nlayer + lay];    // optics.py:2294, :246-250, :1159
+                if constexpr (FUSE == 3) {
+#pragma clang fp contract(off)
+                    a.taus[((long)(a.ncont + m) * a.nlayer + lay) * nw + w] =
+                        (cx * 6.02214086e+23) * a.mol_fac[m * a.nlayer + lay];     // ADDTAU, optics.py:237-250
+                } else {
+                    tg[l] += (cx * 6.02214086e+23) * a.mol_fac[m * a.nlayer + lay];    // optics.py:2294, :246-250, :1159
+                }
             }
         }
     }
@@ -276,18 +245,40 @@ __global__ __launch_bounds__(256) void k_opacity_gas(const GasArgs a)
         double tr[GAS_LT];
 #pragma unroll
         for (int l = 0; l < GAS_LT; ++l) tr[l] = 0.0;
-        for (int q = 0; q < a.nray; ++q) {
-            const double rv = a.ray_tables[q][w];
+        if constexpr (FUSE == 3) {
+#pragma clang fp contract(off)
+            // TAURAY and TAUCLD, the last two planes (optics.py:265-277, :309-319): each Rayleigh term rounded before it is
+            // added, as the reference's ADDTAU
+            for (int q = 0; q < a.nray; ++q) {
+                const double rv = a.ray_tables[q][w];
 #pragma unroll
-            for (int l = 0; l < GAS_LT; ++l)
-                if (l < nl) tr[l] += rv * a.ray_fac[q * a.nlayer + l0 + l];   // :265-271
+                for (int l = 0; l < GAS_LT; ++l)
+                    if (l < nl) tr[l] = tr[l] + rv * a.ray_fac[q * a.nlayer + l0 + l];
+            }
+            double *ray = a.taus + (long)(a.ncont + a.nmol) * a.nlayer * nw, *cld = ray + (long)a.nlayer * nw;
+#pragma unroll
+            for (int l = 0; l < GAS_LT; ++l) {
+                if (l < nl) {
+                    const long o = (long)(l0 + l) * nw + w;
+                    ray[o] = tr[l];
+                    cld[o] = a.taucld ? a.taucld[o] : 0.0;
+                }
+            }
+            return;
+        } else {
+            for (int q = 0; q < a.nray; ++q) {
+                const double rv = a.ray_tables[q][w];
+#pragma unroll
+                for (int l = 0; l < GAS_LT; ++l)
+                    if (l < nl) tr[l] += rv * a.ray_fac[q * a.nlayer + l0 + l];   // :265-271
+            }
         }
         if constexpr (FUSE == 0) {
 #pragma unroll
             for (int l = 0; l < GAS_LT; ++l)
                 if (l < nl) a.tauray[(long)(l0 + l) * nw + w] = tr[l];
         }
-        if constexpr (FUSE != 0) {
+        if constexpr (FUSE == 1 || FUSE == 2) {
             // (ncolper = 1: col == w.)  The mixing of compute_opacity on the values just formed -- the same function
             // on the same operands as k_compute_opacity reads back from HBM, so the same bits; the level sums, the one
             // thing that runs down a column, are k_level_sums' (tau / tau_og are NULL here).
@@ -369,6 +360,59 @@ __global__ __launch_bounds__(256) void k_level_sums(int nlayer, long ncol, const
         run += d[(long)i * ncol + col];
         t[(long)(i + 1) * ncol + col] = run;
     }
+}
+
+// The column pass of a contribution run (reference justdoit.py:1272-1286, find_press :1289-1294): one lane per (species,
+// wavelength) column, grid.y = species.  Down the column cum[0] = 0, cum[i + 1] = cum[i] + tau[i] (numba_cumsum: a sequential
+// sum), counting the levels with cum <= at_tau on the way; cum is nondecreasing, so they are a prefix and numpy's bracket is
+// that count - 1.  p_at = numpy.interp(at_tau, cum, plevel_bar) by the rules of interp.hpp (knots re-read from the plane just
+// written).  taus (nspec, nlayer, nwno), cum (nspec, nlayer + 1, nwno), p_at (nspec, nwno); plevel_bar nlayer + 1 values.
+struct ContribArgs {
+    int nlayer;
+    long nwno;
+    double at_tau;
+    const double *taus, *plevel;
+    double *cum, *p_at;
+};
+struct StridedKnots {       // knot i of one column of a level plane
+    const double *p;
+    long stride;
+    __device__ __forceinline__ double operator[](int i) const { return p[(long)i * stride]; }
+};
+__global__ __launch_bounds__(256) void k_contribution_columns(const ContribArgs a)
+{
+#pragma clang fp contract(off)
+    const long w = blockIdx.x * (long)blockDim.x + threadIdx.x;
+    if (w >= a.nwno) return;
+    const long nw = a.nwno, nlev = a.nlayer + 1;
+    const double *d = a.taus + (long)blockIdx.y * a.nlayer * nw + w;
+    double *t = a.cum + (long)blockIdx.y * nlev * nw + w;
+    const double x = a.at_tau;
+    double run = 0.0;
+    t[0] = 0.0;
+    int cnt = (run <= x) ? 1 : 0;
+    // eight loads in flight per lane, as k_level_sums
+    int i = 0;
+    for (; i + 8 <= a.nlayer; i += 8) {
+        double v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = d[(long)(i + k) * nw];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            run += v[k];
+            t[(long)(i + k + 1) * nw] = run;
+            cnt += (run <= x) ? 1 : 0;
+        }
+    }
+    for (; i < a.nlayer; ++i) {
+        run += d[(long)i * nw];
+        t[(long)(i + 1) * nw] = run;
+        cnt += (run <= x) ? 1 : 0;
+    }
+    const int nin = (int)nlev;
+    const int j = (x != x) ? -2 : (x > run ? nin : cnt - 1);     // run = cum[last]
+    const RegridBracket b = regrid_bracket_at(j, nin, x, StridedKnots{t, nw});
+    a.p_at[(long)blockIdx.y * nw + w] = regrid_value(a.plevel, b);
 }
 
 __global__ __launch_bounds__(1024) void k_compute_opacity(const MixArgs a_in)
@@ -745,7 +789,7 @@ static int gas_launch(picaso_ctx *ctx, int nlayer, int nwno, int ngauss, int mol
                       const double *const *cont_tables, const int *cont_rows,
                       const double *cont_wts, const double *cont_fac, int nray,
                       const double *const *ray_tables, const double *ray_fac, double *taugas,
-                      double *tauray, const MixArgs *mix)
+                      double *tauray, const MixArgs *mix, double *taus = nullptr, const double *taucld = nullptr)
 {
     if (!ctx) return fail(nullptr, "null context");
     if (nlayer < 1 || nwno < 1 || nmol < 0 || ncont < 0 || nray < 0) return fail(ctx, "opacity_gas: bad sizes");
@@ -795,7 +839,11 @@ static int gas_launch(picaso_ctx *ctx, int nlayer, int nwno, int ngauss, int mol
     a.cont_fac = (const double *)(dc + o_cf);
     a.ray_fac = (const double *)(dc + o_rf);
     a.taugas = taugas; a.tauray = tauray;
-    if (mix) {
+    if (taus) {                      // species planes (k_opacity_gas<3>)
+        if (ngauss != 1) return fail(ctx, "opacity_gas: species planes need one column per wavelength");
+        a.fuse = 3;
+        a.taus = taus; a.taucld = taucld;
+    } else if (mix) {
         const MixArgs &m = *mix;
         const bool lean = !m.taucld && !m.w0c && !m.g0c && !m.cld_nin && !m.test_mode && !m.cosb && !m.ftau_cld && !m.ftau_ray &&
                           !m.gcos2 && !m.dtau_og && !m.w0_og && !m.cosb_og && !m.f_deltaM;
@@ -806,12 +854,13 @@ static int gas_launch(picaso_ctx *ctx, int nlayer, int nwno, int ngauss, int mol
     }
     const int block = 256;
     const long ncol = (long)nwno * ngauss;
-    const int lt = a.fuse ? GasTile<1>::LT : GasTile<0>::LT;
+    const int lt = (a.fuse == 1 || a.fuse == 2) ? GasTile<1>::LT : GasTile<0>::LT;
     a.ncg = (unsigned)((ncol + block - 1) / block);
     a.ntile = (unsigned)((nlayer + lt - 1) / lt);
     if ((double)a.ncg * a.ntile > 2147483647.0) return fail(ctx, "opacity_gas: grid too large");
     dim3 grid(a.ncg * a.ntile);
-    if (a.fuse == 2) hipLaunchKernelGGL(k_opacity_gas<2>, grid, dim3(block), 0, ctx->stream, a);
+    if (a.fuse == 3) hipLaunchKernelGGL(k_opacity_gas<3>, grid, dim3(block), 0, ctx->stream, a);
+    else if (a.fuse == 2) hipLaunchKernelGGL(k_opacity_gas<2>, grid, dim3(block), 0, ctx->stream, a);
     else if (a.fuse == 1) hipLaunchKernelGGL(k_opacity_gas<1>, grid, dim3(block), 0, ctx->stream, a);
     else hipLaunchKernelGGL(k_opacity_gas<0>, grid, dim3(block), 0, ctx->stream, a);
     PZ_HIP(ctx, hipGetLastError());
@@ -828,6 +877,33 @@ int picaso_opacity_gas_ck_dev(picaso_ctx *ctx, int nlayer, int nwno, int ngauss,
 {
     return gas_launch(ctx, nlayer, nwno, ngauss, mol_mode, nmol, mol_tables, mol_rows, mol_wts, mol_fac, cont_mode, ncont,
                       cont_tables, cont_rows, cont_wts, cont_fac, nray, ray_tables, ray_fac, taugas, tauray, nullptr);
+}
+
+int picaso_opacity_contribution_dev(picaso_ctx *ctx, int nlayer, int nwno, int mol_mode, int nmol,
+                                    const double *const *mol_tables, const int *mol_rows, const double *mol_wts,
+                                    const double *mol_fac, int cont_mode, int ncont, const double *const *cont_tables,
+                                    const int *cont_rows, const double *cont_wts, const double *cont_fac, int nray,
+                                    const double *const *ray_tables, const double *ray_fac, const double *taucld,
+                                    const double *plevel_bar, double at_tau, double *taus, double *cum, double *p_at)
+{
+    if (!ctx) return fail(nullptr, "null context");
+    if (nlayer < 1 || nwno < 1 || nmol < 0 || ncont < 0) return fail(ctx, "opacity_contribution: bad sizes");
+    if (!taus) return fail(ctx, "opacity_contribution: null taus");
+    if (!cum != !p_at || (cum && !plevel_bar))
+        return fail(ctx, "opacity_contribution: cum, p_at and plevel_bar go together (all NULL: species planes only)");
+    PZ_TRY(gas_launch(ctx, nlayer, nwno, 1, mol_mode, nmol, mol_tables, mol_rows, mol_wts, mol_fac, cont_mode, ncont,
+                      cont_tables, cont_rows, cont_wts, cont_fac, nray, ray_tables, ray_fac, nullptr, nullptr, nullptr,
+                      taus, taucld));
+    if (!cum) return 0;
+    const void *d_p = nullptr;
+    PZ_TRY(table_upload(ctx, plevel_bar, sizeof(double) * ((size_t)nlayer + 1), &d_p));
+    ContribArgs c{};
+    c.nlayer = nlayer; c.nwno = nwno; c.at_tau = at_tau;
+    c.taus = taus; c.plevel = (const double *)d_p; c.cum = cum; c.p_at = p_at;
+    const unsigned nspec = (unsigned)(ncont + nmol + 2);
+    hipLaunchKernelGGL(k_contribution_columns, dim3((unsigned)((nwno + 255) / 256), nspec), dim3(256), 0, ctx->stream, c);
+    PZ_HIP(ctx, hipGetLastError());
+    return 0;
 }
 
 int picaso_level_sums_dev(picaso_ctx *ctx, int nlayer, long ncol, const double *dtau, double *tau, const double *dtau_og,

@@ -1122,6 +1122,38 @@ ASYNC_DEPTH = 4        # spectra of one opacity object in flight through the C d
 #                        blocks -- per slot; a fifth call first finishes the oldest)
 
 
+@_lib.serialized
+def get_contribution(bundle, opacityclass, at_tau=1, dimension="1d"):
+    """The optical depth of every species, its running sum down the atmosphere and the pressure where that sum reaches
+    ``at_tau`` (reference justdoit.py:1090-1286): "which species shapes this feature, and where does it become optically
+    thick?".  Species: the continuum pairs, the molecules of monochromatic tables (none for correlated-k tables, whose
+    molecular opacity is premixed), ``'rayleigh'``, ``'cloud'`` -- the keys of ``compute_opacity(return_mode=True)`` in
+    its order.  The atmosphere is set up as ``picaso()`` sets it up, then ``opacityclass.get_opacities(atm)``; the per-
+    species planes, the sums and the interpolation run on the GPU (``optics.species_opacity``).
+
+    Returns ``{'taus_per_layer': {species: (nlayer, nwno)}, 'cumsum_taus': {species: (nlevel, nwno)},
+    'tau_p_surface': {species: (nwno,)}}``.  ``tau_p_surface[s]`` is an ndarray of the values the reference returns as a
+    list of floats (``numpy.interp(at_tau, cumsum_taus[s][:, w], pressure_bar)`` per column, bit for bit).  The values
+    of each dictionary are views into one host array.  Only ``dimension='1d'`` (the one the reference documents)."""
+    if dimension != "1d":
+        raise NotImplementedError("get_contribution: only dimension='1d' is supported")
+    opa = opacityclass
+    atm = _setup_atmosphere(bundle.inputs, opa, opa.wno)
+    opa.get_opacities(atm)
+    names, taus, cum, p_at = optics.species_opacity(atm, opa, at_tau=at_tau)
+    t, c, p = taus.to_host(), cum.to_host(), p_at.to_host()
+    return {"taus_per_layer": {k: t[i] for i, k in enumerate(names)},
+            "cumsum_taus": {k: c[i] for i, k in enumerate(names)},
+            "tau_p_surface": {k: p[i] for i, k in enumerate(names)}}
+
+
+def find_press(at_tau, a, b, c):
+    """Pressure where the cumulative optical depth ``a`` ``(nlevel, nwno)`` reaches ``at_tau`` in each of the first ``b``
+    columns, on the level pressures ``c`` (reference justdoit.py:1289-1294): a list of floats.  ``get_contribution``
+    computes the same on the GPU."""
+    return [np.interp([at_tau], a[:, iw], c)[0] for iw in range(b)]
+
+
 class PendingSpectrum:
     """Handle of ``picaso_async`` / ``inputs.spectrum_async``: ``result()`` (or calling it) waits for this spectrum's result
     copies, forms the output dictionary -- ``spectrum()``'s, bit for bit -- and returns it (the same object every time)."""

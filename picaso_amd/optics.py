@@ -711,10 +711,10 @@ def _ptr_array(devs):
     return ctypes.cast(arr, ctypes.POINTER(ctypes.POINTER(ctypes.c_double)))
 
 
-def _gas_call(opa, nlayer, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac,
-              ray_tabs, ray_fac, taugas, tauray, mol_mode=None, cont_wts=None, ngauss=1, mix=None):
-    """``picaso_opacity_gas_ck_dev``: gather + interpolate table rows into TAUGAS / TAURAY.
-    ``mol_mode`` 0 nearest, 1 log10-bilinear (monochromatic 'linear'), 2 ln-bilinear (premixed CK);
+def _gas_args(opa, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac, ray_tabs, ray_fac,
+              mol_mode=None, cont_wts=None):
+    """The gas-table arguments of ``picaso_opacity_gas_ck_dev`` from ``mol_mode`` to ``ray_fac`` (the ctypes pointers
+    hold their arrays).  ``mol_mode`` 0 nearest, 1 log10-bilinear (monochromatic 'linear'), 2 ln-bilinear (premixed CK);
     ``cont_wts`` given -> log-linear continuum between two rows per layer (CK)."""
     ip = ctypes.POINTER(ctypes.c_int)
 
@@ -729,11 +729,18 @@ def _gas_call(opa, nlayer, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont
     cw = f64(cont_wts) if cont_wts is not None else None
     cf = f64(cont_fac) if cont_fac is not None else None
     rf = f64(ray_fac) if ray_fac is not None else None
-    gas_args = (_ci(mol_mode),
-                _ci(len(mol_tabs)), _ptr_array(mol_tabs), mr.ctypes.data_as(ip) if mr is not None else None,
-                ptr(mw), ptr(mf), _ci(1 if cw is not None else 0), _ci(len(cont_tabs)), _ptr_array(cont_tabs),
-                cr.ctypes.data_as(ip) if cr is not None else None, ptr(cw), ptr(cf), _ci(len(ray_tabs)),
-                _ptr_array(ray_tabs), ptr(rf))
+    return (_ci(mol_mode),
+            _ci(len(mol_tabs)), _ptr_array(mol_tabs), mr.ctypes.data_as(ip) if mr is not None else None,
+            ptr(mw), ptr(mf), _ci(1 if cw is not None else 0), _ci(len(cont_tabs)), _ptr_array(cont_tabs),
+            cr.ctypes.data_as(ip) if cr is not None else None, ptr(cw), ptr(cf), _ci(len(ray_tabs)),
+            _ptr_array(ray_tabs), ptr(rf))
+
+
+def _gas_call(opa, nlayer, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac,
+              ray_tabs, ray_fac, taugas, tauray, mol_mode=None, cont_wts=None, ngauss=1, mix=None):
+    """``picaso_opacity_gas_ck_dev``: gather + interpolate table rows into TAUGAS / TAURAY (arguments: ``_gas_args``)."""
+    gas_args = _gas_args(opa, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac, ray_tabs, ray_fac,
+                         mol_mode=mol_mode, cont_wts=cont_wts)
     if mix is not None:       # gas stage + compute_opacity in one launch (ngauss = 1): `mix` = the mixing's arguments
         check(load().picaso_gas_compute_opacity_dev(opa.ctx, _ci(nlayer), _ci(opa.nwno), *gas_args, *mix), opa.ctx)
         return
@@ -811,23 +818,29 @@ def gas_stage(atm, opa, taugas, tauray, mix=None):
     if fac is None or fac[0] is not atm.layer["mixingratios"]:
         fac = (atm.layer["mixingratios"], _layer_factors(atm, opa))
         pl["_factors"] = fac
-    mol_fac, cont_fac, ray_names, ray_fac = fac[1]
+    _gas_call(opa, nlayer, taugas=taugas, tauray=tauray, ngauss=ngauss, mix=mix, **_gas_tables(opa, fac[1]))
+
+
+def _gas_tables(opa, factors, molecules=True):
+    """The tables, rows, weights and per-layer coefficients of ``opa._plan`` as keyword arguments of ``_gas_call`` /
+    ``_gas_args``; ``factors`` = ``_layer_factors``.  ``molecules=False``: without the molecular term."""
+    pl = opa._plan
+    mol_fac, cont_fac, ray_names, ray_fac = factors
     cont_tabs = [opa._cia[p] for p in pl["cia_pairs"]]
-    if pl.get("premixed"):
+    if not molecules:
+        mol_tabs, mol_mode = [], 0
+    elif pl.get("premixed"):
         mol_tabs, mol_mode = [pl.get("table", opa._kappa)], 2
-        cont_rows = np.repeat(pl["cia_rows"][None], len(cont_tabs), axis=0) if cont_tabs else None
-        cont_wts = np.repeat(pl["cia_wts"][None], len(cont_tabs), axis=0) if cont_tabs else None
     else:
         mol_tabs = [(opa._mol_log if opa.query_method == "linear" else opa._mol_raw)[m]
                     for m in pl["molecules"]]
         mol_mode = 1 if opa.query_method == "linear" else 0
-        cont_rows = np.repeat(pl["cia_rows"][None], len(cont_tabs), axis=0) if cont_tabs else None
-        cont_wts = None
-    _gas_call(opa, nlayer, mol_tabs, pl["rows"] if mol_tabs else None,
-              pl["wts"] if mol_tabs else None, mol_fac if mol_tabs else None, cont_tabs, cont_rows,
-              cont_fac if cont_tabs else None, [opa._ray[m] for m in ray_names],
-              ray_fac if ray_names else None, taugas, tauray, mol_mode=mol_mode, cont_wts=cont_wts,
-              ngauss=ngauss, mix=mix)
+    cont_rows = np.repeat(pl["cia_rows"][None], len(cont_tabs), axis=0) if cont_tabs else None
+    cont_wts = np.repeat(pl["cia_wts"][None], len(cont_tabs), axis=0) if cont_tabs and pl.get("premixed") else None
+    return dict(mol_tabs=mol_tabs, mol_rows=pl["rows"] if mol_tabs else None, mol_wts=pl["wts"] if mol_tabs else None,
+                mol_fac=mol_fac if mol_tabs else None, cont_tabs=cont_tabs, cont_rows=cont_rows,
+                cont_fac=cont_fac if cont_tabs else None, ray_tabs=[opa._ray[m] for m in ray_names],
+                ray_fac=ray_fac if ray_names else None, mol_mode=mol_mode, cont_wts=cont_wts)
 
 
 def types_namespace_layer(atm_f, tlayer):
@@ -1494,13 +1507,71 @@ def compute_opacity(atmosphere, opacityclass, ngauss=1, stream=2, delta_eddingto
     ``(nlayer|nlevel, nwno, ngauss)``.  As in the reference, any ``test_mode`` other than ``None`` --
     including the signature default ``False`` -- selects a Dlugach test mode (optics.py:372);
     ``picaso()`` passes ``inputs['test_mode']``, which defaults to ``None``."""
-    if plot_opacity or return_mode:
-        raise Exception("plot_opacity / return_mode are plotting aids of the reference and are "
-                        "not part of the accelerated path")
+    if plot_opacity:
+        raise Exception("plot_opacity is a plotting aid of the reference and is not part of the accelerated path")
+    if return_mode:             # optics.py:123-319: {species: (nlayer, nwno)} in the reference's insertion order
+        if ngauss != opacityclass.ngauss:
+            raise Exception("compute_opacity: ngauss=%d but the opacity tables have %d Gauss points"
+                            % (ngauss, opacityclass.ngauss))
+        names, taus, _, _ = species_opacity(atmosphere, opacityclass, fthin_cld=fthin_cld, do_holes=do_holes)
+        h = taus.to_host()
+        return {k: h[i] for i, k in enumerate(names)}
     d = compute_opacity_resident(atmosphere, opacityclass, ngauss=ngauss, stream=stream,
                                  delta_eddington=delta_eddington, test_mode=test_mode, raman=raman,
                                  fthin_cld=fthin_cld, do_holes=do_holes, full_output=full_output)
     return tuple(d[k].to_host().reshape(d[k].shape[:2] + (ngauss,)) for k in OUT_NAMES)
+
+
+def species_names(opacityclass):
+    """The keys of ``compute_opacity(return_mode=True)`` in the reference's insertion order (optics.py:172-319): the
+    continuum pairs (``m[0]+m[1]``), the molecules of monochromatic tables (correlated-k tables have no per-molecule
+    term, :256-262), ``'rayleigh'``, ``'cloud'``."""
+    pl = opacityclass._plan
+    mols = [] if pl.get("premixed") else list(pl["molecules"])
+    return list(pl["cia_pairs"]) + mols + ["rayleigh", "cloud"]
+
+
+def _cloud_opd_device(atm, opa, fthin_cld=None, do_holes=False):
+    """TAUCLD (optics.py:309-315) as an ``(nlayer, nwno)`` device plane, or None for a cloud-free atmosphere (read as
+    zeros).  Tables on their own grid are regridded on the device (``regrid_rows``: numpy.interp's bits)."""
+    if getattr(atm, "cloud_free", False):
+        return None
+    cld = atm.layer["cloud"]
+    nlayer, nwno = atm.c.nlayer, opa.nwno
+    if isinstance(cld, CloudTables) and np.size(cld.wno) == nwno and not _options().host_regrid:
+        return regrid_rows(cld.in_wno, cld.compact["opd"], _wno_device(opa, cld.wno), opa.ctx,
+                           scale=fthin_cld if do_holes else None)
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(cld["opd"], dtype=float), (nlayer, nwno)))
+    return DeviceArray.from_host(fthin_cld * t if do_holes else t, opa.ctx)
+
+
+def species_opacity(atmosphere, opacityclass, at_tau=None, fthin_cld=None, do_holes=False):
+    """The optical depth of every species on its own plane (``compute_opacity(return_mode=True)``, optics.py:123-319) and,
+    with ``at_tau``, the cumulative sums down every column and the pressure [bar] where each reaches ``at_tau``
+    (``get_contribution``, justdoit.py:1272-1294), by ``picaso_opacity_contribution_dev``.  Returns ``(names, taus, cum,
+    p_at)``: DeviceArrays ``(nspecies, nlayer, nwno)``, ``(nspecies, nlevel, nwno)``, ``(nspecies, nwno)`` (the last two
+    None without ``at_tau``), enqueued on the context's stream.  Call ``opacityclass.get_opacities(atmosphere)`` first.
+    The plan's coefficient cache (``gas_stage``) is neither read nor written."""
+    atm, opa = atmosphere, opacityclass
+    ctx = opa.ctx
+    nlayer, nwno = atm.c.nlayer, opa.nwno
+    pl = opa._plan
+    if pl is None or pl["nlayer"] != nlayer:
+        raise Exception("call opacityclass.get_opacities(atmosphere) first")
+    names = species_names(opa)
+    gas = _gas_args(opa, **_gas_tables(opa, _layer_factors(atm, opa), molecules=not pl.get("premixed")))
+    d_cld = _cloud_opd_device(atm, opa, fthin_cld, do_holes)
+    taus = DeviceArray((len(names), nlayer, nwno), ctx)
+    cum = p_at = plev = None
+    if at_tau is not None:
+        cum, p_at = DeviceArray((len(names), nlayer + 1, nwno), ctx), DeviceArray((len(names), nwno), ctx)
+        plev = f64(np.asarray(atm.level["pressure"], dtype=float) / atm.c.pconv)
+    check(load().picaso_opacity_contribution_dev(
+        ctx, _ci(nlayer), _ci(nwno), *gas, ptr(d_cld.addr) if d_cld is not None else None, ptr(plev),
+        _cd(float(at_tau) if at_tau is not None else 0.0), ptr(taus.addr), ptr(cum.addr) if cum is not None else None,
+        ptr(p_at.addr) if p_at is not None else None), ctx)
+    taus._inputs = d_cld                 # the launch is asynchronous: its input lives as long as its output
+    return names, taus, cum, p_at
 
 
 # ------------------------------------------------------------------------------------------------
