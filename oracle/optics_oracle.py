@@ -3,12 +3,15 @@
 Restates, from plain arrays (no sqlite, no classes):
   * interp_molecular : RetrieveOpacities.get_opacities / get_opacities_nearest arithmetic
                        (reference picaso/optics.py:2277-2294, :2350-2351)
+  * nearest_molecular, continuum_nearest : the nearest-row queries (optics.py:2298-2306, 2330-2351)
+  * coef1, gas_sums  : the TAUGAS / TAURAY sums and their species terms (optics.py:144-277)
   * compute_opacity  : reference picaso/optics.py:26-431 (TAUGAS/TAURAY sums :144-277, Raman
                        clip :294, mixing :327-354, test_mode :372-399, delta-Eddington :401-431)
   * pre_mix_ck       : RetrieveCKs.get_pre_mix_ck (optics.py:1081-1161), premixed correlated-k
   * continuum_ck     : RetrieveCKs.get_continuum interpolation (optics.py:1411-1428, 1470-1491)
 Pinned against tests/golden/optics.npz (outputs of the reference's own source on the synthetic DB
-tests/golden/synthetic_opacities.db) by tests/test_oracle_golden.py.
+tests/golden/synthetic_opacities.db) by tests/test_oracle_golden.py and tests/test_optics.py, and
+against tests/golden/ck.npz by tests/test_ck_optics.py.
 """
 import numpy as np
 
@@ -26,6 +29,62 @@ def interp_molecular(rows4, t_interp, p_interp, i_ll, i_hl, i_hh, i_lh):
                     ((t) * (p) * lg[i_hh[ind]]) + ((1 - t) * (p) * lg[i_lh[ind]]))
         out[ind] = cx * AVOGADRO
     return out
+
+
+def nearest_molecular(rows, pt_pairs, player_bar, tlayer):
+    """get_opacities_nearest (reference optics.py:2330-2351): per layer the (P,T) point closest in
+    (ln P, T), its 0-based row of ``rows`` (npt, nwno; ``pt_pairs`` (ptid, P, T) in row order) times
+    N_A.  Returns the plane (nlayer, nwno) and the chosen ptids."""
+    ids = [min(pt_pairs, key=lambda c: np.hypot(np.log(c[1]) - np.log(p), c[2] - t))[0]
+           for p, t in zip(player_bar, tlayer)]
+    row = {pid: i for i, (pid, _, _) in enumerate(pt_pairs)}
+    return rows[[row[i] for i in ids]] * AVOGADRO, np.array(ids)
+
+
+def continuum_nearest(tlayer, cia_temps, table):
+    """get_continuum of RetrieveOpacities (reference optics.py:2298-2306): the row of the CIA
+    temperature nearest to each layer's; ``table`` (n_cia_temps, nwno) in ``cia_temps`` order."""
+    st = np.asarray(cia_temps, dtype=float)
+    return table[[int(np.abs(st - t).argmin()) for t in tlayer]]
+
+
+def coef1(tlevel, plevel_bar, gravity_cgs, mmw, rgas=8.31446261815324):
+    """COEF1 of the collision-induced pairs (reference optics.py:156-168), per layer."""
+    t, p = np.asarray(tlevel, dtype=float), np.asarray(plevel_bar, dtype=float)
+    tlayer = 0.5 * (t[1:] + t[:-1])
+    A = (tlayer / (t[:-1] * t[1:])) * (t[1:] * p[1:] - t[:-1] * p[:-1]) / (p[1:] - p[:-1])
+    B = (tlayer / (t[:-1] * t[1:])) * (t[:-1] - t[1:]) / (p[1:] - p[:-1])
+    return rgas * 273.15 ** 2 * .5E5 * (A * (p[1:] ** 2 - p[:-1] ** 2) + B * (2. / 3.) * (
+        p[1:] ** 3 - p[:-1] ** 3)) / (1.01325 ** 2 * (gravity_cgs / 100.0) * tlayer * mmw)
+
+
+def gas_sums(colden, mmw, mix, coef, continuum=(), molecular=(), rayleigh=(), premixed=None):
+    """TAUGAS / TAURAY of compute_opacity (reference optics.py:144-277) from the per-layer opacities.
+
+    ``continuum``: ((a, b), (nlayer, nwno) continuum_opa) pairs; ``molecular``: (name, (nlayer, nwno)
+    molecular_opa) of monochromatic tables; ``premixed``: the (nlayer, nwno, ngauss) molecular_opa of a
+    correlated-k table; ``rayleigh``: (name, sigma(nwno)); ``mix``: name -> per-layer mixing ratio.
+    In the reference's order: continuum pairs, molecules, Rayleigh.  Returns ``(taugas, tauray, terms)``:
+    taugas (nlayer, nwno[, ngauss]), tauray (nlayer, nwno) and every term on its own plane keyed as
+    compute_opacity(return_mode=True) keys it (:172-277; no molecule keys for correlated-k)."""
+    colden, mmw = np.asarray(colden, dtype=float), np.asarray(mmw, dtype=float)
+    nlayer = colden.size
+    nwno = np.shape([x for _, x in list(continuum) + list(molecular) + list(rayleigh)][0])[-1]
+    terms = {}
+    taugas = np.zeros((nlayer, nwno))
+    for (a, b), opa in continuum:                                   # :224-227
+        terms[a + b] = opa * (coef * mix[a] * mix[b])[:, None]
+        taugas += terms[a + b]
+    for m, opa in molecular:                                        # :246-250
+        terms[m] = opa * (colden * mix[m] / mmw)[:, None]
+        taugas += terms[m]
+    if premixed is not None:                                        # :232-233, :256-262
+        taugas = taugas[:, :, None] + premixed * (colden / mmw)[:, None, None]
+    tauray = np.zeros((nlayer, nwno))
+    for m, sigma in rayleigh:                                       # :265-271
+        tauray += np.asarray(sigma, dtype=float)[None, :] * (colden * mix[m] / mmw)[:, None]
+    terms["rayleigh"] = tauray
+    return taugas, tauray, terms
 
 
 def compute_opacity(taugas, tauray, taucld, w0_cld, g0_cld, raman_factor, stream=2,

@@ -1236,12 +1236,15 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
     mol_mode = 1 if opa.query_method == "linear" else 0
     cont_tabs = [opa._cia[p] for p in pl["cia_pairs"]]
     ray_tabs = [opa._ray[m] for m in ray_names]
-    # the Raman factor: none (the constant), Pollack's row for every layer and facet, or Oklopcic's plane per facet
+    # the Raman factor: none (the constant), Pollack's row for every layer and facet, or Oklopcic's plane per facet.
+    # rf_rows = nlayer: a facet-major plane, of which every chunk of facets reads its own rows.  Pollack's factor is read
+    # as one row (rf_rows = 0) also when raman_device hands over a host-made (nlayer, nwno) plane (PICASO_AMD_RAMAN_PLANES):
+    # all its rows are that row, and the plane has no rows for the facets of a second chunk
     d_rf, rf_rows = None, 0
     if raman == 1:
-        d_rf, rf_rows = raman_device(atm_f, opa, 1)
+        d_rf = raman_device(atm_f, opa, 1)[0]
     elif raman == 0:
-        d_rf = DeviceArray((nfac, nlayer, nwno), ctx)
+        d_rf, rf_rows = DeviceArray((nfac, nlayer, nwno), ctx), nlayer
         tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float), (nlayer, nfac))
         raman_oklopcic_device(opa, np.ascontiguousarray(tl.T).ravel(), d_rf)      # all facets in one launch
     out = {k: DeviceArray((nfac, nlayer, nwno), ctx) for k in OUT_NAMES if k in want}
@@ -1261,7 +1264,7 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
                 d_fp = keep = DeviceArray.from_host(np.ascontiguousarray(h_tall[:, sl].reshape(3 * nl_c, nin)), ctx)
             cld_tab = (_ci(nin), ptr(d_xp.addr), ptr(d_fp.addr), ptr(_wno_device(opa, opa.wno).addr))
         mix = (None, None, None,
-               ptr(d_rf.addr + (off if rf_rows else 0)) if d_rf is not None else None, _ci(nl_c if (d_rf is not None and raman == 0) else 0),
+               ptr(d_rf.addr + (off if rf_rows else 0)) if d_rf is not None else None, _ci(nl_c if rf_rows else 0),
                _cd(0.99999), _ci(0), _ci(1 if delta_eddington else 0), _ci(stream),
                *[ptr(out[k].addr + off) if k in out else None for k in OUT_NAMES], _ci(0), *cld_tab)
         if keep is not None:
@@ -1365,8 +1368,8 @@ def compute_opacity_facet_major_ck(atm_f, opacityclass, numg, numt, stream=2, de
                   taugas.row_block(f0), tauray.row_block(f0), mol_mode=2, cont_wts=cont_wts, ngauss=ngauss)
     # the Raman factor: none (the constant), Pollack's row for every layer and facet, or Oklopcic's plane per facet
     d_rf, rf_rows = None, 0
-    if raman == 1:
-        d_rf, rf_rows = raman_device(atm_f, opa, 1)
+    if raman == 1:                       # one row, also from a host-made plane (see compute_opacity_facet_major)
+        d_rf = raman_device(atm_f, opa, 1)[0]
     elif raman == 0:
         d_rf, rf_rows = DeviceArray((nfac, nlayer, nwno), ctx), nlayer
         tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float).reshape(nlayer, -1), (nlayer, nfac))

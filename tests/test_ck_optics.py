@@ -70,13 +70,10 @@ def test_oracle_ck_against_reference(ck, og):
         tab = np.stack([cont[a + b][t] for t in st])
         cont_opa[a + b] = oo.continuum_ck(L["tlayer"], st, tab)
         assert _close(cont_opa[a + b], ck["continuum_opa/" + a + b], 1e-12), a + b
-    taugas = np.zeros(mol.shape)
-    for a, b in PAIRS:                                           # optics.py:172-237
-        taugas += (cont_opa[a + b] * (L["COEF1"] * L["mix"][a] * L["mix"][b])[:, None])[:, :, None]
-    taugas += mol * (L["colden"] / L["mmw"])[:, None, None]       # optics.py:256-262
-    tauray = np.zeros(mol.shape[:2])
-    for m in ("H2", "He", "CH4", "H2O"):
-        tauray += ray[m][None, :] * (L["colden"] * L["mix"][m] / L["mmw"])[:, None]
+    taugas, tauray, terms = oo.gas_sums(L["colden"], L["mmw"], L["mix"], L["COEF1"],
+                                        continuum=[((a, b), cont_opa[a + b]) for a, b in PAIRS], premixed=mol,
+                                        rayleigh=[(m, ray[m]) for m in ("H2", "He", "CH4", "H2O")])
+    assert taugas.shape == mol.shape and list(terms) == ["H2H2", "H2He", "H2CH4", "rayleigh"]
     b3 = lambda x: x[:, :, None]
     for key in CASES:
         de, s = bool(int(key[2])), int(key[-1])

@@ -340,10 +340,23 @@ def test_config4_full_size_on_one_gpu(oracle, monkeypatch):
     # wavelength blocks read back from the resident planes: [0, 8), [49 996, 50 004), [99 992, 1e5)
     g, gw, t, tw = disco.get_angles_3d(ng, nt)
     u0, u1, ct, _, _ = disco.compute_disco(ng, nt, g, t, np.pi / 3)
-    for lo, hi in ((0, 8), (nwno // 2 - 4, nwno // 2 + 4), (nwno - 8, nwno)):
+    blocks = ((0, 8), (nwno // 2 - 4, nwno // 2 + 4), (nwno - 8, nwno))
+    # the opacity values of those blocks against the numpy reference of every facet's profile (test_opacity_shapes_gpu:
+    # the synthetic tables evaluated at the blocks' wavelengths only)
+    from test_opacity_shapes_gpu import Tables, _facets, _rel, reference_gas, reference_planes
+    cols = np.concatenate([np.arange(lo, hi) for lo, hi in blocks])
+    T = Tables(cols.size, wno=opa.wno[cols])
+    cld = {k: v[:, cols] for k, v in syn.cloud_slab(NLAYER, nwno).items()}
+    ref = [reference_planes(*reference_gas(a, T)[:2], cld) for a in _facets(T, NLAYER, ng, nt)[1]]
+    j = 0
+    for lo, hi in blocks:
         n = hi - lo
         sub = [kept[k].columns_to_host(lo, hi) for k in PLANES]            # (rows, n, 8, 8)
         assert 8 * ((sub[0].shape[0] - 1) * nwno + lo) * nfac > 2 ** 32    # the last layers lie beyond 4 GiB
+        for k, a in zip(PLANES, sub):
+            for f in range(nfac):
+                _rel(a[:, :, f // nt, f % nt], ref[f][k][:, j:j + n], 1e-12, ("config4/planes", k, lo))
+        j += n
         xo = oracle.get_reflected_3d(nlevel, opa.wno[lo:hi], n, ng, nt, *sub, np.full(n, 0.1), u0, u1, float(ct),
                                      np.ones(n), 3, 0, *TTHG)
         xo = xo[0] if isinstance(xo, tuple) else xo

@@ -15,6 +15,7 @@ DB = os.path.join(GOLDEN, "synthetic_opacities.db")
 # molecular weights as the reference's ATMSETUP.get_weights gives them (main-isotope masses), from the fixture
 _G = np.load(os.path.join(GOLDEN, "optics.npz"))
 WEIGHTS = {k: float(_G["in/weight/" + k]) for k in ("H2", "He", "H2O", "CH4")}
+PAIRS = (("H2", "H2"), ("H2", "He"), ("H2", "CH4"))
 CASES = ("de1_s2_r2_tmnone", "de0_s2_r2_tmnone", "de1_s4_r0_tmnone", "de1_s2_r2_tmrayleigh",
          "de0_s2_r2_tmconstant_tau", "de1_s2_r1_tmnone")
 
@@ -75,39 +76,43 @@ def _case_args(key):
     return bool(int(de[2])), int(s[1]), int(r[1]), (None if tm == "tmnone" else tm[2:])
 
 
+def _gold_layers(gold):
+    """per-layer inputs of the TAUGAS / TAURAY sums of the fixture's atmosphere"""
+    from oracle import optics_oracle as oo
+    t = gold["in/tlevel"]
+    mix = {k: 0.5 * (gold["in/mix/" + k][1:] + gold["in/mix/" + k][:-1]) for k in WEIGHTS}
+    mmw_l = sum(gold["in/mix/" + k] * WEIGHTS[k] for k in WEIGHTS)
+    mmw = 0.5 * (mmw_l[1:] + mmw_l[:-1])
+    p = gold["in/plevel_bar"]
+    return dict(mix=mix, mmw=mmw, colden=gold["in/colden"],   # colden as the reference's ATMSETUP gives it
+                tlayer=0.5 * (t[1:] + t[:-1]), player=np.sqrt(p[1:] * p[:-1]),
+                coef=oo.coef1(t, p, float(gold["in/gravity"]), mmw))
+
+
+def _db_rayleigh():
+    import sqlite3
+    from picaso_amd import optics as px
+    conn = sqlite3.connect(DB)
+    ray = {m: px._convert_array(b) for m, b in conn.execute("SELECT molecule, opacity FROM rayleigh")}
+    conn.close()
+    return [(m, ray[m]) for m in ("H2", "He", "CH4", "H2O")]
+
+
 def test_oracle_compute_opacity(gold, pollack_table):
-    """oracle mixing algebra vs the reference: rebuild TAUGAS/TAURAY from the reference's own
+    """oracle mixing algebra vs the reference: rebuild TAUGAS/TAURAY (oracle.gas_sums) from the reference's own
     molecular/continuum planes, then compare all 13 outputs."""
     from oracle import optics_oracle as oo
     from picaso_amd import optics as px
     wno = gold["in/wno"]
     nlevel = len(gold["in/tlevel"])
-    p = gold["in/plevel_bar"] * 1e6
-    t = gold["in/tlevel"]
-    mix = {k: 0.5 * (gold["in/mix/" + k][1:] + gold["in/mix/" + k][:-1]) for k in WEIGHTS}
-    mmw_l = sum(gold["in/mix/" + k] * WEIGHTS[k] for k in WEIGHTS)
-    mmw = 0.5 * (mmw_l[1:] + mmw_l[:-1])
-    g = float(gold["in/gravity"])
-    colden = gold["in/colden"]               # as the reference's ATMSETUP gives it (half-gravity end layers)
-    tlayer = 0.5 * (t[1:] + t[:-1])
-    plev = p / 1e6
-    A = (tlayer / (t[:-1] * t[1:])) * (t[1:] * plev[1:] - t[:-1] * plev[:-1]) / (plev[1:] - plev[:-1])
-    B = (tlayer / (t[:-1] * t[1:])) * (t[:-1] - t[1:]) / (plev[1:] - plev[:-1])
-    COEF1 = 8.31446261815324 * 273.15 ** 2 * .5E5 * (A * (plev[1:] ** 2 - plev[:-1] ** 2) + B * (2. / 3.) * (
-        plev[1:] ** 3 - plev[:-1] ** 3)) / (1.01325 ** 2 * (g / 100.0) * tlayer * mmw)
-    import sqlite3
-    conn = sqlite3.connect(DB)
-    ray = {m: px._convert_array(b) for m, b in conn.execute("SELECT molecule, opacity FROM rayleigh")}
-    conn.close()
+    L = _gold_layers(gold)
+    tlayer = L["tlayer"]
+    ray = _db_rayleigh()
     for qm in ("nearest", "linear"):
-        taugas = np.zeros((nlevel - 1, len(wno)))
-        for a, b in (("H2", "H2"), ("H2", "He"), ("H2", "CH4")):
-            taugas += gold["%s/continuum_opa/%s" % (qm, a + b)] * (COEF1 * mix[a] * mix[b])[:, None]
-        for m in ("H2O", "CH4", "H2"):
-            taugas += gold["%s/molecular_opa/%s" % (qm, m)] * (colden * mix[m] / mmw)[:, None]
-        tauray = np.zeros_like(taugas)
-        for m in ("H2", "He", "CH4", "H2O"):
-            tauray += ray[m][None, :] * (colden * mix[m] / mmw)[:, None]
+        taugas, tauray, _ = oo.gas_sums(
+            L["colden"], L["mmw"], L["mix"], L["coef"],
+            continuum=[((a, b), gold["%s/continuum_opa/%s" % (qm, a + b)]) for a, b in PAIRS],
+            molecular=[(m, gold["%s/molecular_opa/%s" % (qm, m)]) for m in ("H2O", "CH4", "H2")], rayleigh=ray)
         for key in CASES:
             de, s, r, tm = _case_args(key)
             if r == 0:
@@ -122,6 +127,56 @@ def test_oracle_compute_opacity(gold, pollack_table):
                                      gold["in/cld_g0"], rf, stream=s, delta_eddington=de, test_mode=tm)
             for nm, arr in zip(NAMES, out):
                 assert _close(arr, gold["%s/%s/%s" % (qm, key, nm)], 1e-11), (qm, key, nm)
+
+
+def test_oracle_gas_sums_from_the_tables(gold):
+    """The oracle's table queries and TAUGAS / TAURAY sums from the synthetic DB's own tables (the independent reference
+    of tests/test_opacity_shapes_gpu.py): the continuum / molecular planes and the ptids of the nearest query are the
+    reference's, and the 13 planes built on them are the fixture's for both query methods."""
+    import sqlite3
+    from oracle import optics_oracle as oo
+    from picaso_amd import optics as px
+    conn = sqlite3.connect(DB)
+    pt = sorted(set(conn.execute("SELECT ptid, pressure, temperature FROM molecular")))
+    rows = {}
+    for m, pid, b in conn.execute("SELECT molecule, ptid, opacity FROM molecular"):
+        rows.setdefault(m, {})[int(pid)] = px._convert_array(b)
+    cont = {}
+    for m, t, b in conn.execute("SELECT molecule, temperature, opacity FROM continuum"):
+        cont.setdefault(m, {})[float(t)] = px._convert_array(b)
+    conn.close()
+    tab = {m: np.stack([r[pid] for pid, _, _ in pt]) for m, r in rows.items()}
+    L = _gold_layers(gold)
+    opa = px.RetrieveOpacities.__new__(px.RetrieveOpacities)           # its host bracket search only
+    opa.pt_pairs = pt
+    temps = list(dict.fromkeys(t for _, _, t in pt))
+    opa.t_inv_grid = 1 / np.array(temps)
+    opa.p_log_grid = np.log10(np.array(list(dict.fromkeys(p for _, p, _ in pt))))
+    opa.nc_p = np.array([sum(1 for x in pt if x[2] == t) for t in temps])
+    t_i, p_i, i_ll, i_hl, i_lh, i_hh = opa.find_needed_pts(L["tlayer"], L["player"])
+    cia_t = sorted(cont["H2H2"])
+    cplanes = [((a, b), oo.continuum_nearest(L["tlayer"], cia_t, np.stack([cont[a + b][t] for t in cia_t])))
+               for a, b in PAIRS]
+    for qm in ("nearest", "linear"):
+        for (a, b), c in cplanes:
+            assert _close(c, gold["%s/continuum_opa/%s" % (qm, a + b)], 1e-15), a + b
+        mplanes = []
+        for m in ("H2O", "CH4", "H2"):
+            if qm == "linear":
+                mp = oo.interp_molecular(tab[m], t_i[:, 0], p_i[:, 0], i_ll, i_hl, i_hh, i_lh)
+            else:
+                mp, ids = oo.nearest_molecular(tab[m], pt, L["player"], L["tlayer"])
+                assert np.array_equal(ids, gold["nearest/pt_opa_index"])
+            assert _close(mp, gold["%s/molecular_opa/%s" % (qm, m)], 1e-13), (qm, m)
+            mplanes.append((m, mp))
+        taugas, tauray, terms = oo.gas_sums(L["colden"], L["mmw"], L["mix"], L["coef"], continuum=cplanes,
+                                            molecular=mplanes, rayleigh=_db_rayleigh())
+        assert list(terms) == ["H2H2", "H2He", "H2CH4", "H2O", "CH4", "H2", "rayleigh"]
+        assert _close(sum(v for k, v in terms.items() if k != "rayleigh"), taugas, 1e-15)
+        key = qm + "/de1_s2_r2_tmnone"
+        out = oo.compute_opacity(taugas, tauray, gold["in/cld_opd"], gold["in/cld_w0"], gold["in/cld_g0"], 0.99999)
+        for nm, arr in zip(NAMES, out):
+            assert _close(arr, gold["%s/%s" % (key, nm)], 1e-11), (qm, nm)
 
 
 # ------------------------------------------------------------------------------------------------
