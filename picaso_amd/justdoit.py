@@ -92,7 +92,12 @@ def opannection(wave_range=None, filename_db=None, resample=1, method="resampled
     ``$picaso_refdata/opacities/ck_cx_cont_opacities.db``) -> ``RetrieveCKs``; ``'resortrebin'``: directory
     ``ck_db`` of per-gas k-tables (``preload_gases``) mixed on the fly.  ``query_method`` ('nearest' |
     'linear': how (P,T) table points are combined, an attribute the reference sets on the class afterwards) and
-    ``rayleigh_opa`` (Rayleigh cross sections as data) are additions after the reference's keywords."""
+    ``rayleigh_opa`` are additions after the reference's keywords.
+
+    Rayleigh cross sections, for every method: ``rayleigh_opa={species: sigma(wno)}`` if given (``{}``: no Rayleigh
+    scattering); else, for ``'resampled'``, the ``rayleigh`` table of the database if it has one; else all 39 species of
+    ``picaso_amd.rayleigh.Rayleigh`` are computed on the object's wavenumber grid (after ``resample`` and ``wave_range``),
+    as the reference's ``get_available_rayleigh`` does for every opacity object."""
     import glob
     if isinstance(wave_range, (str, bytes, os.PathLike)):
         raise Exception("opannection(wave_range=None, filename_db=None, ...): the first positional argument is "

@@ -12,8 +12,11 @@
   ``picaso()`` can hand them straight to the solvers without a PCIe round trip.
 
 Database I/O (sqlite, ``np.load`` of blobs) and the Rayleigh cross sections are host-side data
-preparation, out of the accelerated path: Rayleigh ``sigma(nu)`` per species is
-supplied by the caller (``rayleigh_opa``) or read from an optional ``rayleigh`` table of the DB.
+preparation, out of the accelerated path.  Rayleigh ``sigma(nu)`` per species, for the
+readers (``from_sqlite``, ``from_files``, ``opannection``): what the caller supplies (``rayleigh_opa``, ``{}`` for
+none) wins, then an optional ``rayleigh`` table of the DB, else ``rayleigh.available_rayleigh`` computes all 39
+species on the object's grid, as the reference does for every opacity object (optics.py:1060-1065, :2041-2046).
+The plain constructors take what they are given (default: none).
 """
 import ctypes
 import io
@@ -29,6 +32,7 @@ from .atmsetup import CloudTables
 from .device import DeviceArray, regrid_rows
 from .options import current as _options
 from .planes import OUT_NAMES
+from .rayleigh import available_rayleigh
 
 _ci, _cd = ctypes.c_int, ctypes.c_double
 AVOGADRO = 6.02214086e+23
@@ -107,7 +111,9 @@ class RetrieveOpacities:
     @classmethod
     def from_sqlite(cls, db_filename, wave_range=None, resample=1, query_method="nearest",
                     rayleigh_opa=None, ctx=None):
-        """Read a monochromatic opacity DB in the reference schema (optics.py:1998-2039, 2159-2239)."""
+        """Read a monochromatic opacity DB in the reference schema (optics.py:1998-2039, 2159-2239).  Rayleigh cross
+        sections: ``rayleigh_opa`` if given (``{}``: none), else the DB's ``rayleigh`` table if it has one, else computed
+        on the final grid (``rayleigh.available_rayleigh``; the reference's ``get_available_rayleigh``, :2041-2046)."""
         conn = sqlite3.connect(db_filename)
         cur = conn.cursor()
         cur.execute("SELECT wavenumber_grid FROM header")
@@ -130,8 +136,8 @@ class RetrieveOpacities:
             try:
                 cur.execute("SELECT molecule, opacity FROM rayleigh")
                 rayleigh_opa = {m: _convert_array(b)[::resample][loc] for m, b in cur.fetchall()}
-            except sqlite3.OperationalError:
-                rayleigh_opa = {}
+            except sqlite3.OperationalError:      # no such table (no database of the reference's has one)
+                rayleigh_opa = available_rayleigh(wno[loc])
         conn.close()
         return cls(wno[loc], pt_pairs, molecular, continuum, sorted(cia_temps), rayleigh_opa,
                    query_method, ctx=ctx)
@@ -305,8 +311,9 @@ class RetrieveCKs:
         (optics.py:676-722): ``method='preweighted'`` reads ONE premixed HDF5 table, ``'resortrebin'`` a directory
         of per-gas tables for on-the-fly mixing (``read_ck_tables``); the continuum comes from the sqlite database
         the reference ships (``read_continuum_db``).  The legacy ``ascii_data`` / ``full_abunds`` directory form
-        (optics.py:772-1058; deprecated there) is not read.  Rayleigh cross sections are data supplied by the
-        caller, as for the monochromatic tables."""
+        (optics.py:772-1058; deprecated there) is not read.  Rayleigh cross sections: ``rayleigh_opa`` if given
+        (``{}``: none), else computed on the k-tables' wavenumber grid (``rayleigh.available_rayleigh``; the reference's
+        ``get_available_rayleigh``, :1060-1065)."""
         if method not in ("preweighted", "resortrebin"):
             raise Exception("Only resortrebin and preweighted are options for Correlated-Ks")
         if method == "preweighted" and os.path.isdir(ck_db):
@@ -322,6 +329,8 @@ class RetrieveCKs:
         press = np.asarray(t["pressures"], dtype=float)
         pressures = np.concatenate([press[:n] for n in nc_p])
         temps_flat = np.concatenate([[tt] * n for tt, n in zip(np.unique(temps), nc_p)])
+        if rayleigh_opa is None:
+            rayleigh_opa = available_rayleigh(t["wno"])
         kw = dict(continuum=continuum, cia_temps=cia_temps, rayleigh_opa=rayleigh_opa, ctx=ctx)
         if method == "preweighted":
             if "kappa" not in t:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """End-to-end time of the cloud-free 1-D spectrum(reflected+thermal) at 1e5 wavelengths x 90 layers (resident
 synthetic opacity tables) -- run on the GPU box.  PROFILE_1D=1: many calls and nothing else (for rocprofv3
---kernel-trace --stats) plus a cProfile of the host side."""
+--kernel-trace --stats) plus a cProfile of the host side.  NRAY=<n> (1..10): the profile carries ten species that scatter
+and the opacity object holds the cross sections (picaso_amd.rayleigh) of the first n of them -- what the Rayleigh loop of
+k_opacity_gas costs per species (tools/gas_time.sh); without it: H2 and He, as ever."""
 import json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,11 +24,16 @@ cia_t = [75.0, 200.0, 500.0, 1000.0, 2000.0, 4000.0]
 continuum = {pr: {t: 10.0 ** (-7.0 + np.cos(wno / 4000.0 + k) + 0.3 * np.log10(t / 300.0)) for t in cia_t}
              for k, pr in enumerate(("H2H2", "H2He"))}
 ray = {m: 1e-27 * (wno / 1e4) ** 4 for m in ("H2", "He")}
-opa = px.RetrieveOpacities(wno, pt, molecular, continuum, cia_t, rayleigh_opa=ray, query_method="linear", ctx=ctx)
 plev = np.logspace(-6, 2, nlevel)
 prof = {"pressure": plev, "temperature": 150.0 + 1200.0 * ((np.log10(plev) + 6) / 8) ** 2, "H2": np.full(nlevel, 0.84),
         "He": np.full(nlevel, 0.155), "H2O": np.full(nlevel, 1e-3), "CH4": np.full(nlevel, 5e-4),
         "CO": np.full(nlevel, 1e-4), "NH3": np.full(nlevel, 1e-5)}
+if os.environ.get("NRAY"):
+    from picaso_amd.rayleigh import Rayleigh
+    prof.update({"CO2": np.full(nlevel, 3e-4), "N2": np.full(nlevel, 2e-3), "Na": np.full(nlevel, 2e-6), "K": np.full(nlevel, 1e-7)})
+    scatterers = [k for k in prof if k not in ("pressure", "temperature")][:int(os.environ["NRAY"])]
+    ray = {m: Rayleigh(wno).compute_sigma(m) for m in scatterers}
+opa = px.RetrieveOpacities(wno, pt, molecular, continuum, cia_t, rayleigh_opa=ray, query_method="linear", ctx=ctx)
 case = jdi.inputs()
 if os.environ.get("PHASE"):            # PHASE=<radians>: a 6 x 6 disk grid at that phase angle instead of the symmetric 1-D one
     case.phase_angle(float(os.environ["PHASE"]), num_gangle=6, num_tangle=6)
@@ -128,4 +135,5 @@ for B in [int(x) for x in os.environ.get("BATCH", "").split(",") if x]:
     out["spectrum_loop_%d_ms_per_spectrum" % B] = round(1e3 * min(tl) / B, 3)
     out["spectrum_batch_%d_equals_loop" % B] = bool(same)
 out["albedo_sum"] = float(np.sum(r.get("albedo", 0.0)))
+out["rayleigh_species"] = len(opa.rayleigh_molecules)
 print(json.dumps(out))
