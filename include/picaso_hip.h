@@ -964,6 +964,26 @@ int picaso_host_setup(const picaso_setup_args *args);
 int picaso_host_setup_facets(const picaso_setup_args *args, int nfacets, long t_stride, const long *mix_stride);
 size_t picaso_host_setup_abi(void);
 
+/* ---- spectra binned to an instrument grid (reference justplotit.py:31-63, mean_regrid) -------------------------------
+ * One output row: the value v[i] formed per column before it is summed, with numpy's rounding (no contraction) --
+ *   op 0: a[i]      op 1: a[i] * k1      op 2: a[i] / b[i] * k1      op 3: (a[i] / b[i] * k1) + (c[i] * k2)
+ * i.e. a result vector as it is, fpfs_reflected = albedo * k, fpfs_thermal = thermal / stellar * k and
+ * fpfs_total = fpfs_thermal + fpfs_reflected of the output dictionary (justdoit.py:552-599).  a, b, c: device (nwno);
+ * the ones an op does not read may be NULL. */
+#define PICASO_REGRID_MAX_ROWS 8
+typedef struct picaso_regrid_row {
+    int op;
+    const double *a, *b, *c;
+    double k1, k2;
+} picaso_regrid_row;
+/* out[r][j] = (the sum of v[i] for i in [start[j], start[j + 1]), taken in increasing i from +0.0) / the number of
+ * columns: what np.bincount(idx, weights) / counts -- scipy's binned_statistic(statistic='mean') -- gives, bit for bit;
+ * an empty bin is NaN.  start: device, nbins + 1 entries, non-decreasing, start[nbins] <= nwno (trusted: the caller
+ * builds it, picaso_amd/regrid.py); rows: host, nrows in [1, PICASO_REGRID_MAX_ROWS]; out: device (nrows, nbins).
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_mean_regrid_dev(picaso_ctx *ctx, long nwno, int nbins, const int *start, int nrows,
+                           const picaso_regrid_row *rows, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,104 @@
+// Bin resident spectra to an instrument grid: the mean of the points of every bin (reference justplotit.py:31-63,
+// mean_regrid -> scipy.stats.binned_statistic(statistic='mean'), which is np.bincount(idx, weights) / counts), fused with
+// the elementwise post-processing of the output dictionary (justdoit.py:552-599: fpfs_reflected = albedo k,
+// fpfs_thermal = thermal / stellar k, fpfs_total = fpfs_thermal + fpfs_reflected).
+//
+// np.bincount adds a bin's weights in increasing index order to a sum that starts at +0.0, so a bin's value is ONE chain
+// of dependent fp64 additions -- there is nothing to reorder if the bits are to be numpy's.  The parallelism is bins x rows:
+// one wave per (bin, row).  The wave reads its bin in coalesced chunks of 64 columns (lane l forms v[base + l]) and every
+// lane carries the same running sum, to which the chunk's 64 values are added in lane order; a value reaches the adder
+// through v_readlane (two scalar registers, no LDS round trip and no barrier), and the next chunk's loads are issued before
+// the chain of the current one, so that a long bin (1 000 columns at R = 100 on a 1e5-point grid) pays the memory latency
+// once.  Contraction is off: op 3 as written is a product, a quotient, a product and a sum, each rounded, as numpy does it.
+#include "common.hpp"
+
+namespace pz {
+
+struct MeanRegridArgs {
+    long nwno;
+    int nbins, nrows;
+    const int *start;                               // (nbins + 1)
+    picaso_regrid_row rows[PICASO_REGRID_MAX_ROWS];
+    double *out;                                    // (nrows, nbins)
+};
+
+__device__ __forceinline__ double regrid_elem(const picaso_regrid_row &r, long i)
+{
+#pragma clang fp contract(off)
+    const double a = r.a[i];
+    if (r.op == 0) return a;
+    if (r.op == 1) return a * r.k1;
+    const double q = a / r.b[i] * r.k1;
+    if (r.op == 2) return q;
+    const double p = r.c[i] * r.k2;
+    return q + p;
+}
+
+// lane `i`'s value in every lane (`i` is the same in all of them)
+__device__ __forceinline__ double lane_value(double v, int i)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), i);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), i);
+    return __hiloint2double(hi, lo);
+}
+
+__global__ __launch_bounds__(64) void k_mean_regrid(const MeanRegridArgs a)
+{
+#pragma clang fp contract(off)
+    const int j = blockIdx.x, lane = threadIdx.x;
+    const picaso_regrid_row &row = a.rows[blockIdx.y];
+    // the caller's table is trusted to be non-decreasing; the clamps keep a broken one from reading outside the arrays
+    long lo = a.start[j], hi = a.start[j + 1];
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > a.nwno ? a.nwno : hi;
+    double s = 0.0;                                  // np.bincount's accumulator starts at +0.0
+    double v = lo + lane < hi ? regrid_elem(row, lo + lane) : 0.0;
+    for (long base = lo; base < hi; base += 64) {
+        const long next = base + 64 + lane;
+        const double vn = next < hi ? regrid_elem(row, next) : 0.0;      // in flight while this chunk is added
+        const long left = hi - base;
+        if (left >= 64) {
+#pragma unroll
+            for (int i = 0; i < 64; ++i) s = s + lane_value(v, i);
+        } else {
+            const int n = (int)left;
+            for (int i = 0; i < n; ++i) s = s + lane_value(v, i);
+        }
+        v = vn;
+    }
+    const long count = hi > lo ? hi - lo : 0;
+    if (lane == 0) a.out[(long)blockIdx.y * a.nbins + j] = s / (double)count;      // an empty bin: 0 / 0 = NaN
+}
+
+}  // namespace pz
+
+using namespace pz;
+
+extern "C" int picaso_mean_regrid_dev(picaso_ctx *ctx, long nwno, int nbins, const int *start, int nrows,
+                                      const picaso_regrid_row *rows, double *out)
+{
+    if (!ctx || !start || !rows || !out) return fail(ctx, "picaso_mean_regrid_dev: null argument");
+    if (nwno < 1 || nwno > 0x7fffffffL)
+        return fail(ctx, "picaso_mean_regrid_dev: nwno must be in [1, 2^31 - 1] (32-bit bin offsets), got %ld", nwno);
+    if (nbins <= 0) return fail(ctx, "picaso_mean_regrid_dev: nbins must be positive, got %d", nbins);
+    if (nrows < 1 || nrows > PICASO_REGRID_MAX_ROWS)
+        return fail(ctx, "picaso_mean_regrid_dev: nrows must be in [1, %d], got %d", PICASO_REGRID_MAX_ROWS, nrows);
+    MeanRegridArgs a{};
+    for (int r = 0; r < nrows; ++r) {
+        const picaso_regrid_row &w = rows[r];
+        if (w.op < 0 || w.op > 3) return fail(ctx, "picaso_mean_regrid_dev: row %d: unknown op %d", r, w.op);
+        if (!w.a || (w.op >= 2 && !w.b) || (w.op == 3 && !w.c))
+            return fail(ctx, "picaso_mean_regrid_dev: row %d: op %d needs %s", r, w.op,
+                        w.op == 3 ? "a, b and c" : (w.op == 2 ? "a and b" : "a"));
+        a.rows[r] = w;
+    }
+    a.nwno = nwno;
+    a.nbins = nbins;
+    a.nrows = nrows;
+    a.start = start;
+    a.out = out;
+    PZ_HIP(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_mean_regrid, dim3((unsigned)nbins, (unsigned)nrows), dim3(64), 0, ctx->stream, a);
+    PZ_HIP(ctx, hipGetLastError());
+    return 0;
+}

@@ -15,6 +15,7 @@ import ctypes
 import numpy as np
 
 from . import _lib, device, optics, planes
+from . import regrid as _regrid
 from . import driver as drv
 from .atmsetup import CloudTables
 from .device import DeviceArray
@@ -22,18 +23,50 @@ from .spectrum import (_bond_denominator, _constant_planes, _ones, _post_final, 
                        _resident_vector, _setup_atmosphere, _trapz_resident)
 
 
-def run(bundle, opa, subs, calculation, opt, dimension="1d"):
-    """``prepare`` + the C call + ``finish``; None when the call is outside what the driver covers."""
-    p = prepare_3d(bundle, opa, subs, calculation, opt) if dimension == "3d" else \
-        prepare(bundle, opa, subs, calculation, opt, early=True)
+def run(bundle, opa, subs, calculation, opt, dimension="1d", regrid=None):
+    """``prepare`` + the C call + ``finish``; None when the call is outside what the driver covers.  ``regrid``: a
+    ``regrid.RegridPlan`` -- the results stay on the device and are binned behind the legs (``enqueue_regrid``)."""
+    p = prepare_3d(bundle, opa, subs, calculation, opt, regrid=regrid) if dimension == "3d" else \
+        prepare(bundle, opa, subs, calculation, opt, early=True, regrid=regrid)
     if p is None:
         return None
     try:
         drv.enqueue(p["table"], p["job"], p.get("phase", 0))
+        enqueue_regrid(p)
         return finish(p)
     except BaseException:
-        drv.abandon(p["table"])
+        abandon(p)
         raise
+
+
+def abandon(p):
+    """Drop what a prepared call has in flight (an exception between the C call and ``finish``)."""
+    drv.abandon(p["table"])
+    if p.get("binned") is not None:
+        p["binned"].abandon()
+        p["binned"] = None
+
+
+def enqueue_regrid(p):
+    """``regrid=``: behind the legs the C call has enqueued, the bin means of every spectral array of the call
+    (``picaso_mean_regrid_dev``) and ONE copy of ``nrows x nbins`` doubles (+ the spectrum-wide integrals that sit behind
+    the result vectors) through a pinned block.  The block's ``albedo_host`` / ``thermal_host`` are NULL: the
+    full-resolution vectors stay where the legs left them.  The thermal leg runs on the block's second stream, so the
+    first stream waits for it here (what ``picaso_toon_spectrum_collect`` does after the thermal copy)."""
+    plan = p.get("regrid")
+    if plan is None:
+        return
+    k, sub = p["table"].blocks[0], p["table"].subs[0][2]
+    nwno, inp, atm = p["nwno"], p["inp"], p["atm"]
+    ctx = sub.ctx
+    alb = ctypes.cast(k.albedo, ctypes.c_void_p).value if p["do_r"] else None
+    disk = ctypes.cast(k.disk, ctypes.c_void_p).value if p["do_t"] else None
+    tails = ([alb + 8 * nwno] if p["do_r"] else []) + ([disk + 8 * nwno] if p["do_t"] else [])
+    if p["do_t"] and k.tctx and k.tctx != k.ctx:
+        _lib.ctx_wait(ctx, ctypes.c_void_p(k.tctx))
+    rows, p["lists"] = _regrid.spectral_rows(alb, disk, None, p["d_stellar"], inp["star"]["semi_major"], inp["star"]["radius"],
+                                             atm.planet.radius)
+    p["binned"] = _regrid.Binned(plan, ctx, rows, tails, keep=p["keep"])
 
 
 def _in_scope(inp, opa, legs, nblocks, opt):
@@ -89,7 +122,7 @@ def _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, hold):
     return None, None, hcld
 
 
-def _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt):
+def _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt, regrid=None):
     """What ``_fill_block`` needs of one call, for 1-D and 3-D alike: stellar inputs, the full-grid result arrays (one
     element longer when the spectrum-wide integrals arrive with them), the list that keeps per-call device objects alive."""
     nwno = opa.nwno
@@ -100,21 +133,22 @@ def _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt):
         stellar = F0PI
     integrals = len(subs) == 1 and nwno > 1 and not opt.host_integrals
     full = {}
-    if do_r:
+    if do_r and regrid is None:
         full["albedo"] = np.empty(nwno + 1 if integrals else nwno)
-    if do_t:
+    if do_t and regrid is None:
         full["thermal"] = np.empty(nwno + 1 if integrals else nwno)
     return dict(inp=inp, opa=opa, nwno=nwno, wno=opa.wno, hold=[], atm=atm, nostar=nostar, F0PI=F0PI, stellar=stellar,
                 nblocks=len(subs), raman=raman, clouds=(None, None, None), do_r=do_r, do_t=do_t,
                 overlap=do_r and do_t and opt.overlap_legs, seen_dev={}, table=table, ng=ng, nt=nt, full=full,
-                integrals=integrals, denom=None)
+                integrals=integrals, denom=None, regrid=regrid, d_stellar=None)
 
 
 def _prepared(c, job, keep):
     """The dictionary ``prepare`` / ``prepare_3d`` return (``finish`` reads it; ``keep`` holds what the job points into)."""
     return dict(table=c["table"], job=job, keep=(keep, c["hold"]), do_r=c["do_r"], do_t=c["do_t"], full=c["full"],
                 nwno=c["nwno"], integrals=c["integrals"], denom=c["denom"] if (c["integrals"] and c["do_r"]) else None,
-                wno=c["wno"], stellar=c["stellar"], inp=c["inp"], atm=c["atm"], opa=c["opa"])
+                wno=c["wno"], stellar=c["stellar"], inp=c["inp"], atm=c["atm"], opa=c["opa"], regrid=c["regrid"],
+                d_stellar=c["d_stellar"])
 
 
 def _fill_block(k, sub, lo, hi, c):
@@ -184,9 +218,12 @@ def _fill_block_legs(k, sub, lo, hi, c):
         k.flux, k.disk = drv._dev(fl), drv._dev(dk)
         k.thermal_pin = ctypes.cast(ctypes.c_void_p(pin.addr), drv._dp)
         k.wno = drv._dev(_resident_vector(sub, "wno", sub.wno, nw))
-        k.thermal_host = drv._host(c["full"]["thermal"])
+        k.thermal_host = drv._host(c["full"].get("thermal"))       # regrid=: NULL, the result stays on the device
     if c["do_r"]:
-        k.albedo_host = drv._host(c["full"]["albedo"])
+        k.albedo_host = drv._host(c["full"].get("albedo"))
+    if c["regrid"] is not None:                 # the stellar vector the flux ratios divide by (one block: the whole grid)
+        c["d_stellar"] = f0 if c["stellar"] is c["F0PI"] else _resident_vector(sub, "stellar", c["stellar"], nw)
+        hold.append(c["d_stellar"])
     k.trapz_d = k.trapz_dr = k.stellar = None
     if c["integrals"]:
         # one block over the grid: the spectrum-wide integrals are formed on the device behind each result vector and
@@ -219,7 +256,7 @@ def _block_table(opa, subs, plan, linear, ck, slot, signature, make):
     return table
 
 
-def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
+def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False, regrid=None):
     """Everything up to the C call: set-up, block table (``slot``: which of several tables of the same signature, for
     spectra that are in flight together), per-call pointers, job.  None: outside the driver's scope.  ``early=True`` (what
     ``run`` and ``picaso_async`` pass): the opacity stage is ALREADY on the stream when this returns and the returned
@@ -228,6 +265,8 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
     inp = bundle.inputs
     legs = set(calculation.split("+"))
     if not _in_scope(inp, opa, legs, len(subs), opt):
+        return None
+    if regrid is not None and not _regrid_in_scope(opa, subs, opt):
         return None
     common = inp["approx"]["rt_params"]["common"]
     toon = inp["approx"]["rt_params"]["toon"]
@@ -262,7 +301,7 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
                          lambda: drv.BlockTable(subs, nlayer, ng, nt, plan["molecules"], plan["cia_pairs"], factors[2],
                                                 linear, choice, host_cloud, do_r, do_t, _constant_planes, sh=is_sh,
                                                 ngauss=opa.ngauss))
-    c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt)
+    c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt, regrid)
     c["clouds"] = _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, c["hold"])
     # The opacity stage first (round 6): as soon as the table rows / weights / coefficients are in the job and the cloud
     # inputs in the blocks, the gas kernel goes on the stream (drv.enqueue(phase=1)); geometry, level tables, resident
@@ -295,6 +334,12 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False):
     return p
 
 
+def _regrid_in_scope(opa, subs, opt):
+    """``regrid=`` through the driver: one block over the grid with the spectrum-wide integrals formed on the device (they
+    need the native grid, and the full-resolution vectors do not come back); otherwise ``Spectrum``."""
+    return len(subs) == 1 and opa.nwno > 1 and not opt.host_integrals
+
+
 def _in_scope_3d(inp, opa, legs, opt):
     """The 3-D calls the C driver covers: what ``Spectrum._plan_3d`` sends through ONE fused gas + mixing launch over all
     facets (facet-major planes) -- reflected and / or thermal Toon, monochromatic resident tables, no cloud or cloud tables
@@ -311,13 +356,15 @@ def _in_scope_3d(inp, opa, legs, opt):
     return inp["approx"]["rt_params"]["common"]["raman"] in (1, 2) and inp["atmosphere"]["exclude_mol"] == 1
 
 
-def prepare_3d(bundle, opa, subs, calculation, opt, slot=None):
+def prepare_3d(bundle, opa, subs, calculation, opt, slot=None, regrid=None):
     """``prepare`` for ``dimension='3d'`` (reference justdoit.py:407-516): the facet-form set-up and the tall plan once
     for all wavelength blocks, a block table with facet-major planes, a job with ``nfacets``."""
     from .spectrum import setup_facets_3d
     inp = bundle.inputs
     legs = set(calculation.split("+"))
     if not _in_scope_3d(inp, opa, legs, opt):
+        return None
+    if regrid is not None and not _regrid_in_scope(opa, subs, opt):
         return None
     common, toon, geom = inp["approx"]["rt_params"]["common"], inp["approx"]["rt_params"]["toon"], inp["disco"]
     raman = common["raman"]
@@ -350,7 +397,7 @@ def prepare_3d(bundle, opa, subs, calculation, opt, slot=None):
     table = _block_table(opa, subs, plan, linear, False, slot, ("3d", nlayer, ng, nt, tuple(factors[2]), choice, do_r, do_t),
                          lambda: drv.BlockTable(subs, nlayer, ng, nt, plan["molecules"], plan["cia_pairs"], factors[2],
                                                 linear, choice, False, do_r, do_t, _constant_planes, facets=nfac))
-    c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt)
+    c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt, regrid)
     hold = c["hold"]
     for b, (lo, hi, sub) in enumerate(subs):
         c["b"] = b
@@ -375,6 +422,12 @@ def finish(p):
     """Second half of ``run``: the results as they arrive (their copies were enqueued with the launches)."""
     table, do_r, do_t, full, nwno, integrals, denom = (p[k] for k in ("table", "do_r", "do_t", "full", "nwno", "integrals", "denom"))
     wno, stellar, inp, atm, opa = (p[k] for k in ("wno", "stellar", "inp", "atm", "opa"))
+    if p.get("binned") is not None:
+        binned, p["binned"] = p["binned"], None
+        vals, tails = binned.wait()
+        bond = tails.pop(0) / denom if do_r else None
+        teff = (tails.pop(0) / 5.67e-5) ** 0.25 if do_t else None
+        return _regrid.output(p["regrid"], vals, p["lists"], bond, teff)
     returns = {}
     out = {"wavenumber": wno}
     if do_r:

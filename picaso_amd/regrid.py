@@ -1,0 +1,221 @@
+"""Spectra binned to an instrument grid on the device: ``spectrum(regrid=...)``.
+
+A retrieval compares binned spectra with data: after every forward model the reference's callers run ``mean_regrid``
+(justplotit.py:31-63) over each spectral array -- on the host, 5-6 ms per array at 1e5 wavelengths, ten times the
+spectrum it follows, plus the copies of the full-resolution arrays.  Here the bins are found once per wavenumber grid
+(``RegridPlan``: bin ``j`` is the contiguous column range ``[start[j], start[j + 1])``), the means are formed on the
+device behind the solvers (``picaso_mean_regrid_dev``, csrc/regrid.hip) together with the flux ratios of the output
+dictionary, and ``nbins`` doubles per output come back.  The sums are taken in ``np.bincount``'s order, so every binned
+array is bit for bit ``jdi.mean_regrid`` of the array the plain call returns.
+"""
+import ctypes
+import weakref
+
+import numpy as np
+
+from . import _lib, device
+from .device import DeviceArray
+
+MAX_ROWS = 8            # PICASO_REGRID_MAX_ROWS
+_plans = weakref.WeakSet()
+
+
+class _Row(ctypes.Structure):
+    """``picaso_regrid_row``"""
+    _fields_ = [("op", ctypes.c_int), ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("c", ctypes.c_void_p),
+                ("k1", ctypes.c_double), ("k2", ctypes.c_double)]
+
+
+class RegridPlan:
+    """The bins of one wavenumber grid: ``edges`` (nbins + 1), ``centres``, ``counts`` (points per bin), ``start`` (the
+    first column of every bin and, last, the end of the last one) with ``mean_regrid``'s semantics -- bins are
+    ``[e_j, e_j+1)``, the last one includes its right edge, columns outside all edges belong to no bin.  ``start`` is
+    uploaded once per context, when a spectrum first uses the plan."""
+
+    def __init__(self, wno, newx=None, R=None):
+        from .justdoit import create_grid
+        x = np.asarray(wno, dtype=float)
+        if x.ndim != 1 or x.size < 1:
+            raise Exception("regrid_plan: the wavenumber grid must be a non-empty 1-D array")
+        if np.any(np.diff(x) <= 0):
+            raise Exception("regrid_plan: the wavenumber grid must be increasing")
+        if newx is None and R is not None:
+            edges = create_grid(1e4 / np.max(x), 1e4 / np.min(x), R)
+        elif newx is not None and R is None:
+            newx = np.asarray(newx, dtype=float)
+            if newx.ndim != 1 or newx.size < 2:
+                raise Exception("regrid_plan: newx must hold at least two points")
+            d = np.diff(newx)
+            if np.any(d <= 0):
+                raise Exception("regrid_plan: newx must be strictly increasing")
+            edges = np.concatenate(([newx[0] - d[0] / 2], newx[:-1] + d / 2.0, [newx[-1] + d[-1] / 2]))
+        else:
+            raise Exception("Please either enter a newx or a R")
+        nb = edges.size - 1
+        if nb < 1:
+            raise Exception("regrid_plan: the new grid has no bins")
+        start = np.empty(nb + 1, dtype=np.int64)
+        start[:nb] = np.searchsorted(x, edges[:nb], side="left")          # the first x >= e_j
+        start[nb] = np.searchsorted(x, edges[nb], side="right")           # the last bin is closed: x <= e_nbins
+        np.maximum.accumulate(start, out=start)
+        self.wno, self.nwno, self.nbins = wno, int(x.size), int(nb)
+        self.edges = edges
+        self.centres = (edges[:-1] + edges[1:]) / 2.0
+        self.start = start.astype(np.int32)
+        self.counts = np.diff(start)
+        for a in (self.edges, self.centres, self.start, self.counts):
+            a.flags.writeable = False
+        self._dev = {}
+        _plans.add(self)
+
+    def device_start(self, ctx):
+        """``start`` in HBM on ``ctx``'s device (int32; carried by a float64 DeviceArray of the same bytes)."""
+        key = getattr(ctx, "value", ctx)
+        hit = self._dev.get(key)
+        if hit is None:
+            padded = np.zeros((self.nbins + 2) // 2 * 2, dtype=np.int32)
+            padded[:self.nbins + 1] = self.start
+            hit = self._dev[key] = DeviceArray.from_host(padded.view(np.float64), ctx)
+        return hit
+
+
+def _drop_context(value):
+    """``destroy_context``: a new context may be created at the same address later."""
+    for plan in list(_plans):
+        plan._dev.pop(value, None)
+
+
+_lib.on_context_destroy(_drop_context)
+
+
+def regrid_plan(opacityclass_or_wno, newx=None, R=None):
+    """The ``RegridPlan`` of a wavenumber grid (an opacity object, or the array itself) for ``newx`` (bin edges half way
+    between its points) or constant resolution ``R`` -- ``mean_regrid``'s two forms, one of which must be given.  With an
+    opacity object the plan is kept on it by content: equal ``R`` or equal ``newx`` values give the same plan again, and its
+    bin table is uploaded once."""
+    wno = getattr(opacityclass_or_wno, "wno", None)
+    if wno is None:
+        return RegridPlan(opacityclass_or_wno, newx=newx, R=R)
+    if (newx is None) == (R is None):
+        raise Exception("Please either enter a newx or a R")
+    opa = opacityclass_or_wno
+    if R is not None:
+        key = ("R", float(R))
+    else:
+        a = np.ascontiguousarray(newx, dtype=float)
+        key = ("newx", a.shape, a.tobytes())
+    cache = opa.__dict__.setdefault("_regrid_plans", {})
+    hit = cache.get(key)
+    if hit is None or hit.wno is not wno:
+        if len(cache) > 16:
+            cache.clear()
+        hit = cache[key] = RegridPlan(wno, newx=newx, R=R)
+    return hit
+
+
+def resolve(regrid, opa):
+    """``regrid=`` of the public calls -> a plan on ``opa``'s grid: a ``RegridPlan``, ``{'R': r}`` or ``{'newx': array}``."""
+    if isinstance(regrid, RegridPlan):
+        if regrid.nwno != opa.nwno or not (regrid.wno is opa.wno or np.array_equal(regrid.wno, opa.wno)):
+            raise Exception("regrid: the plan was made for another wavenumber grid than the opacity object's")
+        return regrid
+    if isinstance(regrid, dict) and set(regrid) <= {"R", "newx"}:
+        return regrid_plan(opa, newx=regrid.get("newx"), R=regrid.get("R"))
+    raise Exception("regrid must be a regrid_plan(), {'R': r} or {'newx': array}")
+
+
+def _addr(x):
+    return None if x is None else int(x.addr if isinstance(x, DeviceArray) else x)
+
+
+def spectral_rows(albedo, thermal, transit, stellar, sa, radius_star, planet_radius):
+    """The rows of one call in the order of the output dictionary -- ``[(key, op, a, b, c, k1, k2)]`` -- and the keys that
+    stay list-valued placeholders, exactly where ``_post_reflected`` / ``_post_thermal`` / ``_post_final`` put them
+    (justdoit.py:552-599).  ``albedo`` / ``thermal`` / ``transit`` / ``stellar``: device vectors (or None)."""
+    rows, lists = [], {}
+    k_r = k_t = None
+    if albedo is not None:
+        rows.append(("albedo", 0, albedo, None, None, 0.0, 0.0))
+        if (not np.isnan(sa)) and (not np.isnan(planet_radius)):
+            k_r = (planet_radius / sa) ** 2.0
+            rows.append(("fpfs_reflected", 1, albedo, None, None, k_r, 0.0))
+        else:
+            lists["fpfs_reflected"] = []
+    if thermal is not None:
+        rows.append(("thermal", 0, thermal, None, None, 0.0, 0.0))
+        if radius_star == "nostar":
+            lists["fpfs_thermal"] = ["No star mode for Brown Dwarfs was used"]
+        elif (not np.isnan(planet_radius)) and (not np.isnan(radius_star)):
+            k_t = (planet_radius / radius_star) ** 2.0
+            rows.append(("fpfs_thermal", 2, thermal, stellar, None, k_t, 0.0))
+        else:
+            lists["fpfs_thermal"] = []
+    if transit is not None:
+        rows.append(("transit_depth", 0, transit, None, None, 0.0, 0.0))
+    if k_r is not None and k_t is not None:
+        rows.append(("fpfs_total", 3, thermal, stellar, albedo, k_t, k_r))
+    return rows, lists
+
+
+class Binned:
+    """The binning of one call, enqueued: ``wait()`` -> ``({key: (nbins) array}, [tail scalars])``."""
+
+    def __init__(self, plan, ctx, rows, tails=(), keep=None):
+        """``rows``: ``spectral_rows``'s.  ``tails``: device addresses of single doubles (the spectrum-wide integrals behind
+        the result vectors) that travel in the same copy.  Everything is enqueued on ``ctx``'s stream: the caller has
+        ordered it behind the producers of the inputs."""
+        if not 1 <= len(rows) <= MAX_ROWS:
+            raise Exception("regrid: %d rows (1 to %d)" % (len(rows), MAX_ROWS))
+        lib = _lib.load()
+        nb, nr = plan.nbins, len(rows)
+        self.plan, self.keys, self.ntail = plan, [r[0] for r in rows], len(tails)
+        crow = (_Row * nr)()
+        for w, (_, op, a, b, c, k1, k2) in zip(crow, rows):
+            w.op, w.a, w.b, w.c, w.k1, w.k2 = op, _addr(a), _addr(b), _addr(c), float(k1), float(k2)
+        d_start = plan.device_start(ctx)
+        self.out = DeviceArray((nr * nb + len(tails),), ctx)
+        _lib.check(lib.picaso_mean_regrid_dev(ctx, ctypes.c_long(plan.nwno), ctypes.c_int(nb), ctypes.c_void_p(d_start.addr),
+                                              ctypes.c_int(nr), crow, ctypes.c_void_p(self.out.addr)), ctx)
+        for i, t in enumerate(tails):
+            _lib.check(lib.picaso_memcpy_d2d(ctx, ctypes.c_void_p(self.out.addr + 8 * (nr * nb + i)),
+                                             ctypes.c_void_p(int(t)), ctypes.c_size_t(8)), ctx)
+        self.pin = self.out.to_host_async(device.PinnedArray(self.out.shape, ctx), ctx)
+        self.keep = (keep, rows, d_start)          # the launch is asynchronous: its inputs live until the copy has landed
+
+    def wait(self):
+        a = self.pin.wait()
+        nb = self.plan.nbins
+        vals = {k: a[i * nb:(i + 1) * nb].copy() for i, k in enumerate(self.keys)}
+        tails = [a[len(self.keys) * nb + i] for i in range(self.ntail)]
+        self.pin.free()
+        self.pin = self.out = self.keep = None
+        return vals, tails
+
+    def abandon(self):
+        if self.pin is not None:
+            self.pin.free()
+            self.pin = self.out = self.keep = None
+
+
+def output(plan, vals, lists, bond_albedo=None, effective_temperature=None):
+    """The output dictionary of a binned call: the keys of the plain one in its order, ``regrid_counts`` added."""
+    out = {"wavenumber": plan.centres}
+
+    def put(key):
+        if key in vals:
+            out[key] = vals[key]
+        elif key in lists:
+            out[key] = lists[key]
+    if "albedo" in vals:
+        put("albedo")
+        out["bond_albedo"] = bond_albedo
+        put("fpfs_reflected")
+    if "thermal" in vals:
+        put("thermal")
+        out["thermal_unit"] = "erg/s/(cm^2)/(cm)"
+        out["effective_temperature"] = effective_temperature
+        put("fpfs_thermal")
+    put("transit_depth")
+    put("fpfs_total")
+    out["regrid_counts"] = plan.counts
+    return out

@@ -217,8 +217,13 @@ class Spectrum:
     (round 4: ``raise``) are ``_solver`` picking the ``*_ck`` launcher for planes that carry a Gauss axis."""
 
     def __init__(self, bundle, opacityclass, dimension="1d", calculation="reflected", full_output=False, as_dict=True,
-                 raw=False, shared=None, batch=None, options=None):
+                 raw=False, shared=None, batch=None, options=None, regrid=None):
+        """``regrid``: a ``regrid.RegridPlan`` on the opacity object's grid -- the spectral arrays come back binned
+        (``picaso_mean_regrid_dev`` behind the legs) and the full-resolution ones stay on the device."""
         self.opt = _options.current(options)
+        if regrid is not None and (raw or shared is not None):
+            raise NotImplementedError("regrid= with devices=N is not supported: bins straddle the wavelength blocks")
+        self.regrid, self.binned = regrid, None
         self.inp = inp = bundle.inputs
         self.opa = opa = opacityclass
         self.ctx = self.tctx = opa.ctx
@@ -490,7 +495,8 @@ class Spectrum:
         self.dev["albedo"] = alb
 
         def collect_reflected():          # read back after every leg has been enqueued
-            self.returns["albedo"] = _fetch(self.prefetched, "albedo", alb, self.returns, "bond_integral")
+            if self.regrid is None:
+                self.returns["albedo"] = _fetch(self.prefetched, "albedo", alb, self.returns, "bond_integral")
             if self.full_output:
                 atm.xint_at_top = xint.to_host()
             if lvl is not None:
@@ -584,7 +590,8 @@ class Spectrum:
         self.dev["thermal"] = disk
 
         def collect_thermal():
-            self.returns["thermal"] = _fetch(self.prefetched, "thermal", disk, self.returns, "teff_integral")
+            if self.regrid is None:
+                self.returns["thermal"] = _fetch(self.prefetched, "thermal", disk, self.returns, "teff_integral")
             if self.full_output:
                 atm.flux_at_top = flux.to_host()
             if tlvl_disk is not None:
@@ -617,7 +624,8 @@ class Spectrum:
             runtr(self.planes_clear, trc)
             resident.axpby(ctx, 1.0 - self.fhole, tr, self.fhole, trc, tr)
         self.dev["transit_depth"] = tr
-        self.collect.append(lambda: self.returns.__setitem__("transit_depth", tr.to_host()))
+        if self.regrid is None:
+            self.collect.append(lambda: self.returns.__setitem__("transit_depth", tr.to_host()))
 
     # ---------------------------------------------------------------- finish
     def prefetch(self, post_ctx=None):
@@ -628,6 +636,9 @@ class Spectrum:
         opacity kernels instead of in front of them.  Preceded by the spectrum-wide integrals of the two results
         (numpy's bits: csrc/integrals.hip), each stored behind its vector so that one copy brings both."""
         opa, wno, nwno = self.opa, self.wno, self.nwno
+        if self.regrid is not None:
+            self._enqueue_regrid(post_ctx)
+            return
         whole = not self.raw and nwno > 1 and self.shared is None and not self.opt.host_integrals
         if "albedo" in self.dev and "albedo" not in self.prefetched:
             src, denom = self.alb, None
@@ -648,10 +659,68 @@ class Spectrum:
             pc = post_ctx or src.ctx
             self.prefetched["thermal"] = (src.to_host_async(device.PinnedArray(src.shape, pc), pc), None)
 
+    def _enqueue_regrid(self, post_ctx=None):
+        """``regrid=``: behind the legs, the spectrum-wide integrals on the native grid (as ``prefetch`` forms them), then the
+        bin means of every spectral array of the call and the one copy that brings them back, on ``post_ctx`` or on
+        ``ctx`` -- ordered here behind the thermal leg's stream."""
+        from . import regrid as _regrid
+        if self.binned is not None:
+            return
+        opa, wno, nwno, dev = self.opa, self.wno, self.nwno, self.dev
+        whole = nwno > 1 and not self.opt.host_integrals
+        ctx = post_ctx or self.ctx
+        d_st = None
+        if "albedo" in dev or "thermal" in dev:
+            d_st = self.d_f0 if self.stellar is self.F0PI else _resident_vector(opa, "stellar", self.stellar, nwno)
+        tails, self.bond_denom = [], None
+        if whole and "albedo" in dev:
+            d_w, _ = _trapz_resident(opa, wno)
+            self.bond_denom = _bond_denominator(opa, wno, self.stellar, d_st)
+            resident.trapz(post_ctx or self.ctx, nwno, d_w, self.alb, self.alb_x.addr + 8 * nwno, mult=d_st)
+            tails.append(self.alb_x.addr + 8 * nwno)
+        if whole and "thermal" in dev:
+            _, d_wr = _trapz_resident(opa, wno)
+            resident.trapz(post_ctx or self.tctx, nwno, d_wr, self.disk, self.disk_x.addr + 8 * nwno, reverse=True)
+            tails.append(self.disk_x.addr + 8 * nwno)
+        if post_ctx is None and self.tctx is not self.ctx and "thermal" in dev:
+            _lib.ctx_wait(self.ctx, self.tctx)
+        rows, self.binned_lists = _regrid.spectral_rows(dev.get("albedo"), dev.get("thermal"), dev.get("transit_depth"), d_st,
+                                                        self.sa, self.radius_star, self.atm.planet.radius)
+        self.binned = _regrid.Binned(self.regrid, ctx, rows, tails, keep=(d_st, self.keep_alive[:]))
+
+    def _finish_binned(self):
+        """``__call__`` with ``regrid=``: the dictionary of the plain call with every spectral array binned."""
+        from . import regrid as _regrid
+        self._enqueue_regrid()
+        atm = self.atm
+        for fin in self.collect:          # full_output / level-flux extras, at native resolution
+            fin()
+        vals, tails = self.binned.wait()
+        bond = teff = None
+        whole = self.nwno > 1 and not self.opt.host_integrals
+        tmp = {}
+        if "albedo" in self.dev:
+            raw = {"albedo": None, "bond_integral": (tails.pop(0), self.bond_denom)} if whole else {"albedo": self.alb.to_host()}
+            _post_reflected(tmp, raw, self.wno, self.stellar, np.nan, np.nan, self.opa)
+            bond = tmp["bond_albedo"]
+        if "thermal" in self.dev:
+            raw = {"thermal": None, "teff_integral": tails.pop(0)} if whole else {"thermal": self.disk.to_host()}
+            _post_thermal(tmp, raw, self.wno, self.stellar, "nostar", np.nan, self.opa)
+            teff = tmp["effective_temperature"]
+        out = _regrid.output(self.regrid, vals, self.binned_lists, bond, teff)
+        del self.keep_alive[:]
+        self.collect = []
+        self.binned = None
+        if self.full_output:
+            out["full_output"] = atm.as_dict() if self.as_dict else atm
+        return out
+
     def __call__(self):
         """Results are read back leg by leg (each copy waits for the stream that produced it) and a leg's spectrum-wide
         integrals run as soon as it has arrived: the Bond-albedo integral overlaps the thermal kernels still running
         on the second stream.  Same stages, same order of keys as ``_postprocess``."""
+        if self.regrid is not None:
+            return self._finish_binned()
         returns, atm = self.returns, self.atm
         out = {"wavenumber": self.wno}
         for fin in self.collect:
