@@ -984,6 +984,20 @@ typedef struct picaso_regrid_row {
 int picaso_mean_regrid_dev(picaso_ctx *ctx, long nwno, int nbins, const int *start, int nrows,
                            const picaso_regrid_row *rows, double *out);
 
+/* ---- spectra convolved with a line-spread function (reference driver.py:338-381, conv_non_uniform_R) -----------------
+ * out[r][i] = sum_k v_r[k] g_ik / sum_k g_ik over the model columns k in [lo[i], hi[i]), g_ik = exp(-(wl[k] - centre[i])^2
+ * / den[i]): a Gaussian of sigma_i = centre_i / R_i / 2.355 (den = 2 sigma^2, formed by the caller) evaluated at the
+ * observed wavelength centre[i].  v_r: the rows of picaso_mean_regrid_dev.  The argument of exp has numpy's bits (no
+ * contraction); the caller cuts the window where the reference's weight is an exact 0.0 (39 sigma: picaso_amd/convolve.py),
+ * so the result differs from the reference by the rounding of exp and the order of the two sums.  That order is fixed: a
+ * point's bits depend on its window alone.  A window without weight (empty, or all weights 0) gives NaN, as the reference
+ * does.  wl (nwno), centre, den, lo, hi (nobs): device; lo / hi are clamped into [0, nwno]; rows: host, nrows in
+ * [1, PICASO_REGRID_MAX_ROWS]; out: device (nrows, nobs).
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_lsf_convolve_dev(picaso_ctx *ctx, long nwno, const double *wl, int nobs, const double *centre,
+                            const double *den, const int *lo, const int *hi, int nrows, const picaso_regrid_row *rows,
+                            double *out /* (nrows, nobs) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@
 // the chain of the current one, so that a long bin (1 000 columns at R = 100 on a 1e5-point grid) pays the memory latency
 // once.  Contraction is off: op 3 as written is a product, a quotient, a product and a sum, each rounded, as numpy does it.
 #include "common.hpp"
+#include "regrid_elem.hpp"
 
 namespace pz {
 
@@ -21,18 +22,6 @@ struct MeanRegridArgs {
     picaso_regrid_row rows[PICASO_REGRID_MAX_ROWS];
     double *out;                                    // (nrows, nbins)
 };
-
-__device__ __forceinline__ double regrid_elem(const picaso_regrid_row &r, long i)
-{
-#pragma clang fp contract(off)
-    const double a = r.a[i];
-    if (r.op == 0) return a;
-    if (r.op == 1) return a * r.k1;
-    const double q = a / r.b[i] * r.k1;
-    if (r.op == 2) return q;
-    const double p = r.c[i] * r.k2;
-    return q + p;
-}
 
 // lane `i`'s value in every lane (`i` is the same in all of them)
 __device__ __forceinline__ double lane_value(double v, int i)
@@ -81,17 +70,8 @@ extern "C" int picaso_mean_regrid_dev(picaso_ctx *ctx, long nwno, int nbins, con
     if (nwno < 1 || nwno > 0x7fffffffL)
         return fail(ctx, "picaso_mean_regrid_dev: nwno must be in [1, 2^31 - 1] (32-bit bin offsets), got %ld", nwno);
     if (nbins <= 0) return fail(ctx, "picaso_mean_regrid_dev: nbins must be positive, got %d", nbins);
-    if (nrows < 1 || nrows > PICASO_REGRID_MAX_ROWS)
-        return fail(ctx, "picaso_mean_regrid_dev: nrows must be in [1, %d], got %d", PICASO_REGRID_MAX_ROWS, nrows);
     MeanRegridArgs a{};
-    for (int r = 0; r < nrows; ++r) {
-        const picaso_regrid_row &w = rows[r];
-        if (w.op < 0 || w.op > 3) return fail(ctx, "picaso_mean_regrid_dev: row %d: unknown op %d", r, w.op);
-        if (!w.a || (w.op >= 2 && !w.b) || (w.op == 3 && !w.c))
-            return fail(ctx, "picaso_mean_regrid_dev: row %d: op %d needs %s", r, w.op,
-                        w.op == 3 ? "a, b and c" : (w.op == 2 ? "a and b" : "a"));
-        a.rows[r] = w;
-    }
+    PZ_TRY(regrid_rows_check(ctx, "picaso_mean_regrid_dev", nrows, rows, a.rows));
     a.nwno = nwno;
     a.nbins = nbins;
     a.nrows = nrows;

@@ -19,11 +19,13 @@ import os
 import numpy as np
 
 from . import _lib, disco, optics, resident
+from . import convolve as _convolve
 from . import regrid as _regrid
 from . import options as _options
 from .device import DeviceArray
 from .options import Options                                                        # noqa: F401  (jdi.Options)
 from .planes import cloud_free_top as _cloud_free_top                               # noqa: F401  (jdi._cloud_free_top)
+from .convolve import ConvolvePlan, conv_non_uniform_R, convolve_plan               # noqa: F401  (jdi.convolve_plan)
 from .regrid import RegridPlan, regrid_plan                                         # noqa: F401  (jdi.regrid_plan)
 from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
                        _fetch, _interp_axis, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
@@ -885,13 +887,16 @@ class inputs:
 
     @_lib.serialized
     def phase_curve(self, opacityclass, full_output=False, plot_opacity=False, n_cpu=1, verbose=False,
-                    clouds_by_phase=None, devices=None, options=None, regrid=None):
+                    clouds_by_phase=None, devices=None, options=None, regrid=None, convolve=None):
         """Spectrum at every phase of ``phase_curve_geometry`` (reference justdoit.py:4741-4777; its
         ``n_cpu`` joblib fan-out is a loop here: the phases share the resident opacity tables and one
         GPU).  ``devices=N`` (or a list of device indices) deals the phases out to N GPUs round-robin -- the
         reference's fan-out of whole phases, with a replica of the opacity tables resident on every device
         (``optics.shard_opacity`` over the full grid, uploaded once) and every phase enqueued before the first
-        result is read.  Returns ``{phase: spectrum output}``.  ``regrid`` is not supported here."""
+        result is read.  Returns ``{phase: spectrum output}``.  ``regrid`` and ``convolve`` are not supported here."""
+        if convolve is not None:
+            raise NotImplementedError("phase_curve(convolve=...) is not supported: convolve each phase's spectrum with "
+                                      "conv_non_uniform_R, or call spectrum(convolve=...) per phase")
         if regrid is not None:
             raise NotImplementedError("phase_curve(regrid=...) is not supported: bin each phase's spectrum with "
                                       "mean_regrid, or call spectrum(regrid=...) per phase")
@@ -1046,11 +1051,13 @@ class inputs:
         t["single_phase"] = single_phase_options(False).index(single_phase)
 
     def spectrum(self, opacityclass, calculation="reflected", dimension="1d", full_output=False,
-                 plot_opacity=False, as_dict=True, devices=None, gather="host", options=None, regrid=None):
+                 plot_opacity=False, as_dict=True, devices=None, gather="host", options=None, regrid=None, convolve=None):
         """Run the spectrum (reference justdoit.py:4779-4840).  ``devices=N`` (or a list of device indices):
         the wavelength grid is cut into N contiguous blocks, one per GPU (``picaso(devices=...)``).  ``regrid``
         (``regrid_plan(...)``, ``{'R': r}`` or ``{'newx': array}``): every spectral array comes back binned on the device,
-        bit for bit ``mean_regrid`` of the plain call's (``picaso(regrid=...)``)."""
+        bit for bit ``mean_regrid`` of the plain call's (``picaso(regrid=...)``).  ``convolve`` (``convolve_plan(...)`` or
+        ``{'wl': array, 'R': scalar_or_array}``): every spectral array comes back convolved with a Gaussian line-spread
+        function of resolving power ``R`` at the wavelengths ``wl``, on the device (``picaso(convolve=...)``)."""
         if dimension not in ("1d", "3d"):
             raise Exception("dimension must be '1d' or '3d'")
         have = self.inputs["atmosphere"].get("profile" if dimension == "1d" else "profile_3d")
@@ -1061,10 +1068,10 @@ class inputs:
             raise Exception("Need to set gravity with the gravity() function")
         return picaso(self, opacityclass, dimension=dimension, calculation=calculation,
                       full_output=full_output, plot_opacity=plot_opacity, as_dict=as_dict, devices=devices,
-                      gather=gather, options=options, regrid=regrid)
+                      gather=gather, options=options, regrid=regrid, convolve=convolve)
 
     def spectrum_async(self, opacityclass, calculation="reflected", dimension="1d", full_output=False, as_dict=True,
-                       options=None, regrid=None):
+                       options=None, regrid=None, convolve=None):
         """``spectrum()`` without the wait: set-up and every launch of this spectrum are enqueued (result copies
         included) and a ``PendingSpectrum`` comes back at once; its ``result()`` is ``spectrum()``'s dictionary, bit for
         bit.  A retrieval that asks for sample i + 1 before it reads sample i hides the host set-up of one call behind the
@@ -1079,13 +1086,13 @@ class inputs:
         if self.inputs["planet"]["gravity"] is None:
             raise Exception("Need to set gravity with the gravity() function")
         return picaso_async(self, opacityclass, dimension=dimension, calculation=calculation, full_output=full_output,
-                            as_dict=as_dict, options=options, regrid=regrid)
+                            as_dict=as_dict, options=options, regrid=regrid, convolve=convolve)
 
 
 @_lib.serialized
 def picaso(bundle, opacityclass, dimension="1d", calculation="reflected", full_output=False,
            plot_opacity=False, as_dict=True, defer=False, devices=None, gather="host", options=None, _raw=False,
-           _shared=None, _batch=None, regrid=None):
+           _shared=None, _batch=None, regrid=None, convolve=None, _reduce=None):
     """Spectrum driver (reference ``picaso()``, justdoit.py:65-621).
 
     The work is ``spectrum.Spectrum``: plan (ATMSETUP, opacity planes) -> enqueue (every leg's solver launches) ->
@@ -1104,17 +1111,25 @@ def picaso(bundle, opacityclass, dimension="1d", calculation="reflected", full_o
     ``fpfs_total``, ``transit_depth``) replaced by ``mean_regrid(wavenumber, array, ...)[1]`` of itself -- bit for bit; the
     sums run on the device in numpy's order (csrc/regrid.hip) and only the binned arrays are copied back -- and
     ``regrid_counts`` (points per bin) added.  ``bond_albedo`` / ``effective_temperature`` are the native grid's,
-    ``full_output`` stays at native resolution.  Not with ``devices=N`` (bins straddle the blocks)."""
+    ``full_output`` stays at native resolution.  Not with ``devices=N`` (bins straddle the blocks).
+
+    ``convolve`` (a ``convolve_plan(...)`` or ``{'wl': array, 'R': scalar_or_array}``; not together with ``regrid``): the
+    dictionary of the plain call with ``wavenumber = 1e4 / wl`` in the caller's order, every spectral array replaced by
+    ``conv_non_uniform_R(array, 1e4 / wavenumber, R, wl)`` of itself -- within ``(2 counts + 10) 2^-53`` of
+    ``conv(|array|)``: the weights are formed on the device once for all arrays (csrc/convolve.hip) and summed in an order
+    of their own -- and ``convolve_counts`` (model columns within 39 sigma of every point) added.  The rest as for
+    ``regrid``.  ``_reduce``: either plan, resolved by the caller."""
     opt = _options.current(options)
-    plan = None
-    if regrid is not None:
-        if devices is not None or _raw or _shared is not None:
-            raise NotImplementedError("regrid= with devices=N is not supported: bins straddle the wavelength blocks, and "
-                                      "no run with more than one rank has been made")
-        plan = _regrid.resolve(regrid, opacityclass)
+    plan = _reduce if _reduce is not None else _convolve.reduction(regrid, convolve, opacityclass)
+    if plan is not None and (devices is not None or _raw or _shared is not None):
+        if plan.kind == "convolve":
+            raise NotImplementedError("convolve= with devices=N is not supported: windows straddle the wavelength "
+                                      "blocks, and no run with more than one rank has been made")
+        raise NotImplementedError("regrid= with devices=N is not supported: bins straddle the wavelength blocks, and "
+                                  "no run with more than one rank has been made")
     if plan is not None and not (full_output or defer) and not any(
             leg in calculation for leg in ("reflected", "thermal", "transmission")):
-        return {"wavenumber": plan.centres, "regrid_counts": plan.counts}
+        return plan.empty_output()
     if not (full_output or defer or _raw) and not any(leg in calculation for leg in ("reflected", "thermal", "transmission")):
         # the reference tests `'reflected' in calculation` etc. and nothing else: a string that names no leg runs its
         # set-up and returns the wavenumber grid alone (justdoit.py:254, 318, 388, 517-621) -- no error there, none here
@@ -1213,7 +1228,7 @@ class PendingSpectrum:
 
 @_lib.serialized
 def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", full_output=False, as_dict=True,
-                 options=None, regrid=None):
+                 options=None, regrid=None, convolve=None):
     """``picaso()`` up to and including the last launch; returns a ``PendingSpectrum``.
 
     What the C driver covers (``onecall.prepare``: the plain 1-D Toon / SH and 3-D spectra) is enqueued through it on one of
@@ -1222,14 +1237,15 @@ def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", 
     patchy clouds, level fluxes, ``full_output`` ...) is ``picaso(defer=True)`` with its result copies already on the
     stream.  Either way the dictionary is the one ``picaso()`` returns for the same inputs.  The case must not be given a
     new star before ``result()`` (the flux ratios are formed there); atmosphere, clouds and geometry may change at once.
-    ``regrid``: as ``picaso`` -- the binning is enqueued behind the legs and ``result()`` returns the binned dictionary."""
+    ``regrid`` / ``convolve``: as ``picaso`` -- the reduction is enqueued behind the legs and ``result()`` returns the binned
+    or convolved dictionary."""
     from . import onecall
     from . import driver as drv
     opt = _options.current(options)
-    plan = _regrid.resolve(regrid, opacityclass) if regrid is not None else None
+    plan = _convolve.reduction(regrid, convolve, opacityclass)
     legs = any(leg in calculation for leg in ("reflected", "thermal", "transmission"))
     if not full_output and not legs:
-        out = {"wavenumber": opacityclass.wno} if plan is None else {"wavenumber": plan.centres, "regrid_counts": plan.counts}
+        out = {"wavenumber": opacityclass.wno} if plan is None else plan.empty_output()
         return PendingSpectrum(lambda: out)
     if not full_output:
         st = opacityclass.__dict__.setdefault("_async_slots", {"n": 0, "live": {}})
@@ -1256,7 +1272,7 @@ def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", 
             st["n"] += 1
             return h
     s = picaso(bundle, opacityclass, dimension=dimension, calculation=calculation, full_output=full_output, as_dict=as_dict,
-               defer=True, options=opt, regrid=plan)
+               defer=True, options=opt, _reduce=plan)
     if not opt.sync_copies:
         s.prefetch()
     return PendingSpectrum(s)
@@ -1350,7 +1366,7 @@ class _SolveBatch:
 
 @_lib.serialized
 def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=False, as_dict=True, batch_size=4,
-                   options=None, regrid=None):
+                   options=None, regrid=None, convolve=None):
     """``[case.spectrum(opacityclass, calculation) for case in cases]`` (1-D) with the solvers of up to
     ``batch_size`` spectra in ONE launch each: what a retrieval or a model grid asks of the reference one
     ``spectrum()`` call and one process at a time (driver.py:405-426).  ``cases``: ``inputs`` objects, each with its
@@ -1359,10 +1375,10 @@ def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=Fal
     dictionary is bit-identical to ``case.spectrum(...)``'s.  The chunks are pipelined: while the GPU solves chunk k the
     host sets up and enqueues chunk k + 1, and only then waits for k's result copies (``picaso_memcpy_d2h_async`` into
     pinned blocks, ``picaso_mark_wait``) and runs its integrals.  HBM: the planes of a chunk stay resident until its
-    launch (0.8 GB per cloudy 1e5 x 90 spectrum, 0.2 GB per cloud-free one), two chunks at a time.  ``regrid``: as
-    ``picaso``; one plan is shared by all members."""
+    launch (0.8 GB per cloudy 1e5 x 90 spectrum, 0.2 GB per cloud-free one), two chunks at a time.  ``regrid`` /
+    ``convolve``: as ``picaso``; one plan is shared by all members."""
     opt = _options.current(options)
-    plan = _regrid.resolve(regrid, opacityclass) if regrid is not None else None
+    plan = _convolve.reduction(regrid, convolve, opacityclass)
     cases = list(cases)
     outs = []
     in_flight = []                 # chunks whose launches and result copies are on the stream
@@ -1378,7 +1394,7 @@ def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=Fal
         fins = []
         for case in chunk:
             fins.append(picaso(case, opacityclass, dimension="1d", calculation=calculation, full_output=full_output,
-                               as_dict=as_dict, defer=True, options=opt, _batch=batch, regrid=plan))
+                               as_dict=as_dict, defer=True, options=opt, _batch=batch, _reduce=plan))
         batch.flush()
         # integrals and result copies on a stream of their own, behind this chunk's solvers
         post = {}

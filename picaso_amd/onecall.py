@@ -25,7 +25,8 @@ from .spectrum import (_bond_denominator, _constant_planes, _ones, _post_final, 
 
 def run(bundle, opa, subs, calculation, opt, dimension="1d", regrid=None):
     """``prepare`` + the C call + ``finish``; None when the call is outside what the driver covers.  ``regrid``: a
-    ``regrid.RegridPlan`` -- the results stay on the device and are binned behind the legs (``enqueue_regrid``)."""
+    ``regrid.Reduction`` (the plan of ``regrid=`` or of ``convolve=``) -- the results stay on the device and are binned or
+    convolved behind the legs (``enqueue_regrid``)."""
     p = prepare_3d(bundle, opa, subs, calculation, opt, regrid=regrid) if dimension == "3d" else \
         prepare(bundle, opa, subs, calculation, opt, early=True, regrid=regrid)
     if p is None:
@@ -48,8 +49,8 @@ def abandon(p):
 
 
 def enqueue_regrid(p):
-    """``regrid=``: behind the legs the C call has enqueued, the bin means of every spectral array of the call
-    (``picaso_mean_regrid_dev``) and ONE copy of ``nrows x nbins`` doubles (+ the spectrum-wide integrals that sit behind
+    """``regrid=`` / ``convolve=``: behind the legs the C call has enqueued, the plan's launch over every spectral array of
+    the call (``picaso_mean_regrid_dev`` / ``picaso_lsf_convolve_dev``) and ONE copy of ``nrows x nbins`` doubles (+ the spectrum-wide integrals that sit behind
     the result vectors) through a pinned block.  The block's ``albedo_host`` / ``thermal_host`` are NULL: the
     full-resolution vectors stay where the legs left them.  The thermal leg runs on the block's second stream, so the
     first stream waits for it here (what ``picaso_toon_spectrum_collect`` does after the thermal copy)."""
@@ -66,7 +67,7 @@ def enqueue_regrid(p):
         _lib.ctx_wait(ctx, ctypes.c_void_p(k.tctx))
     rows, p["lists"] = _regrid.spectral_rows(alb, disk, None, p["d_stellar"], inp["star"]["semi_major"], inp["star"]["radius"],
                                              atm.planet.radius)
-    p["binned"] = _regrid.Binned(plan, ctx, rows, tails, keep=p["keep"])
+    p["binned"] = plan.enqueue(ctx, rows, tails, keep=p["keep"])
 
 
 def _in_scope(inp, opa, legs, nblocks, opt):
@@ -427,7 +428,7 @@ def finish(p):
         vals, tails = binned.wait()
         bond = tails.pop(0) / denom if do_r else None
         teff = (tails.pop(0) / 5.67e-5) ** 0.25 if do_t else None
-        return _regrid.output(p["regrid"], vals, p["lists"], bond, teff)
+        return p["regrid"].output(vals, p["lists"], bond, teff)
     returns = {}
     out = {"wavenumber": wno}
     if do_r:

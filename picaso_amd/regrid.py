@@ -26,11 +26,39 @@ class _Row(ctypes.Structure):
                 ("k1", ctypes.c_double), ("k2", ctypes.c_double)]
 
 
-class RegridPlan:
+class Reduction:
+    """What ``spectrum(regrid=...)`` and ``spectrum(convolve=...)`` share: a plan on one wavenumber grid that turns the
+    resident spectral arrays of a call into ``nout`` values per array behind the legs.  A plan gives ``nout``,
+    ``out_wavenumber`` (the ``wavenumber`` of the output dictionary), ``counts`` (stored under ``counts_key``), ``kind``
+    (the keyword, for messages) and ``launch(ctx, nrows, crows, out_addr)``, which enqueues its kernel and returns the
+    device tables the launch reads."""
+
+    def enqueue(self, ctx, rows, tails=(), keep=None):
+        """One launch and one small copy on ``ctx``'s stream (``Binned``): the hook of ``onecall.enqueue_regrid`` and
+        ``Spectrum._enqueue_regrid``."""
+        return Binned(self, ctx, rows, tails, keep)
+
+    def output(self, vals, lists, bond_albedo=None, effective_temperature=None):
+        return output(self, vals, lists, bond_albedo, effective_temperature)
+
+    def empty_output(self):
+        """The dictionary of a call that names no leg."""
+        return {"wavenumber": self.out_wavenumber, self.counts_key: self.counts}
+
+    def check_grid(self, opa):
+        if self.nwno != opa.nwno or not (self.wno is opa.wno or np.array_equal(self.wno, opa.wno)):
+            raise Exception("%s: the plan was made for another wavenumber grid than the opacity object's" % self.kind)
+        return self
+
+
+class RegridPlan(Reduction):
     """The bins of one wavenumber grid: ``edges`` (nbins + 1), ``centres``, ``counts`` (points per bin), ``start`` (the
     first column of every bin and, last, the end of the last one) with ``mean_regrid``'s semantics -- bins are
     ``[e_j, e_j+1)``, the last one includes its right edge, columns outside all edges belong to no bin.  ``start`` is
     uploaded once per context, when a spectrum first uses the plan."""
+    kind, counts_key = "regrid", "regrid_counts"
+    nout = property(lambda self: self.nbins)
+    out_wavenumber = property(lambda self: self.centres)
 
     def __init__(self, wno, newx=None, R=None):
         from .justdoit import create_grid
@@ -78,6 +106,13 @@ class RegridPlan:
             hit = self._dev[key] = DeviceArray.from_host(padded.view(np.float64), ctx)
         return hit
 
+    def launch(self, ctx, nrows, crows, out_addr):
+        d_start = self.device_start(ctx)
+        _lib.check(_lib.load().picaso_mean_regrid_dev(ctx, ctypes.c_long(self.nwno), ctypes.c_int(self.nbins),
+                                                      ctypes.c_void_p(d_start.addr), ctypes.c_int(nrows), crows,
+                                                      ctypes.c_void_p(out_addr)), ctx)
+        return d_start
+
 
 def _drop_context(value):
     """``destroy_context``: a new context may be created at the same address later."""
@@ -116,9 +151,7 @@ def regrid_plan(opacityclass_or_wno, newx=None, R=None):
 def resolve(regrid, opa):
     """``regrid=`` of the public calls -> a plan on ``opa``'s grid: a ``RegridPlan``, ``{'R': r}`` or ``{'newx': array}``."""
     if isinstance(regrid, RegridPlan):
-        if regrid.nwno != opa.nwno or not (regrid.wno is opa.wno or np.array_equal(regrid.wno, opa.wno)):
-            raise Exception("regrid: the plan was made for another wavenumber grid than the opacity object's")
-        return regrid
+        return regrid.check_grid(opa)
     if isinstance(regrid, dict) and set(regrid) <= {"R", "newx"}:
         return regrid_plan(opa, newx=regrid.get("newx"), R=regrid.get("R"))
     raise Exception("regrid must be a regrid_plan(), {'R': r} or {'newx': array}")
@@ -158,24 +191,22 @@ def spectral_rows(albedo, thermal, transit, stellar, sa, radius_star, planet_rad
 
 
 class Binned:
-    """The binning of one call, enqueued: ``wait()`` -> ``({key: (nbins) array}, [tail scalars])``."""
+    """The reduction of one call, enqueued: ``wait()`` -> ``({key: (nout) array}, [tail scalars])``."""
 
     def __init__(self, plan, ctx, rows, tails=(), keep=None):
         """``rows``: ``spectral_rows``'s.  ``tails``: device addresses of single doubles (the spectrum-wide integrals behind
         the result vectors) that travel in the same copy.  Everything is enqueued on ``ctx``'s stream: the caller has
         ordered it behind the producers of the inputs."""
         if not 1 <= len(rows) <= MAX_ROWS:
-            raise Exception("regrid: %d rows (1 to %d)" % (len(rows), MAX_ROWS))
+            raise Exception("%s: %d rows (1 to %d)" % (plan.kind, len(rows), MAX_ROWS))
         lib = _lib.load()
-        nb, nr = plan.nbins, len(rows)
+        nb, nr = plan.nout, len(rows)
         self.plan, self.keys, self.ntail = plan, [r[0] for r in rows], len(tails)
         crow = (_Row * nr)()
         for w, (_, op, a, b, c, k1, k2) in zip(crow, rows):
             w.op, w.a, w.b, w.c, w.k1, w.k2 = op, _addr(a), _addr(b), _addr(c), float(k1), float(k2)
-        d_start = plan.device_start(ctx)
         self.out = DeviceArray((nr * nb + len(tails),), ctx)
-        _lib.check(lib.picaso_mean_regrid_dev(ctx, ctypes.c_long(plan.nwno), ctypes.c_int(nb), ctypes.c_void_p(d_start.addr),
-                                              ctypes.c_int(nr), crow, ctypes.c_void_p(self.out.addr)), ctx)
+        d_start = plan.launch(ctx, nr, crow, self.out.addr)
         for i, t in enumerate(tails):
             _lib.check(lib.picaso_memcpy_d2d(ctx, ctypes.c_void_p(self.out.addr + 8 * (nr * nb + i)),
                                              ctypes.c_void_p(int(t)), ctypes.c_size_t(8)), ctx)
@@ -184,7 +215,7 @@ class Binned:
 
     def wait(self):
         a = self.pin.wait()
-        nb = self.plan.nbins
+        nb = self.plan.nout
         vals = {k: a[i * nb:(i + 1) * nb].copy() for i, k in enumerate(self.keys)}
         tails = [a[len(self.keys) * nb + i] for i in range(self.ntail)]
         self.pin.free()
@@ -198,8 +229,9 @@ class Binned:
 
 
 def output(plan, vals, lists, bond_albedo=None, effective_temperature=None):
-    """The output dictionary of a binned call: the keys of the plain one in its order, ``regrid_counts`` added."""
-    out = {"wavenumber": plan.centres}
+    """The output dictionary of a binned or convolved call: the keys of the plain one in its order, the plan's counts
+    (``regrid_counts`` / ``convolve_counts``) added."""
+    out = {"wavenumber": plan.out_wavenumber}
 
     def put(key):
         if key in vals:
@@ -217,5 +249,5 @@ def output(plan, vals, lists, bond_albedo=None, effective_temperature=None):
         put("fpfs_thermal")
     put("transit_depth")
     put("fpfs_total")
-    out["regrid_counts"] = plan.counts
+    out[plan.counts_key] = plan.counts
     return out

@@ -218,11 +218,13 @@ class Spectrum:
 
     def __init__(self, bundle, opacityclass, dimension="1d", calculation="reflected", full_output=False, as_dict=True,
                  raw=False, shared=None, batch=None, options=None, regrid=None):
-        """``regrid``: a ``regrid.RegridPlan`` on the opacity object's grid -- the spectral arrays come back binned
-        (``picaso_mean_regrid_dev`` behind the legs) and the full-resolution ones stay on the device."""
+        """``regrid``: a ``regrid.Reduction`` on the opacity object's grid (a ``RegridPlan`` or a ``ConvolvePlan``) -- the
+        spectral arrays come back binned or convolved (the plan's launch behind the legs) and the full-resolution ones stay
+        on the device."""
         self.opt = _options.current(options)
         if regrid is not None and (raw or shared is not None):
-            raise NotImplementedError("regrid= with devices=N is not supported: bins straddle the wavelength blocks")
+            raise NotImplementedError("%s= with devices=N is not supported: its windows straddle the wavelength blocks"
+                                      % regrid.kind)
         self.regrid, self.binned = regrid, None
         self.inp = inp = bundle.inputs
         self.opa = opa = opacityclass
@@ -686,7 +688,7 @@ class Spectrum:
             _lib.ctx_wait(self.ctx, self.tctx)
         rows, self.binned_lists = _regrid.spectral_rows(dev.get("albedo"), dev.get("thermal"), dev.get("transit_depth"), d_st,
                                                         self.sa, self.radius_star, self.atm.planet.radius)
-        self.binned = _regrid.Binned(self.regrid, ctx, rows, tails, keep=(d_st, self.keep_alive[:]))
+        self.binned = self.regrid.enqueue(ctx, rows, tails, keep=(d_st, self.keep_alive[:]))
 
     def _finish_binned(self):
         """``__call__`` with ``regrid=``: the dictionary of the plain call with every spectral array binned."""
@@ -707,7 +709,7 @@ class Spectrum:
             raw = {"thermal": None, "teff_integral": tails.pop(0)} if whole else {"thermal": self.disk.to_host()}
             _post_thermal(tmp, raw, self.wno, self.stellar, "nostar", np.nan, self.opa)
             teff = tmp["effective_temperature"]
-        out = _regrid.output(self.regrid, vals, self.binned_lists, bond, teff)
+        out = self.regrid.output(vals, self.binned_lists, bond, teff)
         del self.keep_alive[:]
         self.collect = []
         self.binned = None
