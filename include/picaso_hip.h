@@ -984,6 +984,36 @@ typedef struct picaso_regrid_row {
 int picaso_mean_regrid_dev(picaso_ctx *ctx, long nwno, int nbins, const int *start, int nrows,
                            const picaso_regrid_row *rows, double *out);
 
+/* ---- contribution functions (reference justplotit.py:1584-1643, :1697-1779) --------------------------------------------
+ * replaces justplotit.thermal_contribution's arithmetic (reference picaso/justplotit.py:1601-1611): with
+ * t = (taugas + taucld) + tauray clipped at tau_max (a NaN stays) and s = cumsum(t) down the column,
+ *   out[l][w] = blackbody(tlayer[l], 1 / wno[w]) * exp(-s[l][w]) * t[l][w] / dlnp[l],   l = 0 .. nlayer - 2,
+ * evaluated left to right without contraction; the Planck function is picaso_blackbody_dev's.  taugas, taucld (NULL:
+ * zeros), tauray: device (nlayer, nwno) with row pitch `pitch`, each element read once; wno: device (nwno); tlayer
+ * (nlayer) and dlnp (nlayer - 1, np.diff(np.log(layer pressure))): host; out: device (nlayer - 1, nwno).  nlayer == 1:
+ * an empty result, nothing is launched. */
+int picaso_thermal_cf_dev(picaso_ctx *ctx, int nlayer, int nwno, long pitch, const double *taugas, const double *taucld,
+                          const double *tauray, const double *tlayer, const double *wno, const double *dlnp,
+                          double tau_max, double *out);
+/* replaces justplotit.transmission_contribution's arithmetic (reference picaso/justplotit.py:1725-1750): the arguments of
+ * picaso_get_transit_1d_dev; out[k][w] = (norm - F_k) / sum_k (norm - F_k), device (nlevel - 1, nwno), where norm is the
+ * transit depth and F_k the depth with row k of dtau zeroed.  Not formed as that difference:
+ *   norm - F_k = (2 / rstar^2) sum_{i > k} z_i dz_i exp(-(TAUALL_i - c_ik)) (1 - exp(-c_ik)),
+ *   c_ik = 2 TAU[k] delta_length[i][i - k - 1],
+ * every term non-negative; the sums over i and over k run in increasing index order from +0.0, so a column's bits do not
+ * depend on the launch shape.  A column that absorbs nothing is NaN in every row (the reference's 0 / 0).  The LDS tile
+ * holds 128 levels; more: an error, nothing is launched. */
+int picaso_transit_cf_dev(picaso_ctx *ctx, const double *z, const double *dz, int nlevel, int nwno, long plane_pitch,
+                          double rstar, const double *mmw, double k_b, double amu, const double *player,
+                          const double *tlayer, const double *colden, const double *dtau, double *out);
+/* picaso_mean_regrid_dev for the rows of one device plane (replaces the row loop of reference
+ * picaso/justplotit.py:1621-1625, :1754-1758): out[r][j] = the mean of in[r * pitch + i], i in [start[j], start[j + 1]),
+ * with the same bits -- the sum in increasing i from +0.0, divided by the count; an empty bin is NaN.  start: device,
+ * nbins + 1 entries; in: device (nrows, nwno) with row pitch `pitch`; out: device (nrows, nbins).  nrows == 0: nothing is
+ * launched. */
+int picaso_mean_regrid_plane_dev(picaso_ctx *ctx, int nrows, long nwno, long pitch, int nbins, const int *start,
+                                 const double *in, double *out);
+
 /* ---- spectra convolved with a line-spread function (reference driver.py:338-381, conv_non_uniform_R) -----------------
  * out[r][i] = sum_k v_r[k] g_ik / sum_k g_ik over the model columns k in [lo[i], hi[i]), g_ik = exp(-(wl[k] - centre[i])^2
  * / den[i]): a Gaussian of sigma_i = centre_i / R_i / 2.355 (den = 2 sigma^2, formed by the caller) evaluated at the

@@ -9,18 +9,9 @@
 // pair with the wavelength index fastest: the write is the only HBM traffic that matters (8 B per element).
 #include "common.hpp"
 #include "device_math.hpp"
+#include "planck_cm.hpp"
 
 namespace pz {
-
-// planck_lambda of device_math.hpp takes a wavenumber and forms wcm = 1/wno; the public function is handed the
-// wavelength itself (the reference's thermal call passes 1/wno, so both see the same wcm bits)
-__device__ __forceinline__ double planck_lambda_cm(double t, double wcm)
-{
-#pragma clang fp contract(off)
-    const double h = 6.62607004e-27, c = 2.99792458e+10, k = 1.38064852e-16;
-    const double w2 = wcm * wcm;
-    return ((2.0 * h * (c * c)) / (w2 * w2 * wcm)) * planck_rcp(fexp(fdiv(h * c, t * (wcm * k))));
-}
 
 template <bool INTEGRATED>
 __global__ __launch_bounds__(256) void k_blackbody(int ntemp, long nwave, const double *__restrict__ t,

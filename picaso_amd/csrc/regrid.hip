@@ -23,14 +23,6 @@ struct MeanRegridArgs {
     double *out;                                    // (nrows, nbins)
 };
 
-// lane `i`'s value in every lane (`i` is the same in all of them)
-__device__ __forceinline__ double lane_value(double v, int i)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), i);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), i);
-    return __hiloint2double(hi, lo);
-}
-
 __global__ __launch_bounds__(64) void k_mean_regrid(const MeanRegridArgs a)
 {
 #pragma clang fp contract(off)
@@ -40,21 +32,7 @@ __global__ __launch_bounds__(64) void k_mean_regrid(const MeanRegridArgs a)
     long lo = a.start[j], hi = a.start[j + 1];
     lo = lo < 0 ? 0 : lo;
     hi = hi > a.nwno ? a.nwno : hi;
-    double s = 0.0;                                  // np.bincount's accumulator starts at +0.0
-    double v = lo + lane < hi ? regrid_elem(row, lo + lane) : 0.0;
-    for (long base = lo; base < hi; base += 64) {
-        const long next = base + 64 + lane;
-        const double vn = next < hi ? regrid_elem(row, next) : 0.0;      // in flight while this chunk is added
-        const long left = hi - base;
-        if (left >= 64) {
-#pragma unroll
-            for (int i = 0; i < 64; ++i) s = s + lane_value(v, i);
-        } else {
-            const int n = (int)left;
-            for (int i = 0; i < n; ++i) s = s + lane_value(v, i);
-        }
-        v = vn;
-    }
+    const double s = bin_sum(lo, hi, lane, [&](long i) { return regrid_elem(row, i); });
     const long count = hi > lo ? hi - lo : 0;
     if (lane == 0) a.out[(long)blockIdx.y * a.nbins + j] = s / (double)count;      // an empty bin: 0 / 0 = NaN
 }

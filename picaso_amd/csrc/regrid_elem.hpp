@@ -18,6 +18,40 @@ __device__ __forceinline__ double regrid_elem(const picaso_regrid_row &r, long i
     return q + p;
 }
 
+// lane `i`'s value in every lane (`i` is the same in all of them)
+__device__ __forceinline__ double lane_value(double v, int i)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), i);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), i);
+    return __hiloint2double(hi, lo);
+}
+
+// np.bincount's sum of one bin by one wave: elem(i) for i in [lo, hi), added in increasing i to +0.0 -- one chain of
+// dependent fp64 additions that every lane carries.  The wave reads the bin in coalesced chunks of 64 columns (lane l
+// forms elem(base + l)), a value reaches the adder through v_readlane (no LDS round trip, no barrier), and the next
+// chunk's loads are issued before the chain of the current one.
+template <typename Elem>
+__device__ __forceinline__ double bin_sum(long lo, long hi, int lane, Elem elem)
+{
+#pragma clang fp contract(off)
+    double s = 0.0;                                  // np.bincount's accumulator starts at +0.0
+    double v = lo + lane < hi ? elem(lo + lane) : 0.0;
+    for (long base = lo; base < hi; base += 64) {
+        const long next = base + 64 + lane;
+        const double vn = next < hi ? elem(next) : 0.0;                  // in flight while this chunk is added
+        const long left = hi - base;
+        if (left >= 64) {
+#pragma unroll
+            for (int i = 0; i < 64; ++i) s = s + lane_value(v, i);
+        } else {
+            const int n = (int)left;
+            for (int i = 0; i < n; ++i) s = s + lane_value(v, i);
+        }
+        v = vn;
+    }
+    return s;
+}
+
 // the argument checks the entry points share: `who` names the caller in the message
 inline int regrid_rows_check(picaso_ctx *ctx, const char *who, int nrows, const picaso_regrid_row *rows,
                              picaso_regrid_row *dst)

@@ -11,6 +11,7 @@
 // element exactly once (algorithmic bytes 8 nwno (nlayer + 1)).
 #include "common.hpp"
 #include "device_math.hpp"
+#include "transit_tab.hpp"
 
 namespace pz {
 
@@ -23,7 +24,6 @@ struct TransitArgs {
     double *out;               // (nwno)
 };
 
-constexpr int TRANSIT_BLOCK = 64;
 #ifndef PZ_TRANSIT_ROWS
 #define PZ_TRANSIT_ROWS 2
 #endif
@@ -98,13 +98,47 @@ __global__ __launch_bounds__(TRANSIT_BLOCK * TRANSIT_WAVES) void k_transit(const
 int launch_transit(picaso_ctx *ctx, const TransitArgs &a)
 {
     const size_t lds = sizeof(double) * (size_t)a.nlevel * TRANSIT_BLOCK;
-    if (lds > 160 * 1024 || a.nlevel > 64 * TRANSIT_WAVES)
+    if (lds > TRANSIT_LDS_MAX || a.nlevel > 64 * TRANSIT_WAVES)
         return fail(ctx, "get_transit_1d: %d levels exceed the LDS tile", a.nlevel);
     const long grid = (a.nwno + TRANSIT_BLOCK - 1) / TRANSIT_BLOCK;
     if (lds > 64 * 1024)
         PZ_HIP(ctx, hipFuncSetAttribute((const void *)k_transit, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_transit, dim3((unsigned)grid), dim3(TRANSIT_BLOCK * TRANSIT_WAVES), lds, ctx->stream, a);
     PZ_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
+// The wavelength-independent tables of one atmosphere, formed on the host in the reference's arithmetic and uploaded:
+// delta_length[nlevel*nlevel], zdz[nlevel], colden[nlayer], mmw_g[nlayer] (shared with contribfn.hip).
+int transit_tables(picaso_ctx *ctx, const double *z, const double *dz, int nlevel, double rstar, const double *mmw,
+                   double k_b, double amu, const double *player, const double *tlayer, const double *colden,
+                   const void **d_tab, double *zmin_term, double *two_over_rs2, bool conditioned)
+{
+    const int n = nlevel, nl = nlevel - 1;
+    std::vector<double> tab((size_t)n * n + n + 2 * (size_t)nl, 0.0);
+    double *dlen = tab.data(), *zdz = dlen + (size_t)n * n, *cd = zdz + n, *mg = cd + nl;
+    // chord segments between shells (fluxes.py:2625-2644); `player`/`tlayer` are indexed exactly as
+    // the reference indexes them (its caller passes the LEVEL pressure/temperature, justdoit.py:391-393)
+    double seg = 0.0;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < i; ++j) {
+            const double ref = z[i], inner = z[i - j], outer = z[i - j - 1];
+            if (conditioned) {
+                // the same two cases with a^2 - b^2 as (a - b)(a + b) and sqrt(p) - sqrt(q) as (p - q) / (sqrt(p) + sqrt(q)):
+                // a few roundings instead of the 2^-53 z / (2 dz) the squares' cancellation leaves in the form above
+                const double p = (outer - ref) * (outer + ref), q = (inner - ref) * (inner + ref);
+                if (inner != ref && outer != ref) seg = ((outer - inner) * (outer + inner)) / (sqrt(p) + sqrt(q));
+                else if (inner == ref) seg = sqrt(p);
+            } else if (inner != ref && outer != ref) seg = sqrt(outer * outer - ref * ref) - sqrt(inner * inner - ref * ref);
+            else if (inner == ref) seg = sqrt(outer * outer - ref * ref);
+            dlen[(size_t)i * n + j] = seg * player[i - j - 1] / tlayer[i - j - 1] / k_b;
+        }
+    double zmin = z[0];
+    for (int i = 0; i < n; ++i) { zdz[i] = z[i] * dz[i]; zmin = z[i] < zmin ? z[i] : zmin; }
+    for (int l = 0; l < nl; ++l) { cd[l] = colden[l]; mg[l] = mmw[l] * amu; }   // mmw in grams (:2623)
+    PZ_TRY(table_upload(ctx, tab.data(), sizeof(double) * tab.size(), d_tab));
+    *zmin_term = (zmin / rstar) * (zmin / rstar);
+    *two_over_rs2 = 2.0 / (rstar * rstar);
     return 0;
 }
 
@@ -124,28 +158,11 @@ int picaso_get_transit_1d_dev(picaso_ctx *ctx, const double *z, const double *dz
     PZ_NEED(ctx, "get_transit_1d", z, dz, mmw, player, tlayer, colden, dtau, rprs2);
     if (plane_pitch < nwno) return fail(ctx, "get_transit_1d: plane_pitch %ld < nwno %d", plane_pitch, nwno);
     PZ_HIP(ctx, hipSetDevice(ctx->device));
-    const int n = nlevel, nl = nlevel - 1;
-    std::vector<double> tab((size_t)n * n + n + 2 * (size_t)nl, 0.0);
-    double *dlen = tab.data(), *zdz = dlen + (size_t)n * n, *cd = zdz + n, *mg = cd + nl;
-    // chord segments between shells (fluxes.py:2625-2644); `player`/`tlayer` are indexed exactly as
-    // the reference indexes them (its caller passes the LEVEL pressure/temperature, justdoit.py:391-393)
-    double seg = 0.0;
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < i; ++j) {
-            const double ref = z[i], inner = z[i - j], outer = z[i - j - 1];
-            if (inner != ref && outer != ref) seg = sqrt(outer * outer - ref * ref) - sqrt(inner * inner - ref * ref);
-            else if (inner == ref) seg = sqrt(outer * outer - ref * ref);
-            dlen[(size_t)i * n + j] = seg * player[i - j - 1] / tlayer[i - j - 1] / k_b;
-        }
-    double zmin = z[0];
-    for (int i = 0; i < n; ++i) { zdz[i] = z[i] * dz[i]; zmin = z[i] < zmin ? z[i] : zmin; }
-    for (int l = 0; l < nl; ++l) { cd[l] = colden[l]; mg[l] = mmw[l] * amu; }   // mmw in grams (:2623)
-    const void *d_tab = nullptr;
-    PZ_TRY(table_upload(ctx, tab.data(), sizeof(double) * tab.size(), &d_tab));
     TransitArgs a{};
+    const void *d_tab = nullptr;
+    PZ_TRY(transit_tables(ctx, z, dz, nlevel, rstar, mmw, k_b, amu, player, tlayer, colden, &d_tab, &a.zmin_term,
+                          &a.two_over_rs2, false));
     a.nlevel = nlevel; a.nwno = nwno; a.pitch = plane_pitch; a.dtau = dtau; a.tab = (const double *)d_tab;
-    a.zmin_term = (zmin / rstar) * (zmin / rstar);
-    a.two_over_rs2 = 2.0 / (rstar * rstar);
     a.out = rprs2;
     return launch_transit(ctx, a);
 }

@@ -1,0 +1,193 @@
+"""Generate tests/golden/contribfn.npz by running the REFERENCE's own source (build container only):
+
+    python tests/golden/make_contribfn.py
+
+``justplotit.thermal_contribution`` (reference justplotit.py:1584-1643) and ``justplotit.transmission_contribution``
+(:1697-1779) on synthetic ``full_output`` dictionaries: 150 wavenumbers (two full 64-lane tiles and a partial one) with a
+gap and one isolated point, so that R = 60 leaves bins empty and one bin with a single column; 13, 3 and 2 levels (the
+last two: fewer chords than waves, a single layer, an empty thermal result); a T(p) that is not isothermal, a cloud slab,
+one opaque layer (dtau 1e4), one all-zero column and one column with a NaN in taugas.
+
+Stored per scene ``s<nlevel>``: the inputs, the reference's thermal CF for tau_max 1 and 1e3 and its CF_bin (tau_max 1,
+R = 60), the reference's transmission CF (its own arguments: layer pressure in bar, layer temperature, constants 1), and
+the same transmission formula restated here in np.longdouble (``tr_cf_x80``) in the non-negative form of DESIGN.md.
+Asserted: the float64 restatement of the transit depth equals the reference's get_transit_1d within nlevel 2^-52, no
+column but the deliberate ones is NaN, and nothing lies in the denormal range where a comparison would be undefined."""
+import importlib
+import os
+import sys
+import types
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+import ref_shim  # noqa: E402
+
+NWNO, R_BIN = 150, 60
+COL_OPAQUE, COL_ZERO, COL_NAN = 17, 70, 131          # one in each 64-lane tile
+TAU_MAXES = (1.0, 1e3)
+
+
+def _justplotit():
+    import matplotlib
+    matplotlib.use("Agg")
+    ref_shim.load("optics")                            # installs the shims and the `picaso` package stub
+    for name in ("bokeh.layouts", "bokeh.models.annotations", "bokeh.transform", "scipy.stats.stats"):
+        if name not in sys.modules:
+            sys.modules[name] = ref_shim._Dummy(name)
+    for name, mod in list(sys.modules.items()):       # `import a.b as c` reads the attribute b of a
+        parent, _, child = name.rpartition(".")
+        if parent and isinstance(sys.modules.get(parent), ref_shim._Dummy) and isinstance(mod, ref_shim._Dummy):
+            setattr(sys.modules[parent], child, mod)
+    return importlib.import_module("picaso.justplotit")
+
+
+def scene(nlevel):
+    """A ``full_output`` dictionary with the reference's keys."""
+    nlayer = nlevel - 1
+    rng = np.random.default_rng(100 + nlevel)
+    wno = np.concatenate((np.linspace(2000.0, 2400.0, 99), [2700.0], np.linspace(3000.0, 3300.0, 50)))
+    assert wno.size == NWNO
+    plev = np.logspace(-5, 1.5, nlevel)                                    # bar
+    x = (np.log10(plev) + 5) / 6.5
+    tlev = 220.0 + 1100.0 * x ** 1.5 - 60.0 * np.sin(3 * x)               # not isothermal
+    play, tlay = np.sqrt(plev[1:] * plev[:-1]), 0.5 * (tlev[1:] + tlev[:-1])
+    mmw = np.full(nlayer, 2.3) + 0.02 * np.arange(nlayer)
+    k_b, amu, g, radius = 1.380649e-16, 1.66053906660e-24, 2500.0, 7.0e9
+    scale_h = k_b * tlay / (mmw * amu * g)
+    dz_lay = scale_h * np.log(plev[1:] / plev[:-1])
+    z = radius + np.concatenate((np.cumsum(dz_lay[::-1])[::-1], [0.0]))    # decreasing, the bottom at `radius`
+    dz = np.concatenate(([dz_lay[0]], dz_lay))
+    # the reference's call makes every slant depth 1e-6 k_b / amu = 83 times the physical one (bar, constants 1), some
+    # 5e3 times the vertical depth on this planet: the column density is scaled up so that slant depths stay of order one
+    colden = 5.0e3 * (plev[1:] - plev[:-1]) * 1e6 / g
+    lam = (wno - wno[0]) / (wno[-1] - wno[0])
+    depth = np.diff(plev)[:, None] / plev[-1]
+    taugas = 30.0 * depth ** 0.8 * 10.0 ** (1.5 * np.sin(9 * lam)[None, :] - 1.0) * rng.uniform(0.7, 1.3, (nlayer, NWNO))
+    tauray = 2.0 * depth * (wno[None, :] / 3300.0) ** 4
+    taucld = np.zeros((nlayer, NWNO))
+    slab = slice(nlayer // 2, nlayer // 2 + max(1, nlayer // 4))
+    taucld[slab] = 0.4 * (1.0 + 0.3 * lam)[None, :]
+    k_opaque = nlayer // 3
+    taugas[k_opaque, COL_OPAQUE] = 1e4
+    taugas[:, COL_ZERO] = tauray[:, COL_ZERO] = taucld[:, COL_ZERO] = 0.0
+    taugas[min(1, nlayer - 1), COL_NAN] = np.nan
+    shape3 = (nlayer, NWNO, 1)
+    return {"wavenumber": wno, "taugas": taugas.reshape(shape3), "taucld": taucld.reshape(shape3),
+            "tauray": tauray.reshape(shape3),
+            "layer": {"pressure": play, "temperature": tlay, "column_density": colden, "mmw": mmw},
+            "level": {"pressure": plev, "temperature": tlev, "z": z, "dz": dz}}
+
+
+def transit_terms(full, dtype):
+    """get_transit_1d (reference fluxes.py:2581-2663) with the reference's arguments (justplotit.py:1728-1738), restated
+    in ``dtype``: ``(F, D)`` -- the transit depth and ``D[k] = sum_{i>k} z_i dz_i exp(-(TAUALL_i - c_ik)) (1 - exp(-c_ik))``,
+    so that ``norm - F_k = 2 D[k]`` (rstar = 1)."""
+    T = dtype
+    z, dz = full["level"]["z"].astype(T), full["level"]["dz"].astype(T)
+    player, tlayer = full["layer"]["pressure"].astype(T), full["layer"]["temperature"].astype(T)
+    colden, mmw = full["layer"]["column_density"].astype(T), full["layer"]["mmw"].astype(T)
+    dtau = ((full["taugas"][:, :, 0] + full["taucld"][:, :, 0]) + full["tauray"][:, :, 0]).astype(T)
+    n = z.size
+    dl = np.zeros((n, n), dtype=T)
+    seg = T(0)
+    for i in range(n):
+        for j in range(i):
+            ref, inner, outer = z[i], z[i - j], z[i - j - 1]
+            if inner != ref and outer != ref:
+                seg = np.sqrt(outer ** 2 - ref ** 2) - np.sqrt(inner ** 2 - ref ** 2)
+            elif inner == ref:
+                seg = np.sqrt(outer ** 2 - ref ** 2)
+            dl[i, j] = seg * player[i - j - 1] / tlayer[i - j - 1]
+    tau = dtau / colden[:, None] * mmw[:, None]
+    tauall = np.zeros((n, dtau.shape[1]), dtype=T)
+    for i in range(n):
+        for j in range(i):
+            tauall[i] = tauall[i] + 2 * tau[i - j - 1] * dl[i, j]
+    F = (z.min() / T(1)) ** 2 + T(2) * ((T(1) - np.exp(-tauall)) * (z * dz)[:, None]).sum(axis=0)
+    D = np.zeros((n - 1, dtau.shape[1]), dtype=T)
+    for k in range(n - 1):
+        for i in range(k + 1, n):
+            c = 2 * tau[k] * dl[i, i - k - 1]
+            D[k] = D[k] + (z[i] * dz[i]) * np.exp(-(tauall[i] - c)) * -np.expm1(-c)
+    return F, D
+
+
+def main():
+    jpi = _justplotit()
+    fluxes = ref_shim.load("fluxes")
+    import matplotlib.pyplot as plt
+    store = {"nlevels": np.array([13, 3, 2]), "R": np.array(R_BIN), "tau_maxes": np.array(TAU_MAXES),
+             "cols": np.array([COL_OPAQUE, COL_ZERO, COL_NAN])}
+    worst = 0.0
+    for nlevel in (13, 3, 2):
+        full = scene(nlevel)
+        nlayer, tag = nlevel - 1, "s%d/" % nlevel
+        for k in ("taugas", "taucld", "tauray"):
+            store[tag + k] = full[k][:, :, 0]
+        store[tag + "wno"] = full["wavenumber"]
+        for grp in ("layer", "level"):
+            for k, v in full[grp].items():
+                store["%s%s/%s" % (tag, grp, k)] = v
+        # ---- thermal
+        with np.errstate(all="ignore"):
+            for tm in TAU_MAXES:
+                if nlayer > 1:
+                    cf = jpi.thermal_contribution(full, tau_max=tm, R=None)[2]
+                else:
+                    cf = np.zeros((0, NWNO))                  # the reference's figure cannot draw an empty plane
+                plt.close("all")
+                assert cf.shape == (nlayer - 1, NWNO)
+                bad = np.isnan(cf).any(axis=0)
+                assert not bad[np.arange(NWNO) != COL_NAN].any()
+                assert not ((cf != 0) & (np.abs(cf) < 1e-290)).any()
+                store["%sth_cf/%g" % (tag, tm)] = cf
+            if nlayer > 1:
+                cf_bin = jpi.thermal_contribution(full, tau_max=1.0, R=R_BIN)[2]
+                plt.close("all")
+                store[tag + "th_cf_bin"] = cf_bin
+                centres = jpi.mean_regrid(full["wavenumber"], full["wavenumber"], R=R_BIN)[0]
+                d = np.diff(centres)
+                edges = np.concatenate(([centres[0] - d[0] / 2], centres[:-1] + d / 2.0, [centres[-1] + d[-1] / 2]))
+                counts = np.histogram(full["wavenumber"], bins=edges)[0]
+                assert (counts == 0).any() and (counts == 1).any(), counts
+                nan_bin = np.searchsorted(edges, full["wavenumber"][COL_NAN], side="right") - 1
+                want = (counts == 0) | ((np.arange(counts.size) == nan_bin) & np.isnan(cf[-1, COL_NAN]))
+                assert np.array_equal(np.isnan(cf_bin[-1]), want)
+                store[tag + "bin_counts"] = counts
+                store[tag + "bin_wavenumber"] = centres
+        # ---- transmission, the reference's arguments
+        with np.errstate(all="ignore"):
+            cf_ref = jpi.transmission_contribution(full, R=None)[3]
+            plt.close("all")
+            dtau = (full["taugas"][:, :, 0] + full["taucld"][:, :, 0]) + full["tauray"][:, :, 0]
+            f_ref = fluxes.get_transit_1d(full["level"]["z"], full["level"]["dz"], nlevel, NWNO, 1, full["layer"]["mmw"], 1, 1,
+                                          full["layer"]["pressure"], full["layer"]["temperature"],
+                                          full["layer"]["column_density"], dtau)
+            f64, _ = transit_terms(full, np.float64)
+            _, d80 = transit_terms(full, np.longdouble)
+            cf80 = d80 / d80.sum(axis=0)
+        ok = np.arange(NWNO) != COL_NAN
+        assert np.all(np.abs(f64[ok] - f_ref[ok]) <= nlevel * 2.0 ** -52 * np.abs(f_ref[ok]))
+        assert np.isnan(f_ref[COL_NAN]) and np.isnan(cf80[:, COL_NAN]).all() and np.isnan(cf80[:, COL_ZERO]).all()
+        ok[COL_ZERO] = False
+        assert not np.isnan(cf80[:, ok]).any() and np.isfinite(cf80[:, COL_OPAQUE]).all()
+        # a share the opaque layer hides is ~ exp(-5e3): 0 in float64, here and on the device; none may lie near the edge
+        assert not ((cf80 > np.longdouble("1e-400")) & (cf80 < 1e-280)).any()
+        cf80 = cf80.astype(np.float64)
+        gap = np.nanmax(np.abs(cf_ref[:, ok] - cf80[:, ok]))
+        worst = max(worst, gap)
+        print("nlevel %d: max |ref - x80| = %.3e, smallest share %.3e, opaque column %s" % (
+            nlevel, gap, cf80[:, ok][cf80[:, ok] > 0].min(), cf80[:, COL_OPAQUE]))
+        store[tag + "tr_cf_ref"] = cf_ref
+        store[tag + "tr_cf_x80"] = cf80
+    path = os.path.join(HERE, "contribfn.npz")
+    np.savez_compressed(path, **store)
+    print("wrote", path, "%.1f KB" % (os.path.getsize(path) / 1024), "largest |ref - x80| = %.3e" % worst)
+
+
+if __name__ == "__main__":
+    main()
