@@ -1028,6 +1028,30 @@ int picaso_lsf_convolve_dev(picaso_ctx *ctx, long nwno, const double *wl, int no
                             const double *den, const int *lo, const int *hi, int nrows, const picaso_regrid_row *rows,
                             double *out /* (nrows, nobs) */);
 
+/* ---- correlated-k tables from line-by-line cross sections (reference opacity_factory.py:1927-1955) --------------------
+ * replaces the bin loop of compute_ck_molecular for ONE P-T point.  xsec: device, the row of n_lbl cross sections.  Bin b
+ * takes the points [lo[b], lo[b] + n[b]) of the row (lo, n: host, nbins entries each; the caller turns the reference's
+ * membership test (og > low) & (og <= high) into them, picaso_amd/opacity_factory.py: ck_segments); bins may overlap, be
+ * empty and come in any order.  Per bin: values <= 0.0 (-0.0 included) become 1e-200, the values are ordered ascending and
+ *   k[b][i] = np.interp(g[i], x, ln(sorted)),   x[j] = j / (n - 1.)
+ * in numpy's operation order, nothing contracted; only the order statistics at j and j + 1 of every Gauss point meet the
+ * logarithm, so k differs from the reference by the rounding of 2 logarithms per element.  n[b] < 2: -200.0, as the
+ * reference.  g: host, ngauss in [1, 32] abscissae strictly inside (0, 1).
+ * Segments of up to lds_cap points are sorted in LDS, longer ones are selected from HBM by radix (csrc/ckfactory.hip); both
+ * give the same bits.  lds_cap: 0 = the built-in default, 16 384 (128 KiB of LDS), which is also the largest value.
+ * k: device (nbins, ngauss).  stats: device (nbins, ngauss, 2) or NULL: the clamped order statistics sorted[j], sorted[j+1]
+ * behind every k (1e-200 where n[b] < 2).  nbins: at most 262 144 per call (lo and n travel in one 4 MiB table slot).
+ * Unlike the other _dev entry points this one WAITS for its kernels: a NaN in a used segment is an error (the lowest such
+ * bin is named), as are a negative count, lo + n > n_lbl, too many bins, ngauss < 1 and g outside (0, 1); for those nothing
+ * is launched. */
+int picaso_ck_from_xsec_dev(picaso_ctx *ctx, long n_lbl, const double *xsec, int nbins, const long long *lo,
+                            const long long *n, int ngauss, const double *g, long lds_cap, double *k /* (nbins, ngauss) */,
+                            double *stats /* (nbins, ngauss, 2) or NULL */);
+/* the upload that goes with it: `bytes` from a pinned block of picaso_host_alloc to device memory, enqueued on the
+ * context's stream; returns at once.  The next row of cross sections travels on a second context's stream while the kernels
+ * of the current one run; picaso_ctx_wait / picaso_sync order it. */
+int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

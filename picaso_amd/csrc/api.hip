@@ -458,6 +458,14 @@ int picaso_memcpy_d2h_async(picaso_ctx *ctx, void *pinned_dst, const void *src, 
     *mark = (void *)ev;
     return 0;
 }
+int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, size_t bytes)
+{
+    if (!ctx || !dst || !pinned_src) return fail(ctx, "picaso_memcpy_h2d_async: null argument");
+    if (bytes == 0) return 0;
+    PZ_HIP(ctx, hipSetDevice(ctx->device));
+    PZ_HIP(ctx, hipMemcpyAsync(dst, pinned_src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+}
 int picaso_mark_wait(picaso_ctx *ctx, void *mark)
 {
     if (!ctx || !mark) return fail(ctx, "picaso_mark_wait: null argument");
