@@ -623,6 +623,22 @@ int picaso_get_thermal_1d_ck_tbatch_dev(picaso_ctx *ctx, int nitem, int nlevel, 
  * (device (nitem, nlevel) each).  Deterministic tree sums, not numpy's order: ~1e-16 of sum|terms| from get_fluxes' own. */
 int picaso_flux_net_sums_dev(picaso_ctx *ctx, int nlevel, int nitem, int nwno, const double *disk4,
                              const double *dwno, double *net_layer, double *net);
+/* What climate.t_start reads of the thermal leg, for `nitem` level-temperature profiles over ONE set of opacity planes:
+ * net_layer[profile][level] and net[profile][level] (DEVICE, (nitem, nlevel) each), the sums over disk angle, Gauss
+ * point and wavenumber of (flux_plus - flux_minus) dwno at the layer mid-points and at the levels, with bin-integrated
+ * Planck functions (calc_type 1).  Arguments as picaso_get_thermal_1d_ck_tbatch_dev (tlevel, plevel, ubar1, gauss_wts,
+ * gweight, tweight on the HOST).  The per-angle level planes are never written: one kernel carries every angle of a column
+ * in registers and reduces in place (toon_lvl.hip, k_thermal_lvl_nets).  No atomics; bit-identical from run to run and
+ * whatever nitem is; a batch larger than the context's scratch budget is processed in chunks of profiles.  Agrees with
+ * picaso_get_thermal_1d_ck_tbatch_dev + picaso_flux_net_sums_dev to ~1e-16 of sum |terms| (the sums are associated
+ * differently).  numg * numt may not exceed picaso_thermal_nets_max_angles() (10). */
+int picaso_thermal_nets_tbatch_dev(picaso_ctx *ctx, int nitem, int nlevel, const double *wno, int nwno, int ngauss,
+                                   int numg, int numt, const double *tlevel, const double *dtau, const double *w0,
+                                   const double *cosb, const double *plevel, const double *ubar1,
+                                   const double *surf_reflect, int hard_surface, const double *dwno,
+                                   const double *gauss_wts, const double *gweight, const double *tweight,
+                                   double *net_layer, double *net);
+int picaso_thermal_nets_max_angles(void);
 /* np.trapezoid(y', x) with d = diff(x) resident: sum_j (d[j] * (y'[j + 1] + y'[j])) / 2.0 over the n - 1 intervals, summed
  * in numpy's own pairwise order (blocks of <= 128 terms with eight partial sums), so the same bits as the reference's
  * spectrum-wide integrals (justdoit.py:552-599: Bond albedo, effective temperature).  y'[k] = y[k] * mult[k] (mult may be

@@ -65,6 +65,14 @@ def load():
     lib.picaso_version.restype = ctypes.c_char_p
     lib.picaso_stream.restype = ctypes.c_void_p
     lib.picaso_stream.argtypes = [ctypes.c_void_p]
+    i, p, v = ctypes.c_int, c_double_p, ctypes.c_void_p
+    if not hasattr(lib, "picaso_thermal_nets_tbatch_dev"):
+        raise PicasoHipError("picaso_amd: %s was built from older sources (no picaso_thermal_nets_tbatch_dev): rebuild it "
+                             "from this tree" % LIB_PATH)
+    lib.picaso_thermal_nets_tbatch_dev.restype = ctypes.c_int
+    lib.picaso_thermal_nets_tbatch_dev.argtypes = [v, i, i, v, i, i, i, i, p, v, v, v, p, p, v, i, v, p, p, p, v, v]
+    lib.picaso_thermal_nets_max_angles.restype = ctypes.c_int
+    lib.picaso_thermal_nets_max_angles.argtypes = []
     _lib = lib
     return lib
 

@@ -31,7 +31,9 @@ OpacityNoEd_Tuple = namedtuple("OpacityNoEd_Tuple", ["DTAU", "TAU", "W0", "COSB"
 ScatteringPhase_Tuple = namedtuple("ScatteringPhase_Tuple", ["surf_reflect", "single_phase", "multi_phase", "frac_a",
                                                              "frac_b", "frac_c", "constant_back", "constant_forward"])
 Disco_Tuple = namedtuple("Disco_Tuple", ["ng", "nt", "gweight", "tweight", "ubar0", "ubar1", "cos_theta"])
-Opagrid_Tuple = namedtuple("Opagrid_Tuple", ["nwno", "delta_wno", "wno", "ngauss", "gauss_wts"])
+# tmin / tmax: the temperature range of the opacity grid, which t_start keeps its trial profiles inside
+Opagrid_Tuple = namedtuple("Opagrid_Tuple", ["nwno", "delta_wno", "wno", "ngauss", "gauss_wts", "tmin", "tmax"],
+                           defaults=(-np.inf, np.inf))
 
 
 @_lib.serialized
@@ -277,3 +279,434 @@ def get_fluxes_tbatch(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, Scatter
     if nets_only:
         return net_layer, net
     return net_layer, net, plus, minus
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The T(P) iteration (reference climate.t_start, climate.py:805-1552) and its helpers.  Host code: the device work of a
+# Newton step is the flux calls, everything else is O(nlevel^2) arithmetic.
+# ---------------------------------------------------------------------------------------------------------------------
+AdiabatBundle_Tuple = namedtuple("AdiabatBundle_Tuple", ["t_table", "p_table", "grad", "cp"])
+convergence_criteriaT = namedtuple("Conv", ["it_max", "itmx", "conv", "convt", "x_max_mult"])     # climate.py:21
+MAX_LEVELS = 128         # the limit the contribution kernels state; mat_sol has no NMAX = 100 / int8 index limit
+
+
+def load_adiabat(path=None):
+    """The H/He adiabat table of the reference (justdoit.py:1726-1735): log10 T (K), log10 P (bar), the adiabatic
+    gradient d ln T / d ln P and log10 cp (erg/g/K) -> ``AdiabatBundle_Tuple``.  ``path=None`` reads
+    ``$picaso_refdata/climate_INPUTS/specific_heat_p_adiabat_grad.json``."""
+    import json
+    if path is None:
+        ref = os.environ.get("picaso_refdata")
+        if ref is None:
+            raise Exception("no file was given and the picaso_refdata environment variable is not set: the adiabat table "
+                            "is looked up under $picaso_refdata/climate_INPUTS, as in the reference")
+        path = os.path.join(ref, "climate_INPUTS", "specific_heat_p_adiabat_grad.json")
+    with open(path) as fh:
+        tab = json.load(fh)
+    return AdiabatBundle_Tuple(np.array(tab["temperature"], dtype=float), np.array(tab["pressure"], dtype=float),
+                               np.array(tab["adiabat_grad"], dtype=float), np.array(tab["specific_heat"], dtype=float))
+
+
+def locate(array, value):
+    """Index ``jl`` of the reference's bisection (climate.py:611-646): the last ``jl`` with ``array[jl] <= value``,
+    0 at or below the first point, ``n - 1`` at or above the last.  ``value`` may be an array."""
+    array = np.asarray(array)
+    n = len(array)
+    v = np.asarray(value, dtype=float)
+    jl = np.clip(np.searchsorted(array, v, side="right") - 1, 0, n - 1)
+    jl = np.where(np.isnan(v) | (v <= array[0]), 0, jl)          # a NaN fails every comparison of the bisection
+    jl = np.where(v >= array[-1], n - 1, jl)
+    return int(jl) if jl.ndim == 0 else jl.astype(np.intp)
+
+
+def did_grad_cp(t, p, AdiabatBundle):
+    """Adiabatic gradient and specific heat at temperature ``t`` (K) and pressure ``p`` (bar): bilinear in the table's
+    log10 axes (reference climate.py:497-567).  As there, the first cell of either axis is not interpolated (the weight is
+    0 below the second point) and points off the table take the edge.  ``t`` and ``p`` may be arrays of one shape."""
+    t_table, p_table, grad, cp = (np.asarray(AdiabatBundle.t_table), np.asarray(AdiabatBundle.p_table),
+                                  np.asarray(AdiabatBundle.grad), np.asarray(AdiabatBundle.cp))
+    temp_log, pres_log = np.log10(np.asarray(t, dtype=float)), np.log10(np.asarray(p, dtype=float))
+
+    def weights(table, x):
+        last = len(table) - 1
+        pos = np.asarray(locate(table, x))
+        top = pos == last
+        pos = np.where(top, last - 1, pos)
+        with np.errstate(invalid="ignore"):
+            fact = (-table[pos] + x) / (table[pos + 1] - table[pos])
+        return pos, np.where(top, 1.0, np.where(pos == 0, 0.0, fact))
+    pos_t, factkt = weights(t_table, temp_log)
+    pos_p, factkp = weights(p_table, pres_log)
+
+    def bilinear(z):
+        return ((1.0 - factkt) * (1.0 - factkp) * z[pos_t, pos_p] + factkt * (1.0 - factkp) * z[pos_t + 1, pos_p]
+                + factkt * factkp * z[pos_t + 1, pos_p + 1] + (1.0 - factkt) * factkp * z[pos_t, pos_p + 1])
+    grad_x, cp_x = bilinear(grad), 10 ** bilinear(cp)
+    if np.ndim(grad_x) == 0:
+        return float(grad_x), float(cp_x)
+    return grad_x, cp_x
+
+
+def convec(temp, pressure, AdiabatBundle, Atmosphere, moist=False):
+    """``grad_x, cp_x`` of every layer: ``did_grad_cp`` at the mean temperature and the geometric-mean pressure
+    (reference climate.py:570-608)."""
+    if moist:
+        raise NotImplementedError("convec: the moist adiabat is not implemented")
+    temp, pressure = f64(temp), f64(pressure)
+    tbar = 0.5 * (temp[:-1] + temp[1:])
+    pbar = np.sqrt(pressure[:-1] * pressure[1:])
+    return did_grad_cp(tbar, pbar, AdiabatBundle)
+
+
+def mat_sol(a, nlevel, nstrat, dflux):
+    """Solve the leading ``nstrat x nstrat`` system of ``a`` for the right-hand side ``dflux[:nstrat]``, in place, and
+    return ``a, dflux`` as the reference does (climate.py:650-802): LU decomposition with implicit row scaling, then
+    back substitution.  The pivot of a column is the LAST row whose scaled magnitude reaches the maximum (``dum >= aamax``),
+    and an exactly zero pivot becomes 1e-20.
+
+    Rows at a time: the decomposition eliminates one column per step over all remaining rows, which gives every element
+    the reference's subtractions in the reference's order; the substitutions run a running sum along each row."""
+    n = int(nstrat)
+    if not 0 < n <= int(nlevel) <= MAX_LEVELS:
+        raise ValueError("mat_sol: needs 0 < nstrat <= nlevel <= %d, got nstrat=%d nlevel=%d" % (MAX_LEVELS, n, nlevel))
+    m = a[:n, :n]                                                # a view: the caller's matrix holds the factors
+    b = dflux
+    aamax = np.abs(m).max(axis=1)
+    if np.any(aamax == 0.0):
+        raise ValueError("Array is singular, cannot be decomposed in n:" + str(n))
+    vv = 1.0 / aamax
+    indx = np.zeros(n, dtype=np.intp)
+    imax = 0
+    for j in range(n):
+        dum = vv[j:] * np.abs(m[j:, j])
+        hit = np.flatnonzero(dum >= np.fmax.reduce(dum, initial=0.0))        # a NaN row never compares >=
+        if len(hit):
+            imax = j + int(hit[-1])
+        if imax != j:
+            m[[j, imax]] = m[[imax, j]]
+            vv[imax] = vv[j]
+        indx[j] = imax
+        if m[j, j] == 0:
+            m[j, j] = 1e-20
+        if j != n - 1:
+            m[j + 1:, j] *= 1.0 / m[j, j]
+            m[j + 1:, j + 1:] -= np.outer(m[j + 1:, j], m[j, j + 1:])
+    for i in range(n):                                            # forward, unscrambling the permutation
+        ll = indx[i]
+        s = b[ll]
+        b[ll] = b[i]
+        b[i] = np.cumsum(np.concatenate(([s], -(m[i, :i] * b[:i]))))[-1]
+    for i in range(n - 1, -1, -1):
+        b[i] = np.cumsum(np.concatenate(([b[i]], -(m[i, i + 1:] * b[i + 1:n]))))[-1] / m[i, i]
+    return a, b
+
+
+def check_convergence(f_vec, n_total, tolf, check, f, dflux, tolmin, temp, temp_old, g, tolx):
+    """The three exits of the line search (reference climate.py:1555-1631) -> ``flag_converge, check``: 2 when the
+    largest residual is below ``tolf``, 2 on a step too small to continue (``check``: whether the gradient vanishes too),
+    2 when the first ``n_total`` temperatures moved by less than ``tolx``; 1 otherwise (take another Newton step)."""
+    n = int(n_total)
+    def largest(x):                                               # of a running `if x > test`: from 0, NaNs passed over
+        return np.fmax.reduce(x, initial=0.0)
+    if largest(np.abs(f_vec[:n])) < tolf:
+        return 2, False
+    if check:
+        den1 = max(f, 0.5 * n)
+        return 2, bool(largest(np.abs(g[:n]) * dflux[:n] / den1) < tolmin)
+    test = largest(np.abs(temp[:n] - temp_old[:n]) / temp_old[:n])
+    if test < tolx:
+        return 2, check
+    return 1, check
+
+
+def growup(nlv, nstr, ngrow):
+    """Move the top of convective zone ``nlv`` up by ``ngrow`` levels (reference climate.py:1634-1652)."""
+    nstr[3 * (nlv - 1) + 1] -= ngrow
+    return nstr
+
+
+def growdown(nlv, nstr, ngrow):
+    """Move the bottom of convective zone ``nlv`` and the top of the radiative zone below it down by ``ngrow`` levels
+    (reference climate.py:1655-1675)."""
+    n = 3 * (nlv - 1) + 2
+    nstr[n] += ngrow
+    nstr[n + 1] += ngrow
+    return nstr
+
+
+@_lib.serialized
+def get_nets_tbatch(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Opagrid, do_holes=False,
+                    fhole=0.0, hole_OpacityWEd=None, hole_OpacityNoEd=None, ctx=None):
+    """``flux_net_ir_layer, flux_net_ir`` ``(nitem, nlevel)`` of every level-temperature profile in ``temperatures``
+    ``(nitem, nlevel)`` over one set of opacities: what ``t_start`` reads of a thermal ``get_fluxes`` call, for the
+    perturbed profiles of a Jacobian in one batch and for a line-search trial with ``nitem = 1``.
+
+    Patchy clouds (``do_holes``): the nets are linear in the fluxes, so the cloudy and the clear plane sets are run one
+    after the other and their ``2 * nlevel`` numbers per profile are blended ``(1 - fhole) * cloudy + fhole * clear``
+    here."""
+    ctx = ctx if ctx is not None else _lib.context()
+    if do_holes and (hole_OpacityWEd is None or hole_OpacityNoEd is None):
+        raise Exception("get_nets_tbatch: do_holes=True needs hole_OpacityWEd and hole_OpacityNoEd")
+    out = _nets_one_set(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Opagrid, ctx)
+    if do_holes:
+        clear = _nets_one_set(temperatures, Atmosphere, hole_OpacityWEd, hole_OpacityNoEd, ScatteringPhase, Disco, Opagrid,
+                              ctx)
+        out = tuple((1.0 - fhole) * a + fhole * b for a, b in zip(out, clear))
+    return out
+
+
+def _nets_one_set(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Opagrid, ctx):
+    """One plane set of get_nets_tbatch: the fused kernel, or -- past the angle count it is compiled for -- the level
+    planes of get_fluxes_tbatch summed on the device."""
+    ng, nt = int(Disco.ng), int(Disco.nt)
+    if ng * nt > resident.thermal_nets_max_angles():
+        return get_fluxes_tbatch(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Opagrid,
+                                 ctx=ctx, nets_only=True)
+    temps = f64(temperatures)
+    nlevel = int(Atmosphere.nlevel)
+    if temps.ndim != 2 or temps.shape[1] != nlevel:
+        raise Exception("get_nets_tbatch: temperatures must be (nitem, nlevel=%d)" % nlevel)
+    nitem = temps.shape[0]
+    nwno, ngauss = int(Opagrid.nwno), int(Opagrid.ngauss)
+    rs = _resident_small(np.zeros(nwno) + f64(ScatteringPhase.surf_reflect), ctx)
+    pl = _planes(OpacityWEd, OpacityNoEd, ctx, thermal_only=True)
+    d_wno, d_dw = _resident_small(f64(Opagrid.wno), ctx), _resident_small(f64(Opagrid.delta_wno), ctx)
+    both = DeviceArray((2, nitem, nlevel), ctx)
+    resident.thermal_nets_tbatch(ctx, nlevel, d_wno, nwno, ngauss, ng, nt, temps, pl["dtau_og"], pl["w0_no_raman"],
+                                 pl["cosb_og"], Atmosphere.p_level, Disco.ubar1, rs, 0, Opagrid.gauss_wts, Disco.gweight,
+                                 Disco.tweight, d_dw, both.row_block(0), both.row_block(1))
+    out = both.to_host()
+    return out[0], out[1]
+
+
+def _lapse(temp, pressure):
+    return (np.log(temp[:-1]) - np.log(temp[1:])) / (np.log(pressure[:-1]) - np.log(pressure[1:]))
+
+
+def t_start(nofczns, nstr, convergence_criteria, rfaci, rfacv, tidal, Atmosphere, OpacityWEd, OpacityNoEd,
+            ScatteringPhase, Disco, Opagrid, AdiabatBundle, F0PI, save_profile, all_profiles, fhole=None,
+            hole_OpacityWEd=None, hole_OpacityNoEd=None, verbose=1, do_holes=None, moist=False, egp_stepmax=False,
+            ctx=None, _fluxes=None):
+    """Newton-Raphson iteration on the level temperatures that zeroes the net flux in the radiative zones, with the
+    opacities held fixed (reference ``climate.t_start``, climate.py:805-1552; same positional arguments).  Returns
+    ``temp, dtdp, all_profiles, flux_net_ir, flux_net_v, flux_plus_ir[0, :]``; when ``it_max`` runs out the fourth value
+    is ``flux_net_ir_layer``, as in the reference.
+
+    ``nstr`` describes the zones: ``nstr[0]`` the top level (0), ``nstr[1]`` the last radiative level of the upper zone,
+    ``nstr[2]`` the last layer of the convective zone below it, and ``nstr[3:6]`` the same for a second pair when
+    ``nofczns = 2``.  The unknowns are the temperatures of the radiative levels; a convective zone continues the adiabat
+    from the level above it (``did_grad_cp``).  The residuals are the net flux (``rfaci * IR + rfacv * visible + tidal``) at
+    the top level and at the layer midpoints of the radiative zones.
+
+    One step: every unknown is raised by ``max(1e-4 T, 3)`` K in turn and the profile rebuilt; the IR nets of ALL those
+    profiles come from one batched call and give the finite-difference matrix ``A``; ``mat_sol`` solves ``A p = -f``; the
+    step is capped (``egp_stepmax``: 0.005 of the temperature norm; otherwise a cap that is multiplied by that norm
+    and by ``(it_max - its) / it_max`` every iteration); a backtracking line search on ``0.5 |f|^2`` follows, each trial one
+    nets-only call, temperatures held inside ``(Opagrid.tmin, Opagrid.tmax)``, ended by ``check_convergence``.
+
+    Calls: the first evaluation is ``get_fluxes(reflected=rfacv != 0, thermal=True)`` (the visible nets stay fixed); the
+    Jacobian and the trials are ``get_nets_tbatch``; one thermal ``get_fluxes`` at the accepted profile gives the returned
+    IR fluxes.  With ``do_holes`` each of them covers both plane sets.
+
+    The caller's ``Atmosphere.t_level`` is NOT modified.  The reference writes its trial temperatures into that array
+    and its callers use the returned one; use the returned ``temp`` here too.  ``moist=True`` (the moist adiabat) is not
+    implemented.  ``nstr[0]`` must be 0, as every caller of the reference passes it.
+
+    ``_fluxes=(single, batched)`` (tests): host callables in place of the two device calls, ``single`` with
+    ``get_fluxes``' arguments and ``batched`` with ``get_nets_tbatch``'s (``None``: ``single`` per profile)."""
+    if moist:
+        raise NotImplementedError("t_start: the moist adiabat (moist=True) is not implemented")
+    nstr = [int(x) for x in nstr]
+    nofczns = int(nofczns)
+    if nstr[0] != 0:
+        raise ValueError("t_start: nstr[0] must be 0 (the top level)")
+    pressure = f64(Atmosphere.p_level)
+    temp = np.array(Atmosphere.t_level, dtype=np.float64)         # a copy: the working profile
+    nlevel = len(temp)
+    if nlevel > MAX_LEVELS:
+        raise ValueError("t_start: at most %d levels" % MAX_LEVELS)
+    tmin, tmax = Opagrid.tmin, Opagrid.tmax
+    it_max = int(convergence_criteria.it_max)                     # the only field of the tuple this function reads
+    tidal = f64(tidal)
+    holes = {}
+    if do_holes:
+        holes = dict(do_holes=True, fhole=fhole, hole_OpacityWEd=hole_OpacityWEd, hole_OpacityNoEd=hole_OpacityNoEd)
+    common = (OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Opagrid)
+    if _fluxes is None:
+        ctx = ctx if ctx is not None else _lib.context()
+
+        def single(*a, **k):
+            return get_fluxes(*a, ctx=ctx, **k)
+
+        def batched(*a, **k):
+            return get_nets_tbatch(*a, ctx=ctx, **k)
+    else:
+        single, batched = _fluxes
+        if batched is None:
+            def batched(temps, atm, *a, **k):
+                rows = [single(atm._replace(t_level=t.copy()), *a, F0PI, False, True, **k) for t in temps]
+                return np.array([r[4] for r in rows]), np.array([r[5] for r in rows])
+
+    def nets(profiles):
+        nl, n = batched(np.ascontiguousarray(profiles), Atmosphere, *common, **holes)
+        return np.asarray(nl), np.asarray(n)
+
+    # zones: the unknown levels n_top..n_strt, the adiabat levels n_strt+1..n_bot, and what a level index loses to
+    # become an index of the solver's vectors
+    zones, unknown, shift = [], [], 0
+    for z in range(nofczns):
+        n_top = nstr[3 * z] + (1 if z else 0)
+        n_strt, n_bot = nstr[3 * z + 1], nstr[3 * z + 2] + 1
+        zones.append((n_top, n_strt, n_bot, shift))
+        unknown += list(range(n_top, n_strt + 1))
+        shift = -1 + sum(zb - zs for _, zs, zb, _ in zones)
+    unknown = np.array(unknown, dtype=np.intp)
+    n_total = len(unknown)
+    index = np.concatenate([np.arange(zt, zs + 1) - sh for zt, zs, _, sh in zones])     # 0..n_total-1 in a valid nstr
+    if not np.array_equal(index, np.arange(n_total)) or (n_total and unknown.max() >= nlevel):
+        raise ValueError("t_start: nstr does not describe contiguous zones: %r" % (nstr,))
+    first = np.zeros(n_total, dtype=bool)
+    first[0] = True
+    dlogp = np.log(pressure[1:]) - np.log(pressure[:-1])           # log p[j] - log p[j-1], at j-1
+    pmid = np.sqrt(pressure[:-1] * pressure[1:])
+
+    def residual(net_ir, net_ir_layer):
+        flux_net = rfaci * net_ir + rfacv * flux_net_v + tidal
+        flux_net_midpt = rfaci * net_ir_layer + rfacv * flux_net_v_layer + tidal
+        return np.where(first, flux_net[unknown], flux_net_midpt[unknown - 1]), flux_net
+
+    def half_sum_sq(v):
+        return 0.5 * np.cumsum(v ** 2)[-1]                         # a running sum, as the reference's loop
+
+    def adiabat(t, zone, t_for_grad):
+        """Continue the adiabat through one convective zone of `t`; the gradient is taken at `t_for_grad[j-1]`
+        (None: at the level just computed)."""
+        _, n_strt, n_bot, _ = zone
+        if t_for_grad is not None and n_bot > n_strt:
+            grads = did_grad_cp(t_for_grad[n_strt:n_bot], pmid[n_strt:n_bot], AdiabatBundle)[0]
+        for j1 in range(n_strt + 1, n_bot + 1):
+            gx = grads[j1 - 1 - n_strt] if t_for_grad is not None else did_grad_cp(t[j1 - 1], pmid[j1 - 1], AdiabatBundle)[0]
+            t[j1] = np.exp(np.log(t[j1 - 1]) + gx * dlogp[j1 - 1])
+
+    first_out = single(Atmosphere._replace(t_level=temp.copy()), *common, F0PI, rfacv != 0, True, **holes)
+    flux_net_v_layer, flux_net_v = first_out[0][0, 0, :], first_out[1][0, 0, :]
+    flux_net_ir_layer, flux_net_ir, flux_plus_ir = first_out[4], first_out[5], first_out[6]
+
+    def finish(layer_in_fourth):
+        out = single(Atmosphere._replace(t_level=temp.copy()), *common, F0PI, False, True, **holes)
+        return temp, _lapse(temp, pressure), all_profiles, out[4] if layer_in_fourth else out[5], flux_net_v, out[6][0, :]
+
+    eps, alf, tolmin, tolf, tolx = 1e-4, 1e-4, 1e-5, 5e-3, 5e-3
+    step_max, alam2 = 0.01, 0.0
+    dflux, g = np.zeros(nlevel), np.zeros(nlevel)
+    flag_converge = 0
+    for its in range(it_max):
+        f_vec, flux_net = residual(flux_net_ir, flux_net_ir_layer)
+        dflux[:n_total] = f_vec
+        beta, temp_old = temp.copy(), temp.copy()
+        flux_net_old, flux_net_midpt_old = flux_net_ir.copy(), flux_net_ir_layer.copy()
+        sum_1 = np.cumsum(temp[:n_total] ** 2)[-1]                 # the reference sums the first n_total levels
+        test = np.fmax.reduce(np.abs(f_vec), initial=0.0)
+        f = half_sum_sq(f_vec)
+        if test / abs(tidal[0]) < 0.01 * tolf:
+            if verbose:
+                print(" We are already at a root, tolf , test = ", 0.01 * tolf, ", ", test / abs(tidal[0]))
+            if its == 0:                                            # the first evaluation is of this very profile
+                return temp, _lapse(temp, pressure), all_profiles, flux_net_ir, flux_net_v, flux_plus_ir[0, :]
+            return finish(False)                                    # the trials gave nets only: the fluxes of THIS profile
+        if egp_stepmax:
+            step_max = 0.005 * max(np.sqrt(sum_1), n_total * 1.0)
+        else:
+            step_max *= max(np.sqrt(sum_1), n_total * 1.0) * max(0.01, (it_max - its) / it_max)
+
+        # ---- the Jacobian: one perturbed profile per unknown, all in one batch.  `temp` is the running profile the
+        # reference rebuilds in place, so a level no zone rewrites keeps what the previous profile left there
+        del_t = np.maximum(eps * temp_old[unknown], 3.0)
+        profiles = np.empty((n_total, nlevel))
+        for k, jm in enumerate(unknown):
+            beta[jm] += del_t[k]
+            for zone in zones:
+                temp[zone[0]:zone[1] + 1] = beta[zone[0]:zone[1] + 1]
+                adiabat(temp, zone, beta)
+            profiles[k] = temp
+            beta[jm] = beta[jm] - del_t[k]
+        net_layer_b, net_b = nets(profiles)
+        A = np.zeros((nlevel, nlevel))
+        rows = np.where(first[None, :], net_b[:, unknown] - flux_net_old[unknown],
+                        net_layer_b[:, unknown - 1] - flux_net_midpt_old[unknown - 1])      # (profile, residual)
+        A[:n_total, :n_total] = (rows / del_t[:, None]).T
+        flux_net_ir_layer, flux_net_ir = net_layer_b[-1], net_b[-1]
+
+        g[:] = 0.0
+        for j in range(n_total):                                   # g = A^T f, summed over j in order
+            g[:n_total] += A[j, :n_total] * f_vec[j]
+        p = np.zeros(nlevel)
+        p[:n_total] = -f_vec
+        f_old = f
+        A, p = mat_sol(A, nlevel, n_total, p)
+
+        norm = np.sqrt(np.cumsum(np.concatenate(([0.0], p[2:n_total] ** 2)))[-1])         # the first two are left out
+        if norm > step_max:
+            p[:n_total] *= step_max / norm
+            dflux[:n_total] = -p[:n_total]
+        slope = np.cumsum(g[:n_total] * p[:n_total])[-1]
+        test = np.fmax.reduce(np.abs(p[:n_total]) / temp_old[:n_total], initial=0.0)
+        alamin = tolx / test
+        alam, f2, check = 1.0, f, False
+        flag_converge = 0
+        while flag_converge == 0:
+            for zone in zones:
+                n_top, n_strt, _, sh = zone
+                temp[n_top:n_strt + 1] = beta[n_top:n_strt + 1] + alam * p[n_top - sh:n_strt + 1 - sh]
+                adiabat(temp, zone, None)
+            low, high = temp < tmin, temp > tmax                  # the damper
+            temp[low], temp[high] = tmin + 0.1, tmax - 0.1
+            net_layer_b, net_b = nets(temp[None, :])
+            flux_net_ir_layer, flux_net_ir = net_layer_b[0], net_b[0]
+            f_vec, flux_net = residual(flux_net_ir, flux_net_ir_layer)
+            f = half_sum_sq(f_vec)
+            if alam < alamin:
+                check = True
+                flag_converge, check = check_convergence(f_vec, n_total, tolf, check, f, dflux, tolmin, temp, temp_old, g, tolx)
+            elif f <= f_old + alf * alam * slope:
+                flag_converge, check = check_convergence(f_vec, n_total, tolf, check, f, dflux, tolmin, temp, temp_old, g, tolx)
+            else:                                                  # backtrack: quadratic first, then cubic
+                if alam == 1.0:
+                    tmplam = -slope / (2 * (f - f_old - slope))
+                else:
+                    rhs_1 = f - f_old - alam * slope
+                    rhs_2 = f2 - f_old - alam2 * slope
+                    anr = ((rhs_1 / alam ** 2) - (rhs_2 / alam2 ** 2)) / (alam - alam2)
+                    b = (-alam2 * rhs_1 / alam ** 2 + alam * rhs_2 / alam2 ** 2) / (alam - alam2)
+                    if anr == 0:
+                        tmplam = -slope / (2.0 * b)
+                    else:
+                        disc = b * b - 3.0 * anr * slope
+                        if disc < 0.0:
+                            tmplam = 0.5 * alam
+                        elif b <= 0.0:
+                            tmplam = (-b + np.sqrt(disc)) / (3.0 * anr)
+                        else:
+                            tmplam = -slope / (b + np.sqrt(disc))
+                    if tmplam > 0.5 * alam:
+                        tmplam = 0.5 * alam
+            if flag_converge not in (1, 2):
+                alam2, f2 = alam, f
+                alam = max(tmplam, 0.1 * alam)
+            if np.isnan(np.sum(temp)):
+                flag_converge = 1
+                temp = temp_old.copy() + 0.5
+                if verbose:
+                    print("Got stuck with temp NaN -- so escaping the while loop in tstart")
+        if verbose:
+            print("Iteration number ", its, ", min , max temp ", temp.min(), temp.max(), ", flux balance ",
+                  flux_net[0] / abs(tidal[0]))
+        if save_profile == 1:
+            all_profiles = np.append(all_profiles, temp_old)
+        if flag_converge == 2:
+            if verbose:
+                print("In t_start: Converged Solution in iterations ", its)
+            return finish(False)
+    if verbose:
+        print("Iterations exceeded it_max ! sorry ")
+    return finish(True)

@@ -386,4 +386,318 @@ int launch_thermal_lvl(picaso_ctx *ctx, const ThermalLvlArgs &a)
     return 0;
 }
 
+
+// ------------------------------------------------------------------------------------------------
+// thermal NET fluxes of many temperature profiles (climate.t_start's Jacobian and line search)
+// ------------------------------------------------------------------------------------------------
+// What the T(P) iteration reads of a thermal get_fluxes call is 2 nlevel numbers per profile:
+//   net[l] = sum_w dwno[w] sum_g gauss_wts[g] sum_k wgt_k (F+_k - F-_k)[l][w][g]     (levels, and the same at mid-points)
+// k_thermal_lvl_angle writes the four (angle, level, column) planes for other kernels to sum.  Here one lane keeps a
+// column ([profile,] wavelength, Gauss point), walks the layers with the recursion state of ALL angles in registers
+// (therm_layer_coeffs once per layer instead of once per angle and direction) and never stores a per-angle value:
+//   pass 1, downward: leaves the disk-weighted sum_k wgt_k F-_k per level and per mid-point in two planes;
+//   pass 2, upward: forms (sum_k wgt_k F+_k - that) gauss_wts dwno per level and adds it over the wave.
+// One partial per (profile, level, wave) goes to a small buffer which k_thermal_nets_finish adds in wave order: no
+// atomics, the same bits on every run, and -- blockIdx.y being the profile, so that a wave never holds two profiles --
+// the same bits however many profiles share the launch.  Every flux value is formed by k_thermal_lvl_angle's
+// expressions in its order; the sums over angle, Gauss point and wavenumber are associated differently from the
+// plane-by-plane path (~1e-16 of sum |terms|).
+constexpr int NETS_MAX_ANGLES = 10;      // per-lane recursion state: one double per angle (the climate solver uses 10)
+
+struct ThermalNetsArgs {
+    ThermalLvlArgs lvl;             // as k_thermal_lvl_solve was launched
+    int na;                         // the disk angles: ubar1, gweight[g], tweight[t] in (g, t) order
+    double u1[NETS_MAX_ANGLES], wgt[NETS_MAX_ANGLES], wgt2[NETS_MAX_ANGLES];
+    const double *gauss_wts;        // device (ngauss)
+    double *dsum;                   // 2 planes (nlevel, ncol): sum_k wgt_k F-_k at the levels, at the mid-points
+    double *partial;                // (nitem, nlevel, 2, nwave)
+    int nwave;
+};
+
+__device__ __forceinline__ double disk_add(double acc, double x, double wg, double wt)
+{
+#pragma clang fp contract(off)      // k_compress: acc = acc + x * gweight * tweight
+    return acc + x * wg * wt;
+}
+
+// The value, as one the compiler cannot share between the angles of a lane.  k_thermal_lvl_angle sees ONE angle: there
+// `0.5 * dt` has a single use and is contracted into the sum that follows it.  With all angles in one block the same
+// product would have one use per angle and be kept as a product, which rounds the mid-point fluxes differently.
+// This (and the branch-free upward loop below) leans on how the compiler contracts products into sums, per basic block
+// and per use count; the assembly was read for 1..10 angles with the compiler this was written for.  What GUARDS it is
+// tests/test_tstart_gpu.py: test_nets_match_the_sums_of_the_level_planes and test_nets_match_for_every_compiled_angle_count
+// hold every net within (N + 8) ulp of the sums of k_thermal_lvl_angle's planes on scenes whose thin top layers turn one
+// differently rounded product into thousands of ulp.  If a compiler update makes them fail, state the rounding here with
+// explicit fma() calls under `#pragma clang fp contract(off)`, following k_thermal_lvl_angle's assembly.
+__device__ __forceinline__ double own_copy(double x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma clang fp contract(off)
+    for (int s = 32; s > 0; s >>= 1) v = v + __shfl_xor(v, s, 64);      // a fixed butterfly: every lane ends with the sum
+    return v;
+}
+
+template <int NA>
+__global__ __launch_bounds__(64) void k_thermal_lvl_nets(const ThermalNetsArgs T)
+{
+    const ThermalLvlArgs &A = T.lvl;
+    const ThermalArgs &a = A.base;
+    const long per = a.per_item;
+    const long c0 = blockIdx.x * 64L + threadIdx.x;
+    const bool valid = c0 < per;                    // lanes past the last column work on it again and add nothing
+    const long wp = valid ? c0 : per - 1;
+    const long item = blockIdx.y;
+    const long w = item * per + wp;                 // the column of the scratch planes
+    const long wv = wp / a.ncolper;
+    const int n = a.nlayer, nlevel = n + 1;
+    const long pitch = a.pitch, nw = a.ncol;
+    const double mu1 = 0.5;
+    const double rs = a.surf_reflect[wv];
+    Exp2Coef K;
+    K.load();
+    const double *s_rho = A.scratch + w, *s_del = s_rho + (long)n * nw, *s_B = s_del + 3 * (long)n * nw;
+    double *d_lvl = T.dsum + w, *d_mid = d_lvl + (long)nlevel * nw;
+    double weight;
+    {
+#pragma clang fp contract(off)
+        weight = valid ? T.gauss_wts[wp - wv * a.ncolper] * a.dwno[wv] : 0.0;
+    }
+    double F[NA];
+    // ---- downward (k_thermal_lvl_angle, blockIdx.z == 0) ----
+    {
+        const double B_top = s_B[0];
+        const double tau_top = a.dtau[wp] * a.plevel[0] / (a.plevel[1] - a.plevel[0]);   // fluxes.py:1797
+        double Bcur = B_top;
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const double mu = T.u1[k], imu = 1.0 / mu;
+            F[k] = (1 - fexpk(-tau_top * imu, K)) * B_top * 2 * PI;                     // :1875
+            acc = disk_add(acc, F[k], T.wgt[k], T.wgt2[k]);
+        }
+        if (valid) d_lvl[0] = acc;
+        for (int i = 0; i < n; ++i) {
+            const double B0 = Bcur;
+            Bcur = s_B[(long)(i + 1) * nw];
+            const long off = (long)i * pitch + wp;
+            const ThermLayer r = therm_layer_coeffs(a, off, B0, Bcur, K);
+            const double dt_layer = a.dtau[off];
+            const double P = s_rho[(long)i * nw], N = s_del[(long)i * nw];
+            const double J = r.gam * (r.lam + 1.0 / mu1) * P, Kc = (1.0 / mu1 - r.lam) * N;  // :1844-1845
+            const double si1 = 2 * PI * (r.B0 - r.b1 * (r.s - mu1)), si2 = 2 * PI * r.b1;     // :1848-1849
+            double acc_l = 0.0, acc_m = 0.0;
+#pragma unroll
+            for (int k = 0; k < NA; ++k) {
+                const double mu = T.u1[k], imu = 1.0 / mu, nlh = 0.5 * NEG_LOG2E * imu;
+                const double Fm = F[k];
+                const double dt = own_copy(dt_layer);
+                // exp(E) and exp(-E) squared per angle from the angle's own copies, as therm_layer_coeffs forms them: there
+                // each has ONE use in this sweep (EP - ea, ea - EM) and is contracted into that difference
+                const double EPm = own_copy(r.EPm), EMm = own_copy(r.EMm);
+                const double EP = EPm * EPm, EM = EMm * EMm;
+                const double eam = fexp2(dt * nlh, K), ea = eam * eam;        // exp(-dtau/(2 mu)), exp(-dtau/mu)
+                const double lp1 = r.lam * mu + 1.0, lm1 = r.lam * mu - 1.0, r2 = frcp(lp1 * lm1);
+                const double lup = r2 * lm1, lum = r2 * lp1;                  // 1/(lam mu + 1), 1/(lam mu - 1)
+                const double fmm = (Fm * eam + (J * lup) * (EPm - eam) - (Kc * lum) * (EMm - eam) +
+                                    si1 * (1. - eam) + si2 * (mu * eam + 0.5 * dt - mu));       // :1889-1893
+                F[k] = (Fm * ea + (J * lup) * (EP - ea) + (Kc * lum) * (ea - EM) + si1 * (1. - ea) +
+                        si2 * (mu * ea + dt - mu));                                              // :1883-1887
+                acc_m = disk_add(acc_m, fmm, T.wgt[k], T.wgt2[k]);
+                acc_l = disk_add(acc_l, F[k], T.wgt[k], T.wgt2[k]);
+            }
+            if (valid) {
+                d_mid[(long)i * nw] = acc_m;
+                d_lvl[(long)(i + 1) * nw] = acc_l;
+            }
+        }
+        if (valid) d_mid[(long)n * nw] = 0.0;
+    }
+    // ---- upward (blockIdx.z == 1), the nets formed on the way ----
+    // A lane of a real column reads back only what it stored itself.  A lane past the last column (`!valid`) stored
+    // nothing and reads the sums of column per - 1, which another lane of THIS wave stored: the last column is always in
+    // the one wave that has such lanes, and a wave's vector stores and later loads of the same address stay in order,
+    // so no fence is needed between the passes.  That order matters although the tail's weight is 0: a stale NaN in the
+    // scratch would make 0 * NaN.  Do not move the tail lanes to another wave or the downward pass to another kernel
+    // without giving them a column of their own.
+    double *part = T.partial + (item * nlevel * 2) * T.nwave + blockIdx.x;
+    auto emit = [&](int lev, double up_mid, double up_lvl) {
+        double net_m, net_l;
+        {
+#pragma clang fp contract(off)
+            // no branch on `valid` here: a lane past the last column re-reads that column's sums and has weight 0.  A
+            // conditional load would cut the loop body into several basic blocks, and the compiler contracts products
+            // into sums per block: the flux expressions above would round differently from k_thermal_lvl_angle's
+            net_m = (up_mid - d_mid[(long)lev * nw]) * weight;
+            net_l = (up_lvl - d_lvl[(long)lev * nw]) * weight;
+        }
+        net_m = wave_sum(net_m);
+        net_l = wave_sum(net_l);
+        if (threadIdx.x == 0) {
+            part[(long)(lev * 2) * T.nwave] = net_m;
+            part[(long)(lev * 2 + 1) * T.nwave] = net_l;
+        }
+    };
+    const double Bb = s_B[(long)n * nw];
+    // b1 of the bottom layer, formed as therm_layer_coeffs forms it
+    const double b1_last = (Bb - s_B[(long)(n - 1) * nw]) * frcp(a.dtau[(long)(n - 1) * pitch + wp]);
+    {
+        double acc = 0.0;
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const double mu = T.u1[k];
+            F[k] = a.hard_surface ? (1.0 - rs) * Bb * 2 * PI : (Bb + b1_last * mu) * 2 * PI;  // :1871-1873
+            acc = disk_add(acc, F[k], T.wgt[k], T.wgt2[k]);
+        }
+        emit(n, 0.0, acc);
+    }
+    double Bnext = Bb;
+    for (int i = n - 1; i >= 0; --i) {
+        const double B0 = s_B[(long)i * nw];
+        const long off = (long)i * pitch + wp;
+        const ThermLayer r = therm_layer_coeffs(a, off, B0, Bnext, K);
+        Bnext = B0;
+        const double dt_layer = a.dtau[off];
+        const double P = s_rho[(long)i * nw], N = s_del[(long)i * nw];
+        const double G = (1.0 / mu1 - r.lam) * P, H = r.gam * (r.lam + 1.0 / mu1) * N;    // :1842-1843
+        const double al1 = 2 * PI * (r.B0 + r.b1 * (r.s - mu1)), al2 = 2 * PI * r.b1;     // :1846-1847
+        const double EPm = r.EPm, EMm = r.EMm;
+        double acc_l = 0.0, acc_m = 0.0;
+#pragma unroll
+        for (int k = 0; k < NA; ++k) {
+            const double mu = T.u1[k], imu = 1.0 / mu, nlh = 0.5 * NEG_LOG2E * imu;
+            const double Fp = F[k];
+            const double dt = own_copy(dt_layer);
+            const double eam = fexp2(dt * nlh, K), ea = eam * eam;
+            const double lp1 = r.lam * mu + 1.0, lm1 = r.lam * mu - 1.0, r2 = frcp(lp1 * lm1);
+            const double lup = r2 * lm1, lum = r2 * lp1;
+            const double fpm = (Fp * eam + (G * lum) * (r.EP * eam - EPm) - (H * lup) * (r.EM * eam - EMm) +
+                                al1 * (1. - eam) + al2 * (mu + 0.5 * dt - (dt + mu) * eam)); // :1903-1907
+            F[k] = (Fp * ea + (G * lum) * (r.EP * ea - 1.0) + (H * lup) * (1.0 - r.EM * ea) + al1 * (1. - ea) +
+                    al2 * (mu - (dt + mu) * ea));                                              // :1897-1901
+            acc_m = disk_add(acc_m, fpm, T.wgt[k], T.wgt2[k]);
+            acc_l = disk_add(acc_l, F[k], T.wgt[k], T.wgt2[k]);
+        }
+        emit(i, acc_m, acc_l);
+    }
+}
+
+// net_layer[item][lev] = sym * sum over the waves of partial[item][lev][0][.], net[item][lev] likewise of [1]: in wave order
+__global__ __launch_bounds__(256) void k_thermal_nets_finish(long nrow, int nwave, double sym, const double *__restrict__ partial,
+                                                             double *__restrict__ net_layer, double *__restrict__ net)
+{
+#pragma clang fp contract(off)
+    const long t = blockIdx.x * 256L + threadIdx.x;      // (item, level, kind)
+    if (t >= 2 * nrow) return;
+    const double *src = partial + t * nwave;
+    double acc = 0.0;
+    for (int j = 0; j < nwave; ++j) acc = acc + src[j];
+    ((t & 1) ? net : net_layer)[t >> 1] = acc * sym;
+}
+
+template <int NA>
+static void launch_nets_na(picaso_ctx *ctx, const ThermalNetsArgs &t, dim3 grid)
+{
+    hipLaunchKernelGGL(k_thermal_lvl_nets<NA>, grid, dim3(64), 0, ctx->stream, t);
+}
+
+// one chunk of profiles: solve (unchanged), the fused sweeps, the sum of the partials
+static int launch_thermal_nets(picaso_ctx *ctx, const ThermalNetsArgs &t, int nitem, double sym, double *net_layer,
+                               double *net)
+{
+    const ThermalArgs &a = t.lvl.base;
+    const int block = a.ncol <= 64L * 256 ? 64 : 256;          // as launch_thermal_lvl
+    hipLaunchKernelGGL(k_thermal_lvl_solve, dim3((unsigned)((a.ncol + block - 1) / block)), dim3(block), 0, ctx->stream,
+                       t.lvl);
+    PZ_HIP(ctx, hipGetLastError());
+    const dim3 grid((unsigned)t.nwave, (unsigned)nitem);
+    switch (t.na) {
+#define PZ_NETS_CASE(NA) case NA: launch_nets_na<NA>(ctx, t, grid); break;
+    PZ_NETS_CASE(1) PZ_NETS_CASE(2) PZ_NETS_CASE(3) PZ_NETS_CASE(4) PZ_NETS_CASE(5) PZ_NETS_CASE(6)
+    PZ_NETS_CASE(7) PZ_NETS_CASE(8) PZ_NETS_CASE(9) PZ_NETS_CASE(10)
+#undef PZ_NETS_CASE
+    default: return fail(ctx, "thermal_nets_tbatch: %d angles, at most %d", t.na, NETS_MAX_ANGLES);
+    }
+    PZ_HIP(ctx, hipGetLastError());
+    const long nrow = (long)nitem * (a.nlayer + 1);
+    hipLaunchKernelGGL(k_thermal_nets_finish, dim3((unsigned)((2 * nrow + 255) / 256)), dim3(256), 0, ctx->stream, nrow,
+                       t.nwave, sym, t.partial, net_layer, net);
+    PZ_HIP(ctx, hipGetLastError());
+    return 0;
+}
+
 }  // namespace pz
+
+extern "C" int picaso_thermal_nets_max_angles(void) { return pz::NETS_MAX_ANGLES; }
+
+extern "C" int picaso_thermal_nets_tbatch_dev(picaso_ctx *ctx, int nitem, int nlevel, const double *wno, int nwno, int ngauss,
+                                              int numg, int numt, const double *tlevel, const double *dtau, const double *w0,
+                                              const double *cosb, const double *plevel, const double *ubar1,
+                                              const double *surf_reflect, int hard_surface, const double *dwno,
+                                              const double *gauss_wts, const double *gweight, const double *tweight,
+                                              double *net_layer, double *net)
+{
+    using namespace pz;
+    if (!ctx) return fail(nullptr, "null context");
+    if (nitem < 1 || nlevel < 2 || nwno < 1 || numg < 1 || numt < 1) return fail(ctx, "thermal_nets_tbatch: bad sizes");
+    if (ngauss < 1 || ngauss > MAX_CK_GAUSS) return fail(ctx, "thermal_nets_tbatch: ngauss must be 1..%d", MAX_CK_GAUSS);
+    const int nang = numg * numt, nlayer = nlevel - 1;
+    if (nang > NETS_MAX_ANGLES) return fail(ctx, "thermal_nets_tbatch: %d angles, at most %d", nang, NETS_MAX_ANGLES);
+    if (!wno || !tlevel || !dtau || !w0 || !cosb || !plevel || !ubar1 || !surf_reflect || !dwno || !gauss_wts || !gweight ||
+        !tweight || !net_layer || !net)
+        return fail(ctx, "thermal_nets_tbatch: null argument");
+    PZ_HIP(ctx, hipSetDevice(ctx->device));
+    const long per = (long)nwno * ngauss;
+    const int nwave = (int)((per + 63) / 64);
+    // per profile: the solve's 4 nlayer + nlevel planes and the 2 nlevel planes of the downward sums (level scratch),
+    // 2 nlevel nwave partials (correlated-k scratch).  Profiles are independent, so a batch past the budget is cut up.
+    const size_t lvl_item = sizeof(double) * ((size_t)4 * nlayer + 3 * (size_t)nlevel) * per;
+    const size_t budget = (size_t)1 << 30;
+    int chunk = (int)(budget / lvl_item);
+    if (chunk < 1) chunk = 1;
+    if (chunk > nitem) chunk = nitem;
+    if (chunk > 65535) chunk = 65535;                         // grid.y
+    const size_t slot = picaso_ctx::SLOT_BYTES / sizeof(double) - (size_t)nlevel - (size_t)ngauss;   // the table of a chunk
+    if ((size_t)chunk > slot / nlevel) chunk = (int)(slot / nlevel);
+    PZ_TRY(lvl_scratch_reserve(ctx, lvl_item * chunk));
+    PZ_TRY(ck_scratch_reserve(ctx, sizeof(double) * (size_t)chunk * nlevel * 2 * nwave));
+    const double sym = (numt == 1) ? 1.0 : 1.0 / (2.0 * 3.14159265358979323846);     // compress_thermal, disco.py:174-175
+    std::vector<double> tab;
+    for (int done = 0; done < nitem; done += chunk) {
+        const int m = nitem - done < chunk ? nitem - done : chunk;
+        tab.assign((size_t)m * nlevel + (size_t)nlevel + (size_t)ngauss, 0.0);
+        memcpy(tab.data(), tlevel + (size_t)done * nlevel, sizeof(double) * (size_t)m * nlevel);
+        memcpy(tab.data() + (size_t)m * nlevel, plevel, sizeof(double) * nlevel);
+        memcpy(tab.data() + (size_t)m * nlevel + nlevel, gauss_wts, sizeof(double) * ngauss);
+        const void *d_tab = nullptr;
+        PZ_TRY(table_upload(ctx, tab.data(), sizeof(double) * tab.size(), &d_tab));
+        ThermalNetsArgs t{};
+        ThermalArgs &a = t.lvl.base;
+        a.nlayer = nlayer;
+        a.ncol = per * m;
+        a.ncolper = ngauss;
+        a.pitch = per;                                        // the planes hold ONE profile's columns
+        a.per_item = per;
+        a.nfac = 1;
+        a.nwno = nwno;
+        a.wno = wno; a.dwno = dwno;
+        a.tlevel = (const double *)d_tab;
+        a.plevel = a.tlevel + (size_t)m * nlevel;
+        a.dtau = dtau; a.w0 = w0; a.cosb = cosb; a.surf_reflect = surf_reflect;
+        a.hard_surface = hard_surface; a.calc_type = 1;       // bin-integrated Planck functions, as climate.get_fluxes
+        t.na = nang;
+        for (int k = 0; k < nang; ++k) { t.u1[k] = ubar1[k]; t.wgt[k] = gweight[k / numt]; t.wgt2[k] = tweight[k % numt]; }
+        t.lvl.nang = nang;
+        t.lvl.scratch = ctx->lvl_scratch;
+        t.gauss_wts = a.plevel + nlevel;
+        t.dsum = ctx->lvl_scratch + ((size_t)4 * nlayer + nlevel) * a.ncol;
+        t.partial = ctx->ck_scratch;
+        t.nwave = nwave;
+        PZ_TRY(launch_thermal_nets(ctx, t, m, sym, net_layer + (size_t)done * nlevel, net + (size_t)done * nlevel));
+    }
+    return 0;
+}

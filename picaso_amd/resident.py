@@ -227,6 +227,26 @@ def thermal_1d_ck_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dt
         ptr(f64(tweight)), _addr(disk4)), ctx)
 
 
+def thermal_nets_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dtau, w0, cosb, plevel, ubar1, surf_reflect,
+                        hard_surface, gauss_wts, gweight, tweight, dwno, net_layer, net):
+    """The thermal net fluxes of every row of ``tlevels`` ``(nitem, nlevel)`` over ONE set of planes
+    (``picaso_thermal_nets_tbatch_dev``): ``net_layer`` and ``net`` are DeviceArrays ``(nitem, nlevel)``, summed over disk
+    angle, Gauss point and wavenumber on the device without the per-angle level planes.  At most
+    ``thermal_nets_max_angles()`` disk angles."""
+    tl = f64(tlevels)
+    nitem = tl.shape[0]
+    tl = f64(tl, (nitem, nlevel))
+    check(load().picaso_thermal_nets_tbatch_dev(
+        ctx, nitem, nlevel, _addr(wno), nwno, ngauss, numg, numt, ptr(tl), _addr(dtau), _addr(w0), _addr(cosb),
+        ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), _addr(surf_reflect), int(hard_surface), _addr(dwno),
+        ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight, (numg,))), ptr(f64(tweight, (numt,))), _addr(net_layer),
+        _addr(net)), ctx)
+
+
+def thermal_nets_max_angles():
+    return int(load().picaso_thermal_nets_max_angles())
+
+
 def transit_1d_ck(ctx, z, dz, nlevel, nwno, ngauss, rstar, mmw, k_b, amu, player, tlayer, colden, dtau,
                   gauss_wts, rprs2):
     """The transmission branch's correlated-k loop (reference justdoit.py:388-405) on a resident
