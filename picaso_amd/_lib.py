@@ -25,12 +25,53 @@ class PicasoHipError(Exception):
     pass
 
 
-def declared_symbols():
-    """Every function name include/picaso_hip.h declares."""
+# C type -> ctypes class, for parameters passed by value and for return values.  Anything with a ``*`` is a
+# ``c_void_p`` (which takes None, an integer address, a ctypes pointer, ``byref(...)`` or a ctypes array).
+_BY_VALUE = {"int": ctypes.c_int, "long": ctypes.c_long, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t,
+             "double": ctypes.c_double}
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "void *": ctypes.c_void_p, "const char *": ctypes.c_char_p,
+            "void": None}
+
+
+def _param_type(decl, func):
+    """ctypes class of one parameter declaration (``const double *const *dtau``, ``long plane_pitch``, ...)."""
+    if "*" in decl:
+        return ctypes.c_void_p
+    words = decl.split()
+    ctype = " ".join(words[:-1])                     # every parameter of the header is named: the last word is the name
+    if ctype not in _BY_VALUE:
+        raise PicasoHipError("picaso_amd: %s declares %s with a parameter %r of a type this binding does not know"
+                             % (os.path.basename(HEADER), func, decl))
+    return _BY_VALUE[ctype]
+
+
+def declared_prototypes():
+    """``{name: (restype, [argtypes])}`` for every function include/picaso_hip.h declares."""
     with open(HEADER) as fh:
         text = fh.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(picaso_[A-Za-z0-9_]+)\s*\(", text)))
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                        # comments
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)                         # preprocessor lines
+    text = re.sub(r"extern\s+\"C\"\s*\{", "", text)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)      # struct bodies
+    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", "", text)             # opaque handles
+    protos = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        m = re.fullmatch(r"(.+?)\b(picaso_\w+) ?\((.*)\)", stmt)
+        if not m:
+            continue
+        ret, name, params = m.group(1).replace(" *", "*").replace("*", " *").strip(), m.group(2), m.group(3).strip()
+        if ret not in _RETURNS:
+            raise PicasoHipError("picaso_amd: %s declares %s with a return type %r this binding does not know"
+                                 % (os.path.basename(HEADER), name, ret))
+        args = [] if params in ("", "void") else [_param_type(p.strip(), name) for p in params.split(",")]
+        protos[name] = (_RETURNS[ret], args)
+    return protos
+
+
+def declared_symbols():
+    """Every function name include/picaso_hip.h declares."""
+    return sorted(declared_prototypes())
 
 
 def _share_hip_runtime_with_torch():
@@ -50,7 +91,8 @@ def _share_hip_runtime_with_torch():
 
 
 def load():
-    """Load the shared library (no GPU needed for this step)."""
+    """Load the shared library and declare every signature of the header on it (no GPU needed for this step): calls
+    take plain Python values, and a call that disagrees with the header raises before C is entered."""
     global _lib
     if _lib is not None:
         return _lib
@@ -60,19 +102,14 @@ def load():
             "g.build()'` (hipcc, gfx950).  There is no CPU fallback." % LIB_PATH)
     _share_hip_runtime_with_torch()
     lib = ctypes.CDLL(LIB_PATH)
-    lib.picaso_last_error.restype = ctypes.c_char_p
-    lib.picaso_last_error.argtypes = [ctypes.c_void_p]
-    lib.picaso_version.restype = ctypes.c_char_p
-    lib.picaso_stream.restype = ctypes.c_void_p
-    lib.picaso_stream.argtypes = [ctypes.c_void_p]
-    i, p, v = ctypes.c_int, c_double_p, ctypes.c_void_p
-    if not hasattr(lib, "picaso_thermal_nets_tbatch_dev"):
-        raise PicasoHipError("picaso_amd: %s was built from older sources (no picaso_thermal_nets_tbatch_dev): rebuild it "
-                             "from this tree" % LIB_PATH)
-    lib.picaso_thermal_nets_tbatch_dev.restype = ctypes.c_int
-    lib.picaso_thermal_nets_tbatch_dev.argtypes = [v, i, i, v, i, i, i, i, p, v, v, v, p, p, v, i, v, p, p, p, v, v]
-    lib.picaso_thermal_nets_max_angles.restype = ctypes.c_int
-    lib.picaso_thermal_nets_max_angles.argtypes = []
+    protos = declared_prototypes()
+    missing = sorted(name for name in protos if not hasattr(lib, name))
+    if missing:
+        raise PicasoHipError("picaso_amd: %s was built from older sources (no %s): rebuild it from this tree"
+                             % (LIB_PATH, ", ".join(missing)))
+    for name, (restype, argtypes) in protos.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -126,7 +163,7 @@ def context(device=None):
         _mark_gpu_used()
         lib = load()
         h = ctypes.c_void_p()
-        rc = lib.picaso_ctx_create(ctypes.c_int(device), ctypes.byref(h))
+        rc = lib.picaso_ctx_create(device, ctypes.byref(h))
         if rc != 0:
             raise PicasoHipError("picaso_amd needs an MI355X (gfx950) GPU: %s"
                                  % lib.picaso_last_error(None).decode())
@@ -160,7 +197,7 @@ def new_context(device=None):
         device = int(os.environ.get("PICASO_AMD_DEVICE", "0"))
     _mark_gpu_used()
     h = ctypes.c_void_p()
-    rc = load().picaso_ctx_create(ctypes.c_int(device), ctypes.byref(h))
+    rc = load().picaso_ctx_create(device, ctypes.byref(h))
     if rc != 0:
         raise PicasoHipError(load().picaso_last_error(None).decode())
     return h
@@ -222,12 +259,29 @@ def f64(x, shape=None):
     return a
 
 
+def addr(x):
+    """None, a DeviceArray (anything with ``.addr``), an integer address of any integer type or a numpy array -> the
+    address as a Python int (None stays None): what a pointer parameter takes."""
+    if x is None:
+        return None
+    if isinstance(x, np.ndarray):
+        return x.ctypes.data
+    return int(getattr(x, "addr", x))
+
+
+def ptr_array(items):
+    """Host table of the addresses of ``items`` (None: NULL) for the ``*const *`` parameters; the table is its own
+    storage, so it lives as long as the caller holds the return value."""
+    return (ctypes.c_void_p * max(1, len(items)))(*[addr(x) for x in items])
+
+
 def ptr(a):
+    """``addr`` as a ``POINTER(c_double)``: for the pointer members of the struct mirrors, and for pointer parameters."""
     if a is None:
         return None
     if isinstance(a, np.ndarray):
         return a.ctypes.data_as(c_double_p)
-    return ctypes.cast(ctypes.c_void_p(int(a)), c_double_p)   # raw device address
+    return ctypes.cast(addr(a), c_double_p)
 
 
 def per_wave(x, nwno):

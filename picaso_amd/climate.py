@@ -238,7 +238,6 @@ def get_fluxes_tbatch(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, Scatter
     summed over wavenumber ON THE DEVICE (``picaso_flux_net_sums_dev``: a fixed tree per row instead of numpy's order, so
     they agree with ``get_fluxes`` to ~1e-15 relative instead of bit for bit) -- 2 x nlevel doubles per profile cross
     PCIe instead of 4 x nlevel x nwno."""
-    import ctypes
     ctx = ctx if ctx is not None else _lib.context()
     temps = f64(temperatures)
     nlevel = int(Atmosphere.nlevel)
@@ -265,9 +264,8 @@ def get_fluxes_tbatch(temperatures, Atmosphere, OpacityWEd, OpacityNoEd, Scatter
                                       Disco.tweight, disk4, dwno=d_dw, calc_type=1)
         if nets_only:
             d_nl, d_n = DeviceArray((m, nlevel), ctx), DeviceArray((m, nlevel), ctx)
-            _lib.check(_lib.load().picaso_flux_net_sums_dev(ctx, ctypes.c_int(nlevel), ctypes.c_int(m), ctypes.c_int(nwno),
-                                                            ctypes.c_void_p(disk4.addr), ctypes.c_void_p(d_dw.addr),
-                                                            ctypes.c_void_p(d_nl.addr), ctypes.c_void_p(d_n.addr)), ctx)
+            _lib.check(_lib.load().picaso_flux_net_sums_dev(ctx, nlevel, m, nwno, disk4.addr, d_dw.addr, d_nl.addr, d_n.addr),
+                       ctx)
             net_layer[c0:c0 + m], net[c0:c0 + m] = d_nl.to_host(), d_n.to_host()
             continue
         fm, fp, fmm, fpm = disk4.to_host().reshape(4, nlevel, m, nwno)

@@ -7,7 +7,6 @@ from an ``inputs`` object the planes are formed on the device and stay there, fr
 reference's calling form) they are uploaded; the same kernels (csrc/contribfn.hip) serve both and only ``CF`` -- binned
 when ``R`` is given -- comes back.
 """
-import ctypes
 
 import numpy as np
 
@@ -15,7 +14,6 @@ from . import _lib, optics, regrid, resident
 from .atmsetup import _Consts
 from .device import DeviceArray
 
-_ci, _cd, _cl = ctypes.c_int, ctypes.c_double, ctypes.c_long
 NEEDS_RADIUS = "transmission needs the stellar radius (star()) and the planet radius and mass (gravity())"
 
 
@@ -37,7 +35,7 @@ def _binned(ctx, cf, wno, R, grid_of):
         return wavenumber, np.zeros((0, plan.nbins))
     out = DeviceArray((nrows, plan.nbins), ctx)
     _lib.check(_lib.load().picaso_mean_regrid_plane_dev(
-        ctx, _ci(nrows), _cl(nwno), _cl(nwno), _ci(plan.nbins), ctypes.c_void_p(plan.device_start(ctx).addr),
+        ctx, nrows, nwno, nwno, plan.nbins, plan.device_start(ctx).addr,
         _lib.ptr(cf.addr), _lib.ptr(out.addr)), ctx)
     return wavenumber, out.to_host()
 
@@ -124,9 +122,9 @@ def thermal_contribution(x, opacityclass=None, tau_max=1.0, R=100, dimension="1d
         dlnp = _lib.f64(np.diff(np.log(p_bar)))
         d_wno = optics._wno_device(grid_of, wno) if grid_of is not wno else DeviceArray.from_host(wno, ctx)
         _lib.check(_lib.load().picaso_thermal_cf_dev(
-            ctx, _ci(nlayer), _ci(nwno), _cl(nwno), _lib.ptr(taugas.addr),
+            ctx, nlayer, nwno, nwno, _lib.ptr(taugas.addr),
             _lib.ptr(taucld.addr) if taucld is not None else None, _lib.ptr(tauray.addr), _lib.ptr(tlayer),
-            _lib.ptr(d_wno.addr), _lib.ptr(dlnp), _cd(float(tau_max)), _lib.ptr(cf.addr)), ctx)
+            _lib.ptr(d_wno.addr), _lib.ptr(dlnp), float(tau_max), _lib.ptr(cf.addr)), ctx)
         wavenumber, out = _binned(ctx, cf, wno, R, grid_of)
     else:
         wavenumber = wno if R is None else cf_grid(grid_of, R)[0]
@@ -174,8 +172,8 @@ def transmission_contribution(x, opacityclass=None, R=None, as_reference=False, 
         resident.axpby(ctx, 1.0, taugas, 1.0, tauray, dtau)
     cf = DeviceArray((nlayer, nwno), ctx)
     _lib.check(_lib.load().picaso_transit_cf_dev(
-        ctx, _lib.ptr(_lib.f64(z, (nlevel,))), _lib.ptr(_lib.f64(level["dz"], (nlevel,))), _ci(nlevel), _ci(nwno), _cl(nwno),
-        _cd(1.0), _lib.ptr(_lib.f64(layer["mmw"], (nlayer,))), _cd(k_b), _cd(amu), _lib.ptr(_lib.f64(player)),
+        ctx, _lib.ptr(_lib.f64(z, (nlevel,))), _lib.ptr(_lib.f64(level["dz"], (nlevel,))), nlevel, nwno, nwno,
+        1.0, _lib.ptr(_lib.f64(layer["mmw"], (nlayer,))), k_b, amu, _lib.ptr(_lib.f64(player)),
         _lib.ptr(_lib.f64(tlayer)), _lib.ptr(_lib.f64(layer["column_density"], (nlayer,))), _lib.ptr(dtau.addr),
         _lib.ptr(cf.addr)), ctx)
     wavenumber, out = _binned(ctx, cf, wno, R, grid_of)

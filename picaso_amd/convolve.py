@@ -15,7 +15,6 @@ sums run over exactly the reference's non-zero terms.  The argument of ``exp`` h
 convolved array differs from ``conv_non_uniform_R`` of the plain call's array by the rounding of ``exp`` and the order of two
 sums of ``counts[i]`` non-negative weights: at most ``(2 counts[i] + 10) 2^-53`` of ``conv(|array|)``.
 """
-import ctypes
 import weakref
 
 import numpy as np
@@ -125,9 +124,8 @@ class ConvolvePlan(_regrid.Reduction):
     def launch(self, ctx, nrows, crows, out_addr):
         tables = d_wl, d_c, d_den, d_win = self.device_tables(ctx)
         _lib.check(_lib.load().picaso_lsf_convolve_dev(
-            ctx, ctypes.c_long(self.nwno), ctypes.c_void_p(d_wl.addr), ctypes.c_int(self.nobs), ctypes.c_void_p(d_c.addr),
-            ctypes.c_void_p(d_den.addr), ctypes.c_void_p(d_win.addr), ctypes.c_void_p(d_win.addr + 4 * self.nobs),
-            ctypes.c_int(nrows), crows, ctypes.c_void_p(out_addr)), ctx)
+            ctx, self.nwno, d_wl.addr, self.nobs, d_c.addr, d_den.addr, d_win.addr, d_win.addr + 4 * self.nobs,
+            nrows, crows, out_addr), ctx)
         return tables
 
 

@@ -15,16 +15,14 @@ class DeviceArray:
         self.size = int(np.prod(self.shape))
         self.nbytes = self.size * 8
         p = ctypes.c_void_p()
-        _lib.check(_lib.load().picaso_dev_malloc(self.ctx, ctypes.c_size_t(self.nbytes),
-                                                 ctypes.byref(p)), self.ctx)
+        _lib.check(_lib.load().picaso_dev_malloc(self.ctx, self.nbytes, ctypes.byref(p)), self.ctx)
         self.addr = p.value
 
     @classmethod
     def from_host(cls, arr, ctx=None):
         a = _lib.f64(arr)
         d = cls(a.shape, ctx)
-        _lib.check(_lib.load().picaso_memcpy_h2d(d.ctx, ctypes.c_void_p(d.addr), _lib.ptr(a),
-                                                 ctypes.c_size_t(d.nbytes)), d.ctx)
+        _lib.check(_lib.load().picaso_memcpy_h2d(d.ctx, d.addr, _lib.ptr(a), d.nbytes), d.ctx)
         return d
 
     @classmethod
@@ -34,10 +32,8 @@ class DeviceArray:
         rows, nwno = int(np.prod(a.shape[:-1])), a.shape[-1]
         n = w_hi - w_lo
         d = cls(a.shape[:-1] + (n,), ctx)
-        src = ctypes.c_void_p(a.ctypes.data + 8 * w_lo)
-        _lib.check(_lib.load().picaso_memcpy_h2d_2d(
-            d.ctx, ctypes.c_void_p(d.addr), ctypes.c_size_t(8 * n), src, ctypes.c_size_t(8 * nwno),
-            ctypes.c_size_t(8 * n), ctypes.c_size_t(rows)), d.ctx)
+        src = _lib.addr(a) + 8 * int(w_lo)
+        _lib.check(_lib.load().picaso_memcpy_h2d_2d(d.ctx, d.addr, 8 * n, src, 8 * nwno, 8 * n, rows), d.ctx)
         return d
 
     def columns_to_host(self, w_lo, w_hi):
@@ -48,16 +44,14 @@ class DeviceArray:
         inner = int(np.prod(self.shape[2:])) if len(self.shape) > 2 else 1
         n = int(w_hi) - int(w_lo)
         out = np.empty((rows, n) + tuple(self.shape[2:]), dtype=np.float64)
-        src = ctypes.c_void_p(self.addr + 8 * int(w_lo) * inner)
+        src = self.addr + 8 * int(w_lo) * inner
         _lib.check(_lib.load().picaso_memcpy_d2h_2d(
-            self.ctx, _lib.ptr(out), ctypes.c_size_t(8 * n * inner), src, ctypes.c_size_t(8 * nwno * inner),
-            ctypes.c_size_t(8 * n * inner), ctypes.c_size_t(rows)), self.ctx)
+            self.ctx, _lib.ptr(out), 8 * n * inner, src, 8 * nwno * inner, 8 * n * inner, rows), self.ctx)
         return out
 
     def to_host(self):
         out = np.empty(self.shape, dtype=np.float64)
-        _lib.check(_lib.load().picaso_memcpy_d2h(self.ctx, _lib.ptr(out), ctypes.c_void_p(self.addr),
-                                                 ctypes.c_size_t(self.nbytes)), self.ctx)
+        _lib.check(_lib.load().picaso_memcpy_d2h(self.ctx, _lib.ptr(out), self.addr, self.nbytes), self.ctx)
         return out
 
     def to_host_async(self, pinned, ctx=None):
@@ -68,8 +62,7 @@ class DeviceArray:
             raise ValueError("pinned block of %d bytes for a result of %d" % (pinned.nbytes, self.nbytes))
         ctx = ctx if ctx is not None else self.ctx
         mark = ctypes.c_void_p()
-        _lib.check(_lib.load().picaso_memcpy_d2h_async(ctx, ctypes.c_void_p(pinned.addr), ctypes.c_void_p(self.addr),
-                                                       ctypes.c_size_t(self.nbytes), ctypes.byref(mark)), ctx)
+        _lib.check(_lib.load().picaso_memcpy_d2h_async(ctx, pinned.addr, self.addr, self.nbytes, ctypes.byref(mark)), ctx)
         pinned._mark, pinned._mark_ctx = mark, ctx
         return pinned
 
@@ -80,8 +73,7 @@ class DeviceArray:
         return d
 
     def zero(self):
-        _lib.check(_lib.load().picaso_memset(self.ctx, ctypes.c_void_p(self.addr), 0,
-                                             ctypes.c_size_t(self.nbytes)), self.ctx)
+        _lib.check(_lib.load().picaso_memset(self.ctx, self.addr, 0, self.nbytes), self.ctx)
 
     def row_block(self, index):
         """Non-owning view of ``self[index]`` (leading axis) -- e.g. one facet of a facet-major stack."""
@@ -143,7 +135,7 @@ class DeviceArray:
 
     def free(self):
         if self.addr and not hasattr(self, "_owner"):
-            _lib.load().picaso_dev_free(self.ctx, ctypes.c_void_p(self.addr))
+            _lib.load().picaso_dev_free(self.ctx, self.addr)
         self.addr = 0
 
     def __del__(self):
@@ -162,7 +154,7 @@ class PinnedArray:
         self.shape = tuple(int(s) for s in np.atleast_1d(shape))
         self.nbytes = int(np.prod(self.shape)) * 8
         p = ctypes.c_void_p()
-        _lib.check(_lib.load().picaso_host_alloc(self.ctx, ctypes.c_size_t(self.nbytes), ctypes.byref(p)), self.ctx)
+        _lib.check(_lib.load().picaso_host_alloc(self.ctx, self.nbytes, ctypes.byref(p)), self.ctx)
         self.addr = p.value
         self._mark = None
         buf = (ctypes.c_double * (self.nbytes // 8)).from_address(self.addr)
@@ -183,7 +175,7 @@ class PinnedArray:
                 except Exception:
                     pass
             self.array = None
-            _lib.load().picaso_host_free(self.ctx, ctypes.c_void_p(self.addr))
+            _lib.load().picaso_host_free(self.ctx, self.addr)
         self.addr = 0
 
     def __del__(self):
@@ -200,9 +192,7 @@ def broadcast_facets(src, nfacets, facet_scale=None, ctx=None):
     rows, nwno = src.shape
     out = DeviceArray((rows, nwno, int(nfacets)), ctx)
     sc = _lib.f64(facet_scale, (int(nfacets),)) if facet_scale is not None else None
-    _lib.check(_lib.load().picaso_broadcast_facets_dev(ctx, ctypes.c_size_t(rows), ctypes.c_int(nwno),
-                                                      ctypes.c_int(int(nfacets)), ctypes.c_void_p(src.addr),
-                                                      _lib.ptr(sc), ctypes.c_void_p(out.addr)), ctx)
+    _lib.check(_lib.load().picaso_broadcast_facets_dev(ctx, rows, nwno, int(nfacets), src.addr, _lib.ptr(sc), out.addr), ctx)
     return out
 
 
@@ -221,9 +211,7 @@ def regrid_rows(xp, fp, d_x, ctx, scale=None):
     nwno = int(d_x.shape[0])
     out = DeviceArray((nrows, nwno), ctx)
     sc = ctypes.byref(ctypes.c_double(float(scale))) if scale is not None else None
-    _lib.check(_lib.load().picaso_regrid_rows_dev(ctx, ctypes.c_int(nrows), ctypes.c_int(nin), ctypes.c_long(nwno),
-                                                  ctypes.c_void_p(d_xp.addr), ctypes.c_void_p(d_fp.addr),
-                                                  ctypes.c_void_p(d_x.addr), sc, ctypes.c_void_p(out.addr)), ctx)
+    _lib.check(_lib.load().picaso_regrid_rows_dev(ctx, nrows, nin, nwno, d_xp.addr, d_fp.addr, d_x.addr, sc, out.addr), ctx)
     out._inputs = (d_xp, d_fp)          # the launch is asynchronous: its inputs live as long as its output
     return out
 
@@ -242,10 +230,8 @@ def regrid_facets(xp, fp, d_x, ctx):
         d_fp = DeviceArray.from_host(fp, ctx)
     nwno = int(d_x.shape[0])
     out = DeviceArray((nlayer, nwno, nfac), ctx)
-    _lib.check(_lib.load().picaso_regrid_facets_dev(ctx, ctypes.c_int(nlayer), ctypes.c_int(nfac), ctypes.c_int(nin),
-                                                    ctypes.c_long(nwno), ctypes.c_void_p(d_xp.addr),
-                                                    ctypes.c_void_p(d_fp.addr), ctypes.c_void_p(d_x.addr),
-                                                    ctypes.c_void_p(out.addr)), ctx)
+    _lib.check(_lib.load().picaso_regrid_facets_dev(ctx, nlayer, nfac, nin, nwno, d_xp.addr, d_fp.addr, d_x.addr, out.addr),
+               ctx)
     out._inputs = (d_xp, d_fp)
     return out
 

@@ -3,7 +3,6 @@
 ``get_angles_1d`` / ``get_angles_3d`` / ``compute_disco`` are tiny host-side table builders (numpy);
 ``compress_disco`` / ``compress_thermal`` run on the GPU through the C ABI.
 """
-import ctypes
 
 import numpy as np
 
@@ -67,9 +66,8 @@ def compress_disco(nwno, cos_theta, xint_at_top, gweight, tweight, F0PI):
     x = f64(xint_at_top, (len(gw), len(tw), nwno))
     f0 = per_wave(F0PI, nwno)
     out = np.zeros(nwno)
-    check(load().picaso_compress_disco(ctx, ctypes.c_int(nwno), ctypes.c_double(cos_theta), ptr(x),
-                                       ptr(gw), ctypes.c_int(len(gw)), ptr(tw),
-                                       ctypes.c_int(len(tw)), ptr(f0), ptr(out)), ctx)
+    check(load().picaso_compress_disco(ctx, nwno, cos_theta, ptr(x), ptr(gw), len(gw), ptr(tw), len(tw), ptr(f0), ptr(out)),
+          ctx)
     return out
 
 
@@ -82,7 +80,5 @@ def compress_thermal(nwno, flux_at_top, gweight, tweight):
     x = f64(flux_at_top)
     inner = x.shape[2:]
     out = np.zeros(inner)
-    check(load().picaso_compress_thermal(ctx, ctypes.c_size_t(int(np.prod(inner))), ptr(x), ptr(gw),
-                                         ctypes.c_int(len(gw)), ptr(tw), ctypes.c_int(len(tw)),
-                                         ptr(out)), ctx)
+    check(load().picaso_compress_thermal(ctx, int(np.prod(inner)), ptr(x), ptr(gw), len(gw), ptr(tw), len(tw), ptr(out)), ctx)
     return out

@@ -54,24 +54,6 @@ class Job(ctypes.Structure):
                 ("ngauss", ctypes.c_int), ("gauss_wts", _dp)]
 
 
-def _dev(x):
-    """DeviceArray / raw address / None -> POINTER(c_double)"""
-    if x is None:
-        return None
-    return ctypes.cast(ctypes.c_void_p(int(x.addr if isinstance(x, DeviceArray) else x)), _dp)
-
-
-def _host(a):
-    return a.ctypes.data_as(_dp) if a is not None else None
-
-
-def _table_ptrs(devs):
-    arr = (_dp * max(1, len(devs)))()
-    for i, d in enumerate(devs):
-        arr[i] = _dev(d)
-    return arr
-
-
 class BlockTable:
     """The blocks of one opacity object (``subs``: [(lo, hi, shard opacity object)]; one entry covering the whole grid
     for a single-GPU spectrum) for one signature of the call -- molecule / continuum / Rayleigh species in table order,
@@ -96,7 +78,7 @@ class BlockTable:
             tabs = [sub._kappa] if ngauss > 1 else [(sub._mol_log if linear else sub._mol_raw)[m] for m in mol_names]
             ncolg = nw * ngauss
             ctabs, rtabs = [sub._cia[p] for p in cia_pairs], [sub._ray[m] for m in ray_names]
-            mt, ct, rt = _table_ptrs(tabs), _table_ptrs(ctabs), _table_ptrs(rtabs)
+            mt, ct, rt = _lib.ptr_array(tabs), _lib.ptr_array(ctabs), _lib.ptr_array(rtabs)
             self.keep += [mt, ct, rt, tabs, ctabs, rtabs]    # the tables themselves too: the structs hold raw addresses
             k.mol_tabs, k.cont_tabs, k.ray_tabs = ctypes.cast(mt, _dpp), ctypes.cast(ct, _dpp), ctypes.cast(rt, _dpp)
             if facets:
@@ -109,22 +91,22 @@ class BlockTable:
             else:
                 tg, tr = DeviceArray((nlayer, ncolg), ctx), DeviceArray((nlayer, nw), ctx)
                 self.keep += [tg, tr]
-                k.taugas, k.tauray = _dev(tg), _dev(tr)
+                k.taugas, k.tauray = _lib.ptr(tg), _lib.ptr(tr)
                 pl = self._alloc_planes(k, self.want, (nlayer, ncolg), (nlayer + 1, ncolg), ctx)
                 legs, refl = _planes.views(choice, pl, lambda: const_planes(sub, nlayer, nw))
             if do_reflected:
                 for i, name in enumerate(_planes.SH_PLANES if sh else _planes.REFLECTED_PLANES):
-                    k.refl_planes[i] = _dev(refl.get(name))       # None: left out, re-derived in the kernel
+                    k.refl_planes[i] = _lib.ptr(refl.get(name))       # None: left out, re-derived in the kernel
                 x, a = DeviceArray((ng, nt, nw), ctx), DeviceArray((nw + 1,), ctx)     # [nw]: the Bond-albedo integral
                 pin = PinnedArray((nw + 1,), ctx)           # the result copy is enqueued with the launches
                 self.keep += [x, a, pin]
-                k.xint, k.albedo, k.albedo_pin = _dev(x), _dev(a), ctypes.cast(ctypes.c_void_p(pin.addr), _dp)
+                k.xint, k.albedo, k.albedo_pin = _lib.ptr(x), _lib.ptr(a), _lib.ptr(pin)
             if do_thermal:                               # (3-D: no cosb plane without cloud)
-                k.th_dtau, k.th_w0, k.th_cosb = (_dev(legs[n]) if n else None for n in choice.thermal)
+                k.th_dtau, k.th_w0, k.th_cosb = (_lib.ptr(legs[n]) if n else None for n in choice.thermal)
             if host_cloud:
                 cw = [DeviceArray((nlayer, nw), ctx) for _ in range(3)]
                 self.keep += cw
-                k.cld_work_opd, k.cld_work_w0, k.cld_work_g0 = (_dev(c) for c in cw)
+                k.cld_work_opd, k.cld_work_w0, k.cld_work_g0 = (_lib.ptr(c) for c in cw)
         self.thermal_ws = {}                              # thermal outputs live on the thermal leg's context
 
     def _alloc_planes(self, k, want, shape, level_shape, ctx):
@@ -134,7 +116,7 @@ class BlockTable:
             if name in want:
                 pl[name] = DeviceArray(level_shape if name in ("tau", "tau_og") else shape, ctx)
                 self.keep.append(pl[name])
-                k.planes[i] = _dev(pl[name])
+                k.planes[i] = _lib.ptr(pl[name])
         return pl
 
     def thermal_workspace(self, b, tctx, ng, nt):
@@ -169,10 +151,10 @@ def make_job(nlayer, plan, factors, linear, raman_rows, stream, delta_eddington,
     j.nlayer, j.mol_mode, j.nmol, j.cont_interp, j.ncont, j.nray = (nlayer, (2 if premixed else (1 if linear else 0)), nmol,
                                                                     (1 if premixed else 0), ncont, len(ray_names))
     j.mol_rows = keep["rows"].ctypes.data_as(_ip) if nmol else None
-    j.mol_wts, j.mol_fac = (_host(keep["wts"]), _host(keep["mol_fac"])) if nmol else (None, None)
+    j.mol_wts, j.mol_fac = (_lib.ptr(keep["wts"]), _lib.ptr(keep["mol_fac"])) if nmol else (None, None)
     j.cont_rows = keep["cont_rows"].ctypes.data_as(_ip) if ncont else None
-    j.cont_wts, j.cont_fac = (_host(keep["cont_wts"]) if (premixed and ncont) else None), (_host(keep["cont_fac"]) if ncont else None)
-    j.ray_fac = _host(keep["ray_fac"]) if len(ray_names) else None
+    j.cont_wts, j.cont_fac = (_lib.ptr(keep["cont_wts"]) if (premixed and ncont) else None), (_lib.ptr(keep["cont_fac"]) if ncont else None)
+    j.ray_fac = _lib.ptr(keep["ray_fac"]) if len(ray_names) else None
     j.raman_rows, j.raman_const = raman_rows, 0.99999
     j.test_mode, j.delta_eddington, j.stream = 0, (1 if delta_eddington else 0), stream
     j.do_reflected, j.do_thermal, j.numg, j.numt = int(do_reflected), int(do_thermal), ng, nt
@@ -180,18 +162,18 @@ def make_job(nlayer, plan, factors, linear, raman_rows, stream, delta_eddington,
     j.ngauss, j.gauss_wts = 1, None
     if gauss_wts is not None and len(gauss_wts) > 1:      # premixed k-tables: the Gauss-point loop inside the solver calls
         keep["gauss_wts"] = _lib.f64(gauss_wts)
-        j.ngauss, j.gauss_wts = int(len(gauss_wts)), _host(keep["gauss_wts"])
+        j.ngauss, j.gauss_wts = int(len(gauss_wts)), _lib.ptr(keep["gauss_wts"])
     if after_opacity is not None:
         after_opacity(j)
     # ---- the legs' half ----
     keep.update(u0=_lib.f64(ubar0, (ng, nt)), u1=_lib.f64(ubar1, (ng, nt)), gw=_lib.f64(gweight), tw=_lib.f64(tweight),
                 tl=_lib.f64(tlevel), pl=_lib.f64(plevel))
-    j.ubar0, j.ubar1, j.cos_theta = _host(keep["u0"]), _host(keep["u1"]), float(cos_theta)
-    j.gweight, j.tweight = _host(keep["gw"]), _host(keep["tw"])
+    j.ubar0, j.ubar1, j.cos_theta = _lib.ptr(keep["u0"]), _lib.ptr(keep["u1"]), float(cos_theta)
+    j.gweight, j.tweight = _lib.ptr(keep["gw"]), _lib.ptr(keep["tw"])
     j.single_phase, j.multi_phase, j.toon_coefficients = int(single_phase), int(multi_phase), int(toon_coefficients)
     j.frac_a, j.frac_b, j.frac_c = float(frac_a), float(frac_b), float(frac_c)
     j.constant_back, j.constant_forward, j.b_top = float(constant_back), float(constant_forward), float(b_top)
-    j.tlevel, j.plevel, j.hard_surface = _host(keep["tl"]), _host(keep["pl"]), int(hard_surface)
+    j.tlevel, j.plevel, j.hard_surface = _lib.ptr(keep["tl"]), _lib.ptr(keep["pl"]), int(hard_surface)
     if sh is not None:                     # inputs["approx"]["rt_params"]["SH"]: the spherical-harmonics solvers
         j.rt_method = 1
         j.sh_w_single_form, j.sh_w_multi_form, j.sh_psingle_form = (int(sh[k]) for k in ("w_single_form", "w_multi_form", "psingle_form"))
@@ -205,18 +187,18 @@ def enqueue(table, job, phase=0):
     """``phase`` 0: the whole spectrum in one call; 1: the opacity stage alone, 2: everything behind it
     (``picaso_toon_spectrum_phase``, 1-D blocks: what ``make_job(after_opacity=...)`` is for)."""
     if phase:
-        rc = _lib.load().picaso_toon_spectrum_phase(ctypes.c_int(table.n), table.blocks, ctypes.byref(job), ctypes.c_int(phase))
+        rc = _lib.load().picaso_toon_spectrum_phase(table.n, table.blocks, ctypes.byref(job), phase)
     else:
-        rc = _lib.load().picaso_toon_spectrum_blocks(ctypes.c_int(table.n), table.blocks, ctypes.byref(job))
+        rc = _lib.load().picaso_toon_spectrum_blocks(table.n, table.blocks, ctypes.byref(job))
     _lib.check(rc, table.subs[0][2].ctx)
 
 
 def collect(table, which):
-    _lib.check(_lib.load().picaso_toon_spectrum_collect(ctypes.c_int(table.n), table.blocks, ctypes.c_int(which)),
+    _lib.check(_lib.load().picaso_toon_spectrum_collect(table.n, table.blocks, which),
                table.subs[0][2].ctx)
 
 
 def abandon(table):
     """Drop result copies nobody will collect (an exception between ``enqueue`` and ``collect``)."""
-    _lib.load().picaso_toon_spectrum_abandon(ctypes.c_int(table.n), table.blocks)
+    _lib.load().picaso_toon_spectrum_abandon(table.n, table.blocks)
 

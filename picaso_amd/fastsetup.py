@@ -17,25 +17,21 @@ from .options import current as _options
 from . import _lib
 from .atmsetup import ATMSETUP, molecular_weight
 
-_vp, _ci, _cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+_P, _I, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double         # SetupArgs' member types
 
 
 class SetupArgs(ctypes.Structure):
-    _fields_ = [("nlevel", _ci), ("nmol", _ci), ("pressure_bar", _vp), ("temperature", _vp), ("mix", _vp), ("weights", _vp),
-                ("gravity", _cd), ("radius", _cd), ("GM", _cd), ("p_reference_bar", _cd), ("pconv", _cd), ("k_b", _cd), ("amu", _cd),
-                ("coef1_scale", _cd), ("coef1_den", _cd), ("log_pratio", _vp), ("log10_player", _vp), ("pbar_cubed_hi", _vp), ("pbar_cubed_lo", _vp),
-                ("nt", _ci), ("npg", _ci), ("t_inv_grid", _vp), ("p_log_grid", _vp), ("nc_p", _vp), ("row_lut", _vp),
-                ("nlut", _ci), ("ncia_t", _ci), ("cia_temps", _vp), ("nopa", _ci), ("ncont", _ci), ("nray", _ci),
-                ("opa_idx", _vp), ("cont_a", _vp), ("cont_b", _vp), ("ray_idx", _vp),
-                ("level_pressure", _vp), ("level_mmw", _vp), ("level_den", _vp), ("z", _vp), ("dz", _vp),
-                ("scale_height", _vp), ("layer_temperature", _vp), ("layer_pressure", _vp), ("layer_mmw", _vp),
-                ("layer_gravity", _vp), ("colden", _vp), ("layer_mix", _vp), ("rows", _vp), ("wts", _vp), ("cia_rows", _vp),
-                ("mol_fac", _vp), ("cont_fac", _vp), ("ray_fac", _vp), ("pt_opa_index", _vp), ("n_pt_opa_index", _vp),
-                ("scratch", _vp), ("premixed", _ci), ("cont_interp", _ci), ("cia_rows2", _vp), ("cia_wts2", _vp)]
-
-
-def _addr(a):
-    return a.__array_interface__["data"][0]
+    _fields_ = [("nlevel", _I), ("nmol", _I), ("pressure_bar", _P), ("temperature", _P), ("mix", _P), ("weights", _P),
+                ("gravity", _D), ("radius", _D), ("GM", _D), ("p_reference_bar", _D), ("pconv", _D), ("k_b", _D), ("amu", _D),
+                ("coef1_scale", _D), ("coef1_den", _D), ("log_pratio", _P), ("log10_player", _P), ("pbar_cubed_hi", _P), ("pbar_cubed_lo", _P),
+                ("nt", _I), ("npg", _I), ("t_inv_grid", _P), ("p_log_grid", _P), ("nc_p", _P), ("row_lut", _P),
+                ("nlut", _I), ("ncia_t", _I), ("cia_temps", _P), ("nopa", _I), ("ncont", _I), ("nray", _I),
+                ("opa_idx", _P), ("cont_a", _P), ("cont_b", _P), ("ray_idx", _P),
+                ("level_pressure", _P), ("level_mmw", _P), ("level_den", _P), ("z", _P), ("dz", _P),
+                ("scale_height", _P), ("layer_temperature", _P), ("layer_pressure", _P), ("layer_mmw", _P),
+                ("layer_gravity", _P), ("colden", _P), ("layer_mix", _P), ("rows", _P), ("wts", _P), ("cia_rows", _P),
+                ("mol_fac", _P), ("cont_fac", _P), ("ray_fac", _P), ("pt_opa_index", _P), ("n_pt_opa_index", _P),
+                ("scratch", _P), ("premixed", _I), ("cont_interp", _I), ("cia_rows2", _P), ("cia_wts2", _P)]
 
 
 def _is_premixed(opa):
@@ -131,15 +127,16 @@ class _Layout:
         self.i_fields = [("rows", 0), ("cia_rows", 4 * self.o_cia), ("pt_opa_index", 4 * self.o_pt),
                          ("n_pt_opa_index", 4 * (self.o_pt + 4 * nl))]
         a = SetupArgs()
-        a.nlevel, a.nmol, a.weights = n, nmol, _addr(sig.weights)
+        a.nlevel, a.nmol, a.weights = n, nmol, _lib.addr(sig.weights)
         a.pconv, a.k_b, a.amu = c.pconv, c.k_b, c.amu
         a.coef1_scale = c.rgas * 273.15 ** 2 * .5E5
         a.nt, a.npg = sig.t_inv_grid.size, sig.p_log_grid.size
-        a.t_inv_grid, a.p_log_grid, a.nc_p, a.row_lut = (_addr(sig.t_inv_grid), _addr(sig.p_log_grid), _addr(sig.nc_p),
-                                                         _addr(sig.row_lut))
-        a.nlut, a.ncia_t, a.cia_temps = sig.row_lut.size, sig.cia_temps.size, _addr(sig.cia_temps)
+        a.t_inv_grid, a.p_log_grid, a.nc_p, a.row_lut = (_lib.addr(sig.t_inv_grid), _lib.addr(sig.p_log_grid), _lib.addr(sig.nc_p),
+                                                         _lib.addr(sig.row_lut))
+        a.nlut, a.ncia_t, a.cia_temps = sig.row_lut.size, sig.cia_temps.size, _lib.addr(sig.cia_temps)
         a.nopa, a.ncont, a.nray = nopa, ncont, nray
-        a.opa_idx, a.cont_a, a.cont_b, a.ray_idx = _addr(sig.opa_idx), _addr(sig.cont_a), _addr(sig.cont_b), _addr(sig.ray_idx)
+        a.opa_idx, a.cont_a, a.cont_b, a.ray_idx = (_lib.addr(sig.opa_idx), _lib.addr(sig.cont_a), _lib.addr(sig.cont_b),
+                                                    _lib.addr(sig.ray_idx))
         a.premixed = a.cont_interp = 1 if sig.premixed else 0
         self.template = bytes(a)
 
@@ -202,16 +199,16 @@ def setup(inp, opa, wno):
     nopa, ncont, nray, sizes, offs, o_cia, o_pt = lay.nopa, lay.ncont, lay.nray, lay.sizes, lay.offs, lay.o_cia, lay.o_pt
     fbuf = np.empty(lay.nf)
     ibuf = np.empty(lay.ni, dtype=np.int32)
-    fb, ib = _addr(fbuf), _addr(ibuf)
-    mixp = (_vp * nmol)(*[_addr(x) for x in mixcols])
+    fb, ib = _lib.addr(fbuf), _lib.addr(ibuf)
+    mixp = (_P * nmol)(*[_lib.addr(x) for x in mixcols])
     gravity = inp["planet"]["gravity"]
     a = SetupArgs.from_buffer_copy(lay.template)            # the grid / index half is the same for every call
-    a.pressure_bar, a.temperature, a.mix = _addr(pbar), _addr(T), ctypes.addressof(mixp)
+    a.pressure_bar, a.temperature, a.mix = _lib.addr(pbar), _lib.addr(T), ctypes.addressof(mixp)
     a.gravity, a.radius, a.p_reference_bar = float(gravity), radius, float(inp["approx"]["p_reference"])
     a.GM = c.G * mass if radius == radius else 0.0
     a.coef1_den = 1.01325 ** 2 * (gravity / 100.0)
     if pg.addr is None:
-        pg.addr = (_addr(pg.log_pratio), _addr(pg.log10_player), _addr(pg.cube_hi), _addr(pg.cube_lo))
+        pg.addr = (_lib.addr(pg.log_pratio), _lib.addr(pg.log10_player), _lib.addr(pg.cube_hi), _lib.addr(pg.cube_lo))
     a.log_pratio, a.log10_player, a.pbar_cubed_hi, a.pbar_cubed_lo = pg.addr
     for name, off in lay.f_fields:
         setattr(a, name, fb + off)
@@ -220,7 +217,7 @@ def setup(inp, opa, wno):
     rows2 = wts2 = None
     if sig.premixed:
         rows2, wts2 = np.empty((nl, 2), dtype=np.int32), np.empty((nl, 2))
-        a.cia_rows2, a.cia_wts2 = _addr(rows2), _addr(wts2)
+        a.cia_rows2, a.cia_wts2 = _lib.addr(rows2), _lib.addr(wts2)
     rc = _lib.load().picaso_host_setup(ctypes.byref(a))
     if rc != 0:
         return None
@@ -319,19 +316,19 @@ def setup_facets(inp, opa, wno, prof_f):
     isz = [nopa * nl * 4, nc1 * nl, 4 * nl, 1]
     ioff = np.concatenate(([0], np.cumsum([x * nfac for x in isz]))).tolist()
     ibuf = np.empty(ioff[-1], dtype=np.int32)
-    fb, ib = _addr(fbuf), _addr(ibuf)
-    mixp = (_vp * nmol)(*[_addr(x) for x in mixcols])
+    fb, ib = _lib.addr(fbuf), _lib.addr(ibuf)
+    mixp = (_P * nmol)(*[_lib.addr(x) for x in mixcols])
     mstr = (ctypes.c_long * nmol)(*strides)
     gravity = inp["planet"]["gravity"]
     a = SetupArgs.from_buffer_copy(lay.template)
-    a.pressure_bar, a.temperature, a.mix = _addr(pbar), _addr(T), ctypes.addressof(mixp)
+    a.pressure_bar, a.temperature, a.mix = _lib.addr(pbar), _lib.addr(T), ctypes.addressof(mixp)
     a.gravity, a.radius, a.p_reference_bar = float(gravity), radius, float(inp["approx"]["p_reference"])
     # a planet radius: gravity G M / z^2 level by level with libm's pow, facet by facet -- what the mirror's facet form does
     # element by element (atmsetup.get_altitude: math.pow per facet) and the reference's per-facet ATMSETUP with its scalars
     a.GM = c.G * mass if radius == radius else 0.0
     a.coef1_den = 1.01325 ** 2 * (gravity / 100.0)
     if pg.addr is None:
-        pg.addr = (_addr(pg.log_pratio), _addr(pg.log10_player), _addr(pg.cube_hi), _addr(pg.cube_lo))
+        pg.addr = (_lib.addr(pg.log_pratio), _lib.addr(pg.log10_player), _lib.addr(pg.cube_hi), _lib.addr(pg.cube_lo))
     a.log_pratio, a.log10_player, a.pbar_cubed_hi, a.pbar_cubed_lo = pg.addr
     for k, name in enumerate(_Layout.F_NAMES):
         setattr(a, name, fb + 8 * foff[k])
@@ -340,8 +337,8 @@ def setup_facets(inp, opa, wno, prof_f):
     rows2 = wts2 = None
     if sig.premixed:
         rows2, wts2 = np.empty((nfac * nl, 2), dtype=np.int32), np.empty((nfac * nl, 2))
-        a.cia_rows2, a.cia_wts2 = _addr(rows2), _addr(wts2)
-    rc = _lib.load().picaso_host_setup_facets(ctypes.byref(a), _ci(nfac), ctypes.c_long(n), mstr)
+        a.cia_rows2, a.cia_wts2 = _lib.addr(rows2), _lib.addr(wts2)
+    rc = _lib.load().picaso_host_setup_facets(ctypes.byref(a), nfac, n, mstr)
     if rc != 0:
         return None
 

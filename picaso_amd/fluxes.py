@@ -6,13 +6,11 @@ be numpy arrays (copied to HBM, result copied back) -- exactly how ``justdoit.pi
 reference (reference picaso/justdoit.py:275-283, 337-342, 492, 510).  For HBM-resident planes use
 ``picaso_amd.resident``.
 """
-import ctypes
 
 import numpy as np
 
 from ._lib import check, context, f64, load, per_wave, ptr, serialized
 
-_ci, _cd = ctypes.c_int, ctypes.c_double
 
 
 @serialized
@@ -40,11 +38,11 @@ def get_reflected_1d(nlevel, wno, nwno, numg, numt, dtau, tau, w0, cosb, gcos2, 
     xint = np.zeros((numg, numt, nwno))
     lvl = [np.zeros((numg, numt, nlevel, nwno)) for _ in range(4)]
     check(load().picaso_get_reflected_1d(
-        ctx, _ci(nlevel), None, _ci(nwno), _ci(numg), _ci(numt), *[ptr(p) for p in planes],
-        ptr(rs), ptr(u0), ptr(u1), _cd(cos_theta), ptr(f0), _ci(int(single_phase)),
-        _ci(int(multi_phase)), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back),
-        _cd(constant_forward), _ci(int(get_toa_intensity)), _ci(int(get_lvl_flux)),
-        _ci(int(toon_coefficients)), _cd(b_top), ptr(xint),
+        ctx, nlevel, None, nwno, numg, numt, *[ptr(p) for p in planes],
+        ptr(rs), ptr(u0), ptr(u1), cos_theta, ptr(f0), int(single_phase),
+        int(multi_phase), frac_a, frac_b, frac_c, constant_back,
+        constant_forward, int(get_toa_intensity), int(get_lvl_flux),
+        int(toon_coefficients), b_top, ptr(xint),
         *[ptr(l) if get_lvl_flux else None for l in lvl]), ctx)
     return xint, tuple(lvl)
 
@@ -63,10 +61,10 @@ def get_reflected_3d(nlevel, wno, nwno, numg, numt, dtau_3d, tau_3d, w0_3d, cosb
     u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
     xint = np.zeros((numg, numt, nwno))
     check(load().picaso_get_reflected_3d(
-        ctx, _ci(nlevel), None, _ci(nwno), _ci(numg), _ci(numt), *[ptr(p) for p in planes],
-        ptr(rs), ptr(u0), ptr(u1), _cd(cos_theta), ptr(f0), _ci(int(single_phase)),
-        _ci(int(multi_phase)), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back),
-        _cd(constant_forward), ptr(xint)), ctx)
+        ctx, nlevel, None, nwno, numg, numt, *[ptr(p) for p in planes],
+        ptr(rs), ptr(u0), ptr(u1), cos_theta, ptr(f0), int(single_phase),
+        int(multi_phase), frac_a, frac_b, frac_c, constant_back,
+        constant_forward, ptr(xint)), ctx)
     return xint
 
 
@@ -87,8 +85,8 @@ def get_thermal_1d(nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb, plevel
     flux = np.zeros((numg, numt, nwno))
     lvl = [np.zeros((numg, numt, nlevel, nwno)) for _ in range(4)]
     check(load().picaso_get_thermal_1d(
-        ctx, _ci(nlevel), ptr(wno_), _ci(nwno), _ci(numg), _ci(numt), ptr(tl), ptr(dt), ptr(w0_),
-        ptr(cb), ptr(pl), ptr(u1), ptr(rs), _ci(int(hard_surface)), ptr(dw), _ci(int(calc_type)),
+        ctx, nlevel, ptr(wno_), nwno, numg, numt, ptr(tl), ptr(dt), ptr(w0_),
+        ptr(cb), ptr(pl), ptr(u1), ptr(rs), int(hard_surface), ptr(dw), int(calc_type),
         ptr(flux), *[ptr(l) if want_lvl else None for l in lvl]), ctx)
     return flux, tuple(lvl)
 
@@ -106,8 +104,8 @@ def get_thermal_3d(nlevel, wno, nwno, numg, numt, tlevel_3d, dtau_3d, w0_3d, cos
     u1 = f64(ubar1, (numg, numt))
     out = np.zeros((numg, numt, nwno))
     check(load().picaso_get_thermal_3d(
-        ctx, _ci(nlevel), ptr(wno_), _ci(nwno), _ci(numg), _ci(numt), ptr(tl), ptr(dt), ptr(w0_),
-        ptr(cb), ptr(pl), ptr(u1), ptr(rs), _ci(int(hard_surface)), ptr(out)), ctx)
+        ctx, nlevel, ptr(wno_), nwno, numg, numt, ptr(tl), ptr(dt), ptr(w0_),
+        ptr(cb), ptr(pl), ptr(u1), ptr(rs), int(hard_surface), ptr(out)), ctx)
     return out
 
 
@@ -140,12 +138,12 @@ def get_reflected_SH(nlevel, nwno, numg, numt, dtau, tau, w0, cosb, ftau_cld, ft
     xint = np.zeros((numg, numt, nwno))
     flux = np.zeros((numg, numt, stream * nlevel, nwno))
     check(load().picaso_get_reflected_SH(
-        ctx, _ci(nlevel), _ci(nwno), _ci(numg), _ci(numt), *[ptr(p) for p in arrs], ptr(rs), ptr(u0),
-        ptr(u1), _cd(cos_theta), ptr(f0), _ci(int(w_single_form)), _ci(int(w_multi_form)),
-        _ci(int(psingle_form)), _ci(int(w_single_rayleigh)), _ci(int(w_multi_rayleigh)),
-        _ci(int(psingle_rayleigh)), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back),
-        _cd(constant_forward), _ci(int(stream)), _cd(b_top), _ci(int(flx)), _ci(int(single_form)),
-        _ci(1 if compound_f_deltaM else 0), ptr(xint), ptr(flux) if flx else None), ctx)
+        ctx, nlevel, nwno, numg, numt, *[ptr(p) for p in arrs], ptr(rs), ptr(u0),
+        ptr(u1), cos_theta, ptr(f0), int(w_single_form), int(w_multi_form),
+        int(psingle_form), int(w_single_rayleigh), int(w_multi_rayleigh),
+        int(psingle_rayleigh), frac_a, frac_b, frac_c, constant_back,
+        constant_forward, int(stream), b_top, int(flx), int(single_form),
+        1 if compound_f_deltaM else 0, ptr(xint), ptr(flux) if flx else None), ctx)
     if compound_f_deltaM and (w_single_form == 0 or w_multi_form == 0) and \
             isinstance(f_deltaM, np.ndarray) and f_deltaM.dtype == np.float64 and f_deltaM.flags.writeable:
         gb = constant_back * np.asarray(cosb_og, dtype=float)
@@ -169,9 +167,9 @@ def get_thermal_SH(nlevel, wno, nwno, numg, numt, tlevel, dtau, tau, w0, cosb, d
     u1 = f64(ubar1, (numg, numt))
     xint = np.zeros((numg, numt, nwno))
     check(load().picaso_get_thermal_SH(
-        ctx, _ci(nlevel), ptr(wno_), _ci(nwno), _ci(numg), _ci(numt), ptr(tl), ptr(dt), ptr(ta),
-        ptr(w0_), ptr(cbo), ptr(pl), ptr(u1), ptr(rs), _ci(int(stream)), _ci(int(hard_surface)),
-        _ci(differs), _ci(int(flx)), ptr(xint)), ctx)
+        ctx, nlevel, ptr(wno_), nwno, numg, numt, ptr(tl), ptr(dt), ptr(ta),
+        ptr(w0_), ptr(cbo), ptr(pl), ptr(u1), ptr(rs), int(stream), int(hard_surface),
+        differs, int(flx), ptr(xint)), ctx)
     return xint, np.zeros((numg, numt, stream * nlevel, nwno))
 
 
@@ -185,8 +183,8 @@ def get_transit_1d(z, dz, nlevel, nwno, rstar, mmw, k_b, amu, player, tlayer, co
         raise Exception("get_transit_1d: DTAU of shape %s, expected %s" % (d.shape, (nlevel - 1, nwno)))
     out = np.zeros(nwno)
     check(load().picaso_get_transit_1d(
-        ctx, ptr(f64(z, (nlevel,))), ptr(f64(dz, (nlevel,))), _ci(nlevel), _ci(nwno), _cd(rstar),
-        ptr(f64(mmw, (nlevel - 1,))), _cd(k_b), _cd(amu), ptr(f64(player)), ptr(f64(tlayer)),
+        ctx, ptr(f64(z, (nlevel,))), ptr(f64(dz, (nlevel,))), nlevel, nwno, rstar,
+        ptr(f64(mmw, (nlevel - 1,))), k_b, amu, ptr(f64(player)), ptr(f64(tlayer)),
         ptr(f64(colden, (nlevel - 1,))), ptr(d), ptr(out)), ctx)
     return out
 
@@ -200,7 +198,7 @@ def blackbody(t, w):
     t_ = np.ascontiguousarray(np.atleast_1d(t), dtype=np.float64).ravel()
     w_ = np.ascontiguousarray(np.atleast_1d(w), dtype=np.float64).ravel()
     out = np.zeros((t_.size, w_.size))
-    check(load().picaso_blackbody(ctx, _ci(t_.size), ptr(t_), ctypes.c_long(w_.size), ptr(w_), ptr(out)), ctx)
+    check(load().picaso_blackbody(ctx, t_.size, ptr(t_), w_.size, ptr(w_), ptr(out)), ctx)
     return out
 
 
@@ -214,7 +212,7 @@ def blackbody_integrated(T, wave, dwave):
     w_ = np.ascontiguousarray(np.atleast_1d(wave), dtype=np.float64).ravel()
     d_ = f64(np.atleast_1d(dwave), (w_.size,))
     out = np.zeros((t_.size, w_.size))
-    check(load().picaso_blackbody_integrated(ctx, _ci(t_.size), ptr(t_), ctypes.c_long(w_.size), ptr(w_), ptr(d_),
+    check(load().picaso_blackbody_integrated(ctx, t_.size, ptr(t_), w_.size, ptr(w_), ptr(d_),
                                              ptr(out)), ctx)
     return out
 

@@ -64,7 +64,7 @@ def enqueue_regrid(p):
     disk = ctypes.cast(k.disk, ctypes.c_void_p).value if p["do_t"] else None
     tails = ([alb + 8 * nwno] if p["do_r"] else []) + ([disk + 8 * nwno] if p["do_t"] else [])
     if p["do_t"] and k.tctx and k.tctx != k.ctx:
-        _lib.ctx_wait(ctx, ctypes.c_void_p(k.tctx))
+        _lib.ctx_wait(ctx, k.tctx)
     rows, p["lists"] = _regrid.spectral_rows(alb, disk, None, p["d_stellar"], inp["star"]["semi_major"], inp["star"]["radius"],
                                              atm.planet.radius)
     p["binned"] = plan.enqueue(ctx, rows, tails, keep=p["keep"])
@@ -165,11 +165,11 @@ def _fill_block_opacity(k, sub, lo, hi, c):
     nw, nwno, hold, atm = hi - lo, c["nwno"], c["hold"], c["atm"]
     if c["raman"] == 1:
         row, _ = optics.raman_device(atm, sub, 1)
-        k.raman = drv._dev(row)
+        k.raman = _lib.ptr(row)
     elif c["raman"] == 0:           # (nlayer, nwno) plane from the layer temperatures (picaso_raman_oklopcic_dev), same stream
         rplane, _ = optics.raman_device(atm, sub, 0)
         hold.append(rplane)
-        k.raman = drv._dev(rplane)
+        k.raman = _lib.ptr(rplane)
     else:
         k.raman = None
     dcld, dtab, hcld = c["clouds"]
@@ -185,12 +185,12 @@ def _fill_block_opacity(k, sub, lo, hi, c):
                                                        DeviceArray.from_host(dtab[2], sub.ctx))
         d_xp, d_fp = hit[1], hit[2]
         hold.append((d_xp, d_fp))
-        k.cld_tab_nin, k.cld_tab_xp, k.cld_tab_fp = dtab[0], drv._dev(d_xp), drv._dev(d_fp)
-        k.wno = drv._dev(_resident_vector(sub, "wno", sub.wno, nw))
+        k.cld_tab_nin, k.cld_tab_xp, k.cld_tab_fp = dtab[0], _lib.ptr(d_xp), _lib.ptr(d_fp)
+        k.wno = _lib.ptr(_resident_vector(sub, "wno", sub.wno, nw))
     elif dcld is not None:
-        k.cld_opd, k.cld_w0, k.cld_g0 = (drv._dev(x) for x in dcld)
+        k.cld_opd, k.cld_w0, k.cld_g0 = (_lib.ptr(x) for x in dcld)
     elif hcld is not None:
-        k.cld_host_opd, k.cld_host_w0, k.cld_host_g0 = (drv._host(h) for h in hcld)
+        k.cld_host_opd, k.cld_host_w0, k.cld_host_g0 = (_lib.ptr(h) for h in hcld)
         k.cld_host_pitch = nwno
     if c["do_t"]:
         tctx = sub.ctx
@@ -211,17 +211,17 @@ def _fill_block_legs(k, sub, lo, hi, c):
     sr_full = np.ndim(sr) > 0 and np.size(sr) == nwno and nwno > 1
     rs = _resident_vector(sub, "surf_reflect", np.asarray(sr, dtype=float).reshape(nwno)[lo:hi] if sr_full else sr, nw)
     f0 = _resident_vector(sub, "F0PI", 1.0 if c["nostar"] else (c["F0PI"] if c["nblocks"] == 1 else c["F0PI"][lo:hi]), nw)
-    k.surf_reflect, k.F0PI = drv._dev(rs), drv._dev(f0)
+    k.surf_reflect, k.F0PI = _lib.ptr(rs), _lib.ptr(f0)
     hold.append((rs, f0))            # the block holds raw addresses: the vectors live as long as the call is in flight
     if c["do_t"]:
         tctx = c["tctx"][c["b"]]
         fl, dk, pin = c["table"].thermal_workspace(c["b"], tctx, c["ng"], c["nt"])
-        k.flux, k.disk = drv._dev(fl), drv._dev(dk)
-        k.thermal_pin = ctypes.cast(ctypes.c_void_p(pin.addr), drv._dp)
-        k.wno = drv._dev(_resident_vector(sub, "wno", sub.wno, nw))
-        k.thermal_host = drv._host(c["full"].get("thermal"))       # regrid=: NULL, the result stays on the device
+        k.flux, k.disk = _lib.ptr(fl), _lib.ptr(dk)
+        k.thermal_pin = _lib.ptr(pin)
+        k.wno = _lib.ptr(_resident_vector(sub, "wno", sub.wno, nw))
+        k.thermal_host = _lib.ptr(c["full"].get("thermal"))       # regrid=: NULL, the result stays on the device
     if c["do_r"]:
-        k.albedo_host = drv._host(c["full"].get("albedo"))
+        k.albedo_host = _lib.ptr(c["full"].get("albedo"))
     if c["regrid"] is not None:                 # the stellar vector the flux ratios divide by (one block: the whole grid)
         c["d_stellar"] = f0 if c["stellar"] is c["F0PI"] else _resident_vector(sub, "stellar", c["stellar"], nw)
         hold.append(c["d_stellar"])
@@ -233,10 +233,10 @@ def _fill_block_legs(k, sub, lo, hi, c):
         if c["do_r"]:
             d_st = f0 if c["stellar"] is c["F0PI"] else _resident_vector(sub, "stellar", c["stellar"], nw)
             hold.append(d_st)
-            k.trapz_d, k.stellar = drv._dev(d_w), drv._dev(d_st)
+            k.trapz_d, k.stellar = _lib.ptr(d_w), _lib.ptr(d_st)
             c["denom"] = _bond_denominator(sub, c["wno"], c["stellar"], d_st)
         if c["do_t"]:
-            k.trapz_dr = drv._dev(d_wr)
+            k.trapz_dr = _lib.ptr(d_wr)
 
 
 def _block_table(opa, subs, plan, linear, ck, slot, signature, make):
@@ -407,8 +407,8 @@ def prepare_3d(bundle, opa, subs, calculation, opt, slot=None, regrid=None):
         if cld3 is not None:        # the tall tables, resident per device (kept on the cloud dictionary by content)
             d_xp, d_tall, _, nin = optics._facet_major_cloud_tables(cld3, nlayer, nfac, sub.ctx, stamp=stamp3)
             hold.append((d_xp, d_tall))
-            k.cld_tab_nin, k.cld_tab_xp, k.cld_tab_fp = nin, drv._dev(d_xp), drv._dev(d_tall)
-            k.wno = drv._dev(_resident_vector(sub, "wno", sub.wno, hi - lo))
+            k.cld_tab_nin, k.cld_tab_xp, k.cld_tab_fp = nin, _lib.ptr(d_xp), _lib.ptr(d_tall)
+            k.wno = _lib.ptr(_resident_vector(sub, "wno", sub.wno, hi - lo))
     tl = np.ascontiguousarray(np.asarray(tlev3, dtype=float).reshape(nlevel, nfac).T)
     pv = np.ascontiguousarray(np.asarray(plev3, dtype=float).reshape(nlevel, nfac).T)
     job, keep = drv.make_job(nlayer, plan, factors, linear, 0, common["stream"], common["delta_eddington"], do_r, do_t, ng, nt,

@@ -160,8 +160,7 @@ def compute_ck(cxs, og_wvno_grid, wvno_low, wvno_high, gauss_pts, _lds_cap=0, _r
                     old.free()
             pinned[s], dev[s] = PinnedArray(row.shape, aux), DeviceArray(row.shape, ctx)
         pinned[s].array[:] = row
-        _lib.check(lib.picaso_memcpy_h2d_async(aux, ctypes.c_void_p(dev[s].addr), ctypes.c_void_p(pinned[s].addr),
-                                               ctypes.c_size_t(8 * row.size)), aux)
+        _lib.check(lib.picaso_memcpy_h2d_async(aux, dev[s].addr, pinned[s].addr, 8 * row.size), aux)
         return int(row.size)
 
     try:
@@ -176,10 +175,8 @@ def compute_ck(cxs, og_wvno_grid, wvno_low, wvno_high, gauss_pts, _lds_cap=0, _r
                 raise Exception("compute_ck: row %d has %d points, its wavenumber grid %d" % (i, n_lbl, n_grid))
             per = nbins * ngauss * 8
             _lib.check(lib.picaso_ck_from_xsec_dev(
-                ctx, ctypes.c_long(n_lbl), ctypes.c_void_p(dev[i & 1].addr), ctypes.c_int(nbins),
-                lo.ctypes.data_as(_c_ll_p), n.ctypes.data_as(_c_ll_p), ctypes.c_int(ngauss), _lib.ptr(g),
-                ctypes.c_long(int(_lds_cap)), ctypes.c_void_p(d_k.addr + i * per),
-                ctypes.c_void_p(d_stats.addr + 2 * i * per) if _return_stats else None), ctx)
+                ctx, n_lbl, dev[i & 1].addr, nbins, lo.ctypes.data_as(_c_ll_p), n.ctypes.data_as(_c_ll_p), ngauss, _lib.ptr(g),
+                int(_lds_cap), d_k.addr + i * per, d_stats.addr + 2 * i * per if _return_stats else None), ctx)
         k = d_k.to_host()
         return (k, d_stats.to_host()) if _return_stats else k
     finally:

@@ -27,14 +27,13 @@ import sqlite3
 import numpy as np
 
 from . import _lib
-from ._lib import check, f64, load, ptr
+from ._lib import check, f64, load, ptr, ptr_array
 from .atmsetup import CloudTables
 from .device import DeviceArray, regrid_rows
 from .options import current as _options
 from .planes import OUT_NAMES
 from .rayleigh import available_rayleigh
 
-_ci, _cd = ctypes.c_int, ctypes.c_double
 AVOGADRO = 6.02214086e+23
 
 
@@ -713,13 +712,6 @@ class _LazyPlanes(dict):
         return dict.__getitem__(self, k)
 
 
-def _ptr_array(devs):
-    arr = (ctypes.c_void_p * max(1, len(devs)))()
-    for i, d in enumerate(devs):
-        arr[i] = d.addr
-    return ctypes.cast(arr, ctypes.POINTER(ctypes.POINTER(ctypes.c_double)))
-
-
 def _gas_args(opa, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac, ray_tabs, ray_fac,
               mol_mode=None, cont_wts=None):
     """The gas-table arguments of ``picaso_opacity_gas_ck_dev`` from ``mol_mode`` to ``ray_fac`` (the ctypes pointers
@@ -738,11 +730,11 @@ def _gas_args(opa, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, c
     cw = f64(cont_wts) if cont_wts is not None else None
     cf = f64(cont_fac) if cont_fac is not None else None
     rf = f64(ray_fac) if ray_fac is not None else None
-    return (_ci(mol_mode),
-            _ci(len(mol_tabs)), _ptr_array(mol_tabs), mr.ctypes.data_as(ip) if mr is not None else None,
-            ptr(mw), ptr(mf), _ci(1 if cw is not None else 0), _ci(len(cont_tabs)), _ptr_array(cont_tabs),
-            cr.ctypes.data_as(ip) if cr is not None else None, ptr(cw), ptr(cf), _ci(len(ray_tabs)),
-            _ptr_array(ray_tabs), ptr(rf))
+    return (mol_mode,
+            len(mol_tabs), ptr_array(mol_tabs), mr.ctypes.data_as(ip) if mr is not None else None,
+            ptr(mw), ptr(mf), 1 if cw is not None else 0, len(cont_tabs), ptr_array(cont_tabs),
+            cr.ctypes.data_as(ip) if cr is not None else None, ptr(cw), ptr(cf), len(ray_tabs),
+            ptr_array(ray_tabs), ptr(rf))
 
 
 def _gas_call(opa, nlayer, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac,
@@ -751,10 +743,10 @@ def _gas_call(opa, nlayer, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont
     gas_args = _gas_args(opa, mol_tabs, mol_rows, mol_wts, mol_fac, cont_tabs, cont_rows, cont_fac, ray_tabs, ray_fac,
                          mol_mode=mol_mode, cont_wts=cont_wts)
     if mix is not None:       # gas stage + compute_opacity in one launch (ngauss = 1): `mix` = the mixing's arguments
-        check(load().picaso_gas_compute_opacity_dev(opa.ctx, _ci(nlayer), _ci(opa.nwno), *gas_args, *mix), opa.ctx)
+        check(load().picaso_gas_compute_opacity_dev(opa.ctx, nlayer, opa.nwno, *gas_args, *mix), opa.ctx)
         return
     check(load().picaso_opacity_gas_ck_dev(
-        opa.ctx, _ci(nlayer), _ci(opa.nwno), _ci(ngauss), *gas_args, ptr(taugas.addr), ptr(tauray.addr)), opa.ctx)
+        opa.ctx, nlayer, opa.nwno, ngauss, *gas_args, ptr(taugas.addr), ptr(tauray.addr)), opa.ctx)
 
 
 def _layer_factors(atm, opacityclass):
@@ -912,8 +904,8 @@ def raman_oklopcic_device(opa, tlayer, out):
     nlayer = tlayer.size
     jat = np.ascontiguousarray(np.stack([j_fraction(j, tlayer) for j in range(10)]), dtype=np.float64)
     check(load().picaso_raman_oklopcic_dev(
-        opa.ctx, _ci(nlayer), ctypes.c_long(opa.nwno), _ci(c.size), ptr(hit["Q"].addr), ptr(hit["QS"].addr),
-        hit["ji"].ctypes.data_as(ctypes.c_void_p), hit["isray"].ctypes.data_as(ctypes.c_void_p), ptr(jat), _cd(0.99999),
+        opa.ctx, nlayer, opa.nwno, c.size, ptr(hit["Q"].addr), ptr(hit["QS"].addr),
+        hit["ji"].ctypes.data_as(ctypes.c_void_p), hit["isray"].ctypes.data_as(ctypes.c_void_p), ptr(jat), 0.99999,
         ptr(out.addr)), opa.ctx)
 
 
@@ -1108,9 +1100,9 @@ def compute_opacity_facets(atms, opacityclass, numg, numt, stream=2, delta_eddin
     out = {k: (DeviceArray(((nlayer + 1 if k in ("tau", "tau_og") else nlayer), nwno, numg, numt), ctx)
                if (want is None or k in want) else None) for k in OUT_NAMES}
     check(load().picaso_compute_opacity_facets_dev(
-        ctx, _ci(nlayer), _ci(nwno), _ci(nfac), ptr(tg3.addr), ptr(tr3.addr),
+        ctx, nlayer, nwno, nfac, ptr(tg3.addr), ptr(tr3.addr),
         *[ptr(d.addr) if d is not None else None for d in d_c], ptr(d_rf.addr) if d_rf is not None else None,
-        _ci(rf_rows), _cd(0.99999), _ci(tm), _ci(1 if delta_eddington else 0), _ci(stream),
+        rf_rows, 0.99999, tm, 1 if delta_eddington else 0, stream,
         *[ptr(out[k].addr) if out[k] is not None else None for k in OUT_NAMES]), ctx)
     return {k: v for k, v in out.items() if v is not None}
 
@@ -1264,18 +1256,18 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
         sl = slice(f0 * nlayer, f1 * nlayer)
         nl_c = (f1 - f0) * nlayer
         off = f0 * nlayer * nwno * 8
-        cld_tab, keep = (_ci(0), None, None, None), None
+        cld_tab, keep = (0, None, None, None), None
         if cloud_tables is not None:
             d_xp, d_tall, h_tall, nin = cloud_tables
             if f0 == 0 and f1 == nfac:           # one launch: the resident (3 ntot, nin) rows as they are
                 d_fp = d_tall
             else:                                # this chunk's opd / w0 / g0 rows, contiguous
                 d_fp = keep = DeviceArray.from_host(np.ascontiguousarray(h_tall[:, sl].reshape(3 * nl_c, nin)), ctx)
-            cld_tab = (_ci(nin), ptr(d_xp.addr), ptr(d_fp.addr), ptr(_wno_device(opa, opa.wno).addr))
+            cld_tab = (nin, ptr(d_xp.addr), ptr(d_fp.addr), ptr(_wno_device(opa, opa.wno).addr))
         mix = (None, None, None,
-               ptr(d_rf.addr + (off if rf_rows else 0)) if d_rf is not None else None, _ci(nl_c if rf_rows else 0),
-               _cd(0.99999), _ci(0), _ci(1 if delta_eddington else 0), _ci(stream),
-               *[ptr(out[k].addr + off) if k in out else None for k in OUT_NAMES], _ci(0), *cld_tab)
+               ptr(d_rf.addr + (off if rf_rows else 0)) if d_rf is not None else None, nl_c if rf_rows else 0,
+               0.99999, 0, 1 if delta_eddington else 0, stream,
+               *[ptr(out[k].addr + off) if k in out else None for k in OUT_NAMES], 0, *cld_tab)
         if keep is not None:
             out.setdefault("_cloud_chunks", []).append(keep)
         cont_rows = np.repeat(pl["cia_rows"][None, sl], len(cont_tabs), axis=0) if cont_tabs else None
@@ -1392,10 +1384,10 @@ def compute_opacity_facet_major_ck(atm_f, opacityclass, numg, numt, stream=2, de
     out = {k: (DeviceArray((nfac, (nlayer + 1 if k in ("tau", "tau_og") else nlayer), nwno, ngauss), ctx)
                if (want is None or k in want) else None) for k in OUT_NAMES}
     check(load().picaso_compute_opacity_facet_major_ck_dev(
-        ctx, _ci(nfac), _ci(nlayer), _ci(nwno), _ci(ngauss), ptr(taugas.addr), ptr(tauray.addr),
-        *[ptr(d.addr) if d is not None else None for d in d_cld[:3]], ctypes.c_long(d_cld[3]),
-        ptr(d_rf.addr) if d_rf is not None else None, _ci(rf_rows), _cd(0.99999), _ci(tm),
-        _ci(1 if delta_eddington else 0), _ci(stream),
+        ctx, nfac, nlayer, nwno, ngauss, ptr(taugas.addr), ptr(tauray.addr),
+        *[ptr(d.addr) if d is not None else None for d in d_cld[:3]], d_cld[3],
+        ptr(d_rf.addr) if d_rf is not None else None, rf_rows, 0.99999, tm,
+        1 if delta_eddington else 0, stream,
         *[ptr(out[k].addr) if out[k] is not None else None for k in OUT_NAMES]), ctx)
     out = {k: v for k, v in out.items() if v is not None}
     out["_fm"], out["_ck"] = True, True
@@ -1449,7 +1441,7 @@ def compute_opacity_resident(atmosphere, opacityclass, ngauss=1, stream=2, delta
         t = plane(cld["opd"])
         return fthin_cld * t if do_holes else t             # optics.py:314-315
     on_device = isinstance(cld, CloudTables) and np.size(cld.wno) == nwno and not _options().host_regrid
-    cld_tab = (_ci(0), None, None, None)
+    cld_tab = (0, None, None, None)
     tab_keep = None
     if getattr(atm, "cloud_free", False) and not do_holes:  # no cloud profile: NULL planes read as zero
         d_cld = d_w0 = d_g0 = None
@@ -1461,7 +1453,7 @@ def compute_opacity_resident(atmosphere, opacityclass, ngauss=1, stream=2, delta
             stack = cld.__dict__["_stack"] = np.concatenate([cld.compact[k] for k in ("opd", "w0", "g0")])
         tab_keep = (DeviceArray.from_host(np.ascontiguousarray(cld.in_wno, dtype=np.float64), ctx),
                     DeviceArray.from_host(np.ascontiguousarray(stack, dtype=np.float64), ctx), _wno_device(opa, cld.wno))
-        cld_tab = (_ci(int(np.size(cld.in_wno))), ptr(tab_keep[0].addr), ptr(tab_keep[1].addr), ptr(tab_keep[2].addr))
+        cld_tab = (int(np.size(cld.in_wno)), ptr(tab_keep[0].addr), ptr(tab_keep[1].addr), ptr(tab_keep[2].addr))
         d_cld = d_w0 = d_g0 = None
     elif on_device:     # tables on their own wavenumber grid: interpolated where they are used (same bits)
         d_x = _wno_device(opa, cld.wno)
@@ -1488,15 +1480,15 @@ def compute_opacity_resident(atmosphere, opacityclass, ngauss=1, stream=2, delta
         rows = nlayer + 1 if k in ("tau", "tau_og") else nlayer
         out[k] = DeviceArray((rows,) + gshape, ctx) if (want is None or k in want) else None
     mix_args = (*[ptr(x.addr) if x is not None else None for x in (d_cld, d_w0, d_g0)],
-                ptr(raman_plane.addr) if raman_plane else None, _ci(raman_rows),
-                _cd(raman_const), _ci(tm), _ci(1 if delta_eddington else 0), _ci(stream),
+                ptr(raman_plane.addr) if raman_plane else None, raman_rows,
+                raman_const, tm, 1 if delta_eddington else 0, stream,
                 *[ptr(out[k].addr) if out[k] is not None else None for k in OUT_NAMES])
     if fused:
-        gas_stage(atm, opa, None, None, mix=mix_args + (_ci(1),) + cld_tab)
+        gas_stage(atm, opa, None, None, mix=mix_args + (1,) + cld_tab)
         if tab_keep is not None:
             out["_cloud_tables"] = tab_keep          # the launch is asynchronous: its inputs live as long as its outputs
     else:
-        check(load().picaso_compute_opacity_ck_dev(ctx, _ci(nlayer), _ci(nwno), _ci(ngauss), ptr(taugas.addr),
+        check(load().picaso_compute_opacity_ck_dev(ctx, nlayer, nwno, ngauss, ptr(taugas.addr),
                                                    ptr(tauray.addr), *mix_args), ctx)
     out = {k: v for k, v in out.items() if v is not None}
     if full_output:
@@ -1579,8 +1571,8 @@ def species_opacity(atmosphere, opacityclass, at_tau=None, fthin_cld=None, do_ho
         cum, p_at = DeviceArray((len(names), nlayer + 1, nwno), ctx), DeviceArray((len(names), nwno), ctx)
         plev = f64(np.asarray(atm.level["pressure"], dtype=float) / atm.c.pconv)
     check(load().picaso_opacity_contribution_dev(
-        ctx, _ci(nlayer), _ci(nwno), *gas, ptr(d_cld.addr) if d_cld is not None else None, ptr(plev),
-        _cd(float(at_tau) if at_tau is not None else 0.0), ptr(taus.addr), ptr(cum.addr) if cum is not None else None,
+        ctx, nlayer, nwno, *gas, ptr(d_cld.addr) if d_cld is not None else None, ptr(plev),
+        float(at_tau) if at_tau is not None else 0.0, ptr(taus.addr), ptr(cum.addr) if cum is not None else None,
         ptr(p_at.addr) if p_at is not None else None), ctx)
     taus._inputs = d_cld                 # the launch is asynchronous: its input lives as long as its output
     return names, taus, cum, p_at

@@ -108,9 +108,7 @@ class RegridPlan(Reduction):
 
     def launch(self, ctx, nrows, crows, out_addr):
         d_start = self.device_start(ctx)
-        _lib.check(_lib.load().picaso_mean_regrid_dev(ctx, ctypes.c_long(self.nwno), ctypes.c_int(self.nbins),
-                                                      ctypes.c_void_p(d_start.addr), ctypes.c_int(nrows), crows,
-                                                      ctypes.c_void_p(out_addr)), ctx)
+        _lib.check(_lib.load().picaso_mean_regrid_dev(ctx, self.nwno, self.nbins, d_start.addr, nrows, crows, out_addr), ctx)
         return d_start
 
 
@@ -157,10 +155,6 @@ def resolve(regrid, opa):
     raise Exception("regrid must be a regrid_plan(), {'R': r} or {'newx': array}")
 
 
-def _addr(x):
-    return None if x is None else int(x.addr if isinstance(x, DeviceArray) else x)
-
-
 def spectral_rows(albedo, thermal, transit, stellar, sa, radius_star, planet_radius):
     """The rows of one call in the order of the output dictionary -- ``[(key, op, a, b, c, k1, k2)]`` -- and the keys that
     stay list-valued placeholders, exactly where ``_post_reflected`` / ``_post_thermal`` / ``_post_final`` put them
@@ -204,12 +198,11 @@ class Binned:
         self.plan, self.keys, self.ntail = plan, [r[0] for r in rows], len(tails)
         crow = (_Row * nr)()
         for w, (_, op, a, b, c, k1, k2) in zip(crow, rows):
-            w.op, w.a, w.b, w.c, w.k1, w.k2 = op, _addr(a), _addr(b), _addr(c), float(k1), float(k2)
+            w.op, w.a, w.b, w.c, w.k1, w.k2 = op, _lib.addr(a), _lib.addr(b), _lib.addr(c), float(k1), float(k2)
         self.out = DeviceArray((nr * nb + len(tails),), ctx)
         d_start = plan.launch(ctx, nr, crow, self.out.addr)
         for i, t in enumerate(tails):
-            _lib.check(lib.picaso_memcpy_d2d(ctx, ctypes.c_void_p(self.out.addr + 8 * (nr * nb + i)),
-                                             ctypes.c_void_p(int(t)), ctypes.c_size_t(8)), ctx)
+            _lib.check(lib.picaso_memcpy_d2d(ctx, self.out.addr + 8 * (nr * nb + i), _lib.addr(t), 8), ctx)
         self.pin = self.out.to_host_async(device.PinnedArray(self.out.shape, ctx), ctx)
         self.keep = (keep, rows, d_start)          # the launch is asynchronous: its inputs live until the copy has landed
 

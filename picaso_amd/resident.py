@@ -8,18 +8,9 @@ import ctypes
 
 import numpy as np
 
-from ._lib import check, f64, load, ptr
+from ._lib import addr, check, f64, load, ptr, ptr_array
 from .device import DeviceArray
 from .planes import REFLECTED_PLANES, SH_PLANES
-
-_ci, _cd = ctypes.c_int, ctypes.c_double
-
-
-def _addr(x):
-    if x is None:
-        return None
-    return ptr(x.addr if isinstance(x, DeviceArray) else x)
-
 
 def upload_scene(scene, keys, w_lo=None, w_hi=None, ctx=None):
     """Upload the named (rows, nwno) planes / (nwno) vectors of a host scene dict, optionally only
@@ -43,8 +34,8 @@ def reflected_can_derive(nlevel, nwno, numg, numt, ubar0, ubar1, cos_theta, sing
     ``w0``): ``picaso_reflected_1d_can_derive``."""
     u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
     return bool(load().picaso_reflected_1d_can_derive(
-        _ci(nlevel), ctypes.c_long(nwno), _ci(numg), _ci(numt), ptr(u0), ptr(u1), _cd(cos_theta), _ci(single_phase),
-        _ci(multi_phase), _cd(frac_c), _ci(toon_coefficients), _ci(1 if get_lvl_flux else 0)))
+        nlevel, nwno, numg, numt, ptr(u0), ptr(u1), cos_theta, single_phase,
+        multi_phase, frac_c, toon_coefficients, 1 if get_lvl_flux else 0))
 
 
 def reflected_1d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta,
@@ -59,12 +50,12 @@ def reflected_1d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, uba
     tw = f64(tweight) if tweight is not None else None
     pitch = nwno if plane_pitch is None else plane_pitch
     check(load().picaso_get_reflected_1d_dev(
-        ctx, _ci(nlevel), _ci(nwno), ctypes.c_long(pitch), _ci(numg), _ci(numt),
-        *[_addr(planes.get(k)) for k in REFLECTED_PLANES], _addr(surf_reflect), ptr(u0), ptr(u1),
-        _cd(cos_theta), _addr(F0PI), _ci(single_phase), _ci(multi_phase), _cd(frac_a), _cd(frac_b),
-        _cd(frac_c), _cd(constant_back), _cd(constant_forward), _ci(1), _ci(0),
-        _ci(toon_coefficients), _cd(b_top), _addr(xint_at_top), None, None, None, None,
-        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None, _addr(albedo)),
+        ctx, nlevel, nwno, pitch, numg, numt,
+        *[addr(planes.get(k)) for k in REFLECTED_PLANES], addr(surf_reflect), ptr(u0), ptr(u1),
+        cos_theta, addr(F0PI), single_phase, multi_phase, frac_a, frac_b,
+        frac_c, constant_back, constant_forward, 1, 0,
+        toon_coefficients, b_top, addr(xint_at_top), None, None, None, None,
+        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None, addr(albedo)),
         ctx)
 
 
@@ -79,18 +70,12 @@ def thermal_1d(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb, pleve
     tw = f64(tweight) if tweight is not None else None
     pitch = nwno if plane_pitch is None else plane_pitch
     check(load().picaso_get_thermal_1d_dev(
-        ctx, _ci(nlevel), _addr(wno), _ci(nwno), ctypes.c_long(pitch), _ci(numg), _ci(numt),
-        ptr(tl), _addr(dtau), _addr(w0), _addr(cosb), ptr(pl), ptr(u1), _addr(surf_reflect),
-        _ci(int(hard_surface)), _addr(dwno), _ci(calc_type), _addr(flux_at_top),
-        *[_addr(x) for x in (lvl_fluxes if lvl_fluxes is not None else [None] * 4)],
+        ctx, nlevel, addr(wno), nwno, pitch, numg, numt,
+        ptr(tl), addr(dtau), addr(w0), addr(cosb), ptr(pl), ptr(u1), addr(surf_reflect),
+        int(hard_surface), addr(dwno), calc_type, addr(flux_at_top),
+        *[addr(x) for x in (lvl_fluxes if lvl_fluxes is not None else [None] * 4)],
         ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None,
-        _addr(flux_disk)), ctx)
-
-
-def _ptr_array(items):
-    """Host array of device addresses (``const double *const *`` of the batched entry points)."""
-    arr = (ctypes.c_void_p * len(items))(*[(x.addr if isinstance(x, DeviceArray) else x) for x in items])   # None: NULL
-    return arr, ctypes.cast(arr, ctypes.POINTER(ctypes.POINTER(ctypes.c_double)))
+        addr(flux_disk)), ctx)
 
 
 def _per_spectrum(x, nspec):
@@ -121,20 +106,18 @@ def reflected_1d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     pitch = nwno if plane_pitch is None else plane_pitch
-    keep, cols = [], []
+    cols = []
     for k in REFLECTED_PLANES:
-        a, p = _ptr_array([pl.get(k) for pl in planes])
-        keep.append(a)
-        cols.append(p)
-    a_rs, p_rs = _ptr_array(_per_spectrum(surf_reflect, nspec))
-    a_f0, p_f0 = _ptr_array(_per_spectrum(F0PI, nspec))
-    a_x, p_x = _ptr_array(_per_spectrum(xint_at_top, nspec))
+        cols.append(ptr_array([pl.get(k) for pl in planes]))
+    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
+    p_f0 = ptr_array(_per_spectrum(F0PI, nspec))
+    p_x = ptr_array(_per_spectrum(xint_at_top, nspec))
     fuse = albedo is not None and gw is not None and tw is not None
-    a_al, p_al = _ptr_array(_per_spectrum(albedo, nspec)) if fuse else (None, None)
+    p_al = ptr_array(_per_spectrum(albedo, nspec)) if fuse else None
     check(load().picaso_get_reflected_1d_batch_dev(
-        ctx, _ci(nspec), _ci(nlevel), _ci(nwno), ctypes.c_long(pitch), _ci(numg), _ci(numt), *cols, p_rs,
-        _ci(ngeom), ptr(u0), ptr(u1), ptr(ct), p_f0, _ci(single_phase), _ci(multi_phase), _cd(frac_a), _cd(frac_b),
-        _cd(frac_c), _cd(constant_back), _cd(constant_forward), _ci(toon_coefficients), _cd(b_top), p_x,
+        ctx, nspec, nlevel, nwno, pitch, numg, numt, *cols, p_rs,
+        ngeom, ptr(u0), ptr(u1), ptr(ct), p_f0, single_phase, multi_phase, frac_a, frac_b,
+        frac_c, constant_back, constant_forward, toon_coefficients, b_top, p_x,
         ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
 
 
@@ -153,16 +136,16 @@ def thermal_1d_batch(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb,
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     pitch = nwno if plane_pitch is None else plane_pitch
-    a_dt, p_dt = _ptr_array(list(dtau))
-    a_w0, p_w0 = _ptr_array(_per_spectrum(w0, nspec))
-    a_cb, p_cb = _ptr_array(_per_spectrum(cosb, nspec))
-    a_rs, p_rs = _ptr_array(_per_spectrum(surf_reflect, nspec))
-    a_fx, p_fx = _ptr_array(_per_spectrum(flux_at_top, nspec))
+    p_dt = ptr_array(list(dtau))
+    p_w0 = ptr_array(_per_spectrum(w0, nspec))
+    p_cb = ptr_array(_per_spectrum(cosb, nspec))
+    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
+    p_fx = ptr_array(_per_spectrum(flux_at_top, nspec))
     fuse = flux_disk is not None and gw is not None and tw is not None
-    a_fd, p_fd = _ptr_array(_per_spectrum(flux_disk, nspec)) if fuse else (None, None)
+    p_fd = ptr_array(_per_spectrum(flux_disk, nspec)) if fuse else None
     check(load().picaso_get_thermal_1d_batch_dev(
-        ctx, _ci(nspec), _ci(nlevel), _addr(wno), _ci(nwno), ctypes.c_long(pitch), _ci(numg), _ci(numt), ptr(tl),
-        p_dt, p_w0, p_cb, ptr(pl), _ci(ngeom), ptr(u1), p_rs, _ci(int(hard_surface)), _addr(dwno), _ci(calc_type),
+        ctx, nspec, nlevel, addr(wno), nwno, pitch, numg, numt, ptr(tl),
+        p_dt, p_w0, p_cb, ptr(pl), ngeom, ptr(u1), p_rs, int(hard_surface), addr(dwno), calc_type,
         p_fx, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_fd), ctx)
 
 
@@ -182,13 +165,13 @@ def reflected_1d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect,
     wts = f64(gauss_wts, (ngauss,))
     lv = list(lvl_fluxes) if lvl_fluxes is not None else [None] * 4
     check(load().picaso_get_reflected_1d_ck_dev(
-        ctx, _ci(nlevel), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt),
-        *[_addr(planes[k]) for k in REFLECTED_PLANES], _addr(surf_reflect), ptr(u0), ptr(u1),
-        _cd(cos_theta), _addr(F0PI), _ci(single_phase), _ci(multi_phase), _cd(frac_a), _cd(frac_b),
-        _cd(frac_c), _cd(constant_back), _cd(constant_forward), _ci(int(get_toa_intensity)),
-        _ci(1 if lvl_fluxes is not None else 0), _ci(toon_coefficients), _cd(b_top), ptr(wts),
-        _addr(xint_at_top), *[_addr(x) for x in lv], ptr(gw) if gw is not None else None,
-        ptr(tw) if tw is not None else None, _addr(albedo)), ctx)
+        ctx, nlevel, nwno, ngauss, numg, numt,
+        *[addr(planes[k]) for k in REFLECTED_PLANES], addr(surf_reflect), ptr(u0), ptr(u1),
+        cos_theta, addr(F0PI), single_phase, multi_phase, frac_a, frac_b,
+        frac_c, constant_back, constant_forward, int(get_toa_intensity),
+        1 if lvl_fluxes is not None else 0, toon_coefficients, b_top, ptr(wts),
+        addr(xint_at_top), *[addr(x) for x in lv], ptr(gw) if gw is not None else None,
+        ptr(tw) if tw is not None else None, addr(albedo)), ctx)
 
 
 def thermal_1d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, cosb, plevel, ubar1,
@@ -204,11 +187,11 @@ def thermal_1d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, 
     wts = f64(gauss_wts, (ngauss,))
     lv = list(lvl_fluxes) if lvl_fluxes is not None else [None] * 4
     check(load().picaso_get_thermal_1d_ck_dev(
-        ctx, _ci(nlevel), _addr(wno), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt), ptr(tl),
-        _addr(dtau), _addr(w0), _addr(cosb), ptr(pl), ptr(u1), _addr(surf_reflect),
-        _ci(int(hard_surface)), _addr(dwno), _ci(calc_type), ptr(wts), _addr(flux_at_top),
-        *[_addr(x) for x in lv], ptr(gw) if gw is not None else None,
-        ptr(tw) if tw is not None else None, _addr(flux_disk)), ctx)
+        ctx, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(tl),
+        addr(dtau), addr(w0), addr(cosb), ptr(pl), ptr(u1), addr(surf_reflect),
+        int(hard_surface), addr(dwno), calc_type, ptr(wts), addr(flux_at_top),
+        *[addr(x) for x in lv], ptr(gw) if gw is not None else None,
+        ptr(tw) if tw is not None else None, addr(flux_disk)), ctx)
 
 
 def thermal_1d_ck_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dtau, w0, cosb, plevel, ubar1, surf_reflect,
@@ -221,10 +204,10 @@ def thermal_1d_ck_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dt
     nitem = tl.shape[0]
     tl = f64(tl, (nitem, nlevel))
     check(load().picaso_get_thermal_1d_ck_tbatch_dev(
-        ctx, _ci(nitem), _ci(nlevel), _addr(wno), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt), ptr(tl), _addr(dtau),
-        _addr(w0), _addr(cosb), ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), _addr(surf_reflect),
-        _ci(int(hard_surface)), _addr(dwno), _ci(calc_type), ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight)),
-        ptr(f64(tweight)), _addr(disk4)), ctx)
+        ctx, nitem, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(tl), addr(dtau),
+        addr(w0), addr(cosb), ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), addr(surf_reflect),
+        int(hard_surface), addr(dwno), calc_type, ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight)),
+        ptr(f64(tweight)), addr(disk4)), ctx)
 
 
 def thermal_nets_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dtau, w0, cosb, plevel, ubar1, surf_reflect,
@@ -237,10 +220,10 @@ def thermal_nets_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dta
     nitem = tl.shape[0]
     tl = f64(tl, (nitem, nlevel))
     check(load().picaso_thermal_nets_tbatch_dev(
-        ctx, nitem, nlevel, _addr(wno), nwno, ngauss, numg, numt, ptr(tl), _addr(dtau), _addr(w0), _addr(cosb),
-        ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), _addr(surf_reflect), int(hard_surface), _addr(dwno),
-        ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight, (numg,))), ptr(f64(tweight, (numt,))), _addr(net_layer),
-        _addr(net)), ctx)
+        ctx, nitem, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(tl), addr(dtau), addr(w0), addr(cosb),
+        ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), addr(surf_reflect), int(hard_surface), addr(dwno),
+        ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight, (numg,))), ptr(f64(tweight, (numt,))), addr(net_layer),
+        addr(net)), ctx)
 
 
 def thermal_nets_max_angles():
@@ -253,9 +236,9 @@ def transit_1d_ck(ctx, z, dz, nlevel, nwno, ngauss, rstar, mmw, k_b, amu, player
     ``DTAU_OG`` plane ``(nlevel-1, nwno*ngauss)``, Gauss index fastest; ``rprs2`` (nwno) DeviceArray."""
     wts = f64(gauss_wts, (ngauss,))
     check(load().picaso_get_transit_1d_ck_dev(
-        ctx, ptr(f64(z, (nlevel,))), ptr(f64(dz, (nlevel,))), _ci(nlevel), _ci(nwno), _ci(ngauss),
-        _cd(rstar), ptr(f64(mmw, (nlevel - 1,))), _cd(k_b), _cd(amu), ptr(f64(player)), ptr(f64(tlayer)),
-        ptr(f64(colden, (nlevel - 1,))), _addr(dtau), ptr(wts), _addr(rprs2)), ctx)
+        ctx, ptr(f64(z, (nlevel,))), ptr(f64(dz, (nlevel,))), nlevel, nwno, ngauss,
+        rstar, ptr(f64(mmw, (nlevel - 1,))), k_b, amu, ptr(f64(player)), ptr(f64(tlayer)),
+        ptr(f64(colden, (nlevel - 1,))), addr(dtau), ptr(wts), addr(rprs2)), ctx)
 
 
 def mix_all_gases_gasesfly(ctx, kappas, mixes, gauss_pts, gauss_wts, indices, out=None):
@@ -275,53 +258,46 @@ def mix_all_gases_gasesfly(ctx, kappas, mixes, gauss_pts, gauss_wts, indices, ou
         raise Exception("mix_all_gases_gasesfly: indices must be (4, nlayer) and mixes (ngas, nlayer)")
     if out is None:
         out = DeviceArray((nlayer, 4, nwno, nk), ctx)
-    ptrs = (ctypes.c_void_p * len(kappas))(*[k.addr for k in kappas])
     check(load().picaso_mix_all_gases_gasesfly_dev(
-        ctx, _ci(len(kappas)), ctypes.cast(ptrs, ctypes.POINTER(ctypes.POINTER(ctypes.c_double))), _ci(npres),
-        _ci(ntemp), _ci(nwno), _ci(nk), ptr(mx), ptr(f64(gauss_pts, (nk,))), ptr(f64(gauss_wts, (nk,))),
-        idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _ci(nlayer), _addr(out)), ctx)
+        ctx, len(kappas), ptr_array(kappas), npres, ntemp, nwno, nk, ptr(mx), ptr(f64(gauss_pts, (nk,))), ptr(f64(gauss_wts, (nk,))),
+        idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), nlayer, addr(out)), ctx)
     return out
 
 
 def axpby(ctx, a, x, b, y, out):
     """``out = a*x + b*y`` on DeviceArrays of equal size (patchy-cloud blend, justdoit.py:300-305)."""
     n = int(np.prod(x.shape))
-    check(load().picaso_axpby_dev(ctx, ctypes.c_size_t(n), _cd(a), _addr(x), _cd(b), _addr(y),
-                                  _addr(out)), ctx)
+    check(load().picaso_axpby_dev(ctx, n, a, addr(x), b, addr(y), addr(out)), ctx)
 
 
 def trapz(ctx, n, d, y, out, mult=None, reverse=False):
     """``np.trapezoid(y * mult, x)`` with ``d = diff(x)`` resident, summed in numpy's own pairwise order (same bits);
     ``reverse``: over ``y[::-1]`` (and ``mult[::-1]``).  ``out``: a DeviceArray / address of one double
     (``picaso_trapz_dev``; the Bond-albedo and effective-temperature integrals of justdoit.py:552-599)."""
-    check(load().picaso_trapz_dev(ctx, ctypes.c_long(int(n)), _addr(d), _addr(y), _addr(mult), _ci(1 if reverse else 0),
-                                  _addr(out)), ctx)
+    check(load().picaso_trapz_dev(ctx, int(n), addr(d), addr(y), addr(mult), 1 if reverse else 0, addr(out)), ctx)
 
 
 def compress_disco(ctx, nwno, cos_theta, xint_at_top, gweight, tweight, F0PI, albedo):
     """``disco.compress_disco`` on DeviceArrays (reference disco.py:117-149)."""
     gw, tw = f64(gweight), f64(tweight)
-    check(load().picaso_compress_disco_dev(ctx, _ci(nwno), _cd(cos_theta), _addr(xint_at_top), ptr(gw),
-                                           _ci(gw.size), ptr(tw), _ci(tw.size), _addr(F0PI),
-                                           _addr(albedo)), ctx)
+    check(load().picaso_compress_disco_dev(ctx, nwno, cos_theta, addr(xint_at_top), ptr(gw), gw.size, ptr(tw), tw.size,
+                                           addr(F0PI), addr(albedo)), ctx)
 
 
 def compress_thermal(ctx, ninner, flux_at_top, gweight, tweight, flux):
     """``disco.compress_thermal`` on DeviceArrays (reference disco.py:151-181)."""
     gw, tw = f64(gweight), f64(tweight)
-    check(load().picaso_compress_thermal_dev(ctx, ctypes.c_size_t(ninner), _addr(flux_at_top), ptr(gw),
-                                             _ci(gw.size), ptr(tw), _ci(tw.size), _addr(flux)), ctx)
+    check(load().picaso_compress_thermal_dev(ctx, ninner, addr(flux_at_top), ptr(gw), gw.size, ptr(tw), tw.size, addr(flux)),
+          ctx)
 
 
 def reflected_SH_can_derive(stream, w_single_form=0, w_multi_form=0, psingle_form=0, w_single_rayleigh=1,
                             w_multi_rayleigh=1, psingle_rayleigh=1, frac_c=2.0, single_form=0, flx=0):
     """True when ``reflected_SH`` with these options takes a cloud-free atmosphere as ``dtau`` and ``w0`` only
     (``picaso_reflected_SH_can_derive``)."""
-    lib = load()
-    lib.picaso_reflected_SH_can_derive.argtypes = [ctypes.c_int] * 7 + [ctypes.c_double] + [ctypes.c_int] * 2
-    return bool(lib.picaso_reflected_SH_can_derive(int(stream), int(w_single_form), int(w_multi_form), int(psingle_form),
-                                                   int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh),
-                                                   float(frac_c), int(single_form), int(flx)))
+    return bool(load().picaso_reflected_SH_can_derive(int(stream), int(w_single_form), int(w_multi_form), int(psingle_form),
+                                                      int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh),
+                                                      float(frac_c), int(single_form), int(flx)))
 
 
 def reflected_SH_can_derive_levels(nlevel, plane_pitch, stream, w_single_form=0, w_multi_form=0, psingle_form=0,
@@ -330,10 +306,7 @@ def reflected_SH_can_derive_levels(nlevel, plane_pitch, stream, w_single_form=0,
     """True when ``reflected_SH`` / ``reflected_SH_ck`` with these options may be handed ``None`` for the level planes
     ``tau`` and ``tau_og`` (both): the launch then carries the beam exponentials as running products of the layers'
     (``picaso_reflected_SH_can_derive_levels``)."""
-    lib = load()
-    lib.picaso_reflected_SH_can_derive_levels.argtypes = ([ctypes.c_int, ctypes.c_long] + [ctypes.c_int] * 7
-                                                          + [ctypes.c_double] + [ctypes.c_int] * 2)
-    return bool(lib.picaso_reflected_SH_can_derive_levels(
+    return bool(load().picaso_reflected_SH_can_derive_levels(
         int(nlevel), int(plane_pitch), int(stream), int(w_single_form), int(w_multi_form), int(psingle_form),
         int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh), float(frac_c), int(single_form), int(flx)))
 
@@ -353,14 +326,14 @@ def reflected_SH(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, uba
     tw = f64(tweight) if tweight is not None else None
     pitch = nwno if plane_pitch is None else plane_pitch
     check(load().picaso_get_reflected_SH_top_dev(
-        ctx, _ci(nlevel), _ci(nwno), ctypes.c_long(pitch), _ci(numg), _ci(numt),
-        *[_addr(planes.get(k)) for k in SH_PLANES], _addr(surf_reflect), ptr(u0), ptr(u1), _cd(cos_theta),
-        _addr(F0PI), _ci(int(w_single_form)), _ci(int(w_multi_form)), _ci(int(psingle_form)),
-        _ci(int(w_single_rayleigh)), _ci(int(w_multi_rayleigh)), _ci(int(psingle_rayleigh)), _cd(frac_a),
-        _cd(frac_b), _cd(frac_c), _cd(constant_back), _cd(constant_forward), _ci(int(stream)), _cd(b_top),
-        _ci(0), _ci(int(single_form)), _ci(1 if compound_f_deltaM else 0), _ci(int(cloud_free_above)),
-        _addr(xint_at_top), None,
-        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None, _addr(albedo)), ctx)
+        ctx, nlevel, nwno, pitch, numg, numt,
+        *[addr(planes.get(k)) for k in SH_PLANES], addr(surf_reflect), ptr(u0), ptr(u1), cos_theta,
+        addr(F0PI), int(w_single_form), int(w_multi_form), int(psingle_form),
+        int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh), frac_a,
+        frac_b, frac_c, constant_back, constant_forward, int(stream), b_top,
+        0, int(single_form), 1 if compound_f_deltaM else 0, int(cloud_free_above),
+        addr(xint_at_top), None,
+        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None, addr(albedo)), ctx)
 
 
 def reflected_SH_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -380,22 +353,20 @@ def reflected_SH_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     pitch = nwno if plane_pitch is None else plane_pitch
-    keep, cols = [], []
+    cols = []
     for k in SH_PLANES:
-        a, p = _ptr_array([pl[k] for pl in planes])
-        keep.append(a)
-        cols.append(p)
-    a_rs, p_rs = _ptr_array(_per_spectrum(surf_reflect, nspec))
-    a_f0, p_f0 = _ptr_array(_per_spectrum(F0PI, nspec))
-    a_x, p_x = _ptr_array(_per_spectrum(xint_at_top, nspec))
+        cols.append(ptr_array([pl[k] for pl in planes]))
+    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
+    p_f0 = ptr_array(_per_spectrum(F0PI, nspec))
+    p_x = ptr_array(_per_spectrum(xint_at_top, nspec))
     fuse = albedo is not None and gw is not None and tw is not None
-    a_al, p_al = _ptr_array(_per_spectrum(albedo, nspec)) if fuse else (None, None)
+    p_al = ptr_array(_per_spectrum(albedo, nspec)) if fuse else None
     check(load().picaso_get_reflected_SH_batch_dev(
-        ctx, _ci(nspec), _ci(nlevel), _ci(nwno), ctypes.c_long(pitch), _ci(numg), _ci(numt), *cols, p_rs, _ci(ngeom),
-        ptr(u0), ptr(u1), ptr(ct), p_f0, _ci(int(w_single_form)), _ci(int(w_multi_form)), _ci(int(psingle_form)),
-        _ci(int(w_single_rayleigh)), _ci(int(w_multi_rayleigh)), _ci(int(psingle_rayleigh)), _cd(frac_a), _cd(frac_b),
-        _cd(frac_c), _cd(constant_back), _cd(constant_forward), _ci(int(stream)), _cd(b_top), _ci(int(single_form)),
-        _ci(1 if compound_f_deltaM else 0), p_x, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
+        ctx, nspec, nlevel, nwno, pitch, numg, numt, *cols, p_rs, ngeom,
+        ptr(u0), ptr(u1), ptr(ct), p_f0, int(w_single_form), int(w_multi_form), int(psingle_form),
+        int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh), frac_a, frac_b,
+        frac_c, constant_back, constant_forward, int(stream), b_top, int(single_form),
+        1 if compound_f_deltaM else 0, p_x, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
 
 
 def reflected_3d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -408,11 +379,11 @@ def reflected_3d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, uba
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_reflected_3d_dev(
-        ctx, _ci(nlevel), _ci(nwno), _ci(numg), _ci(numt), *[_addr(planes.get(k)) for k in REFLECTED_PLANES],
-        _addr(surf_reflect), ptr(u0), ptr(u1), _cd(cos_theta), _addr(F0PI), _ci(single_phase),
-        _ci(multi_phase), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back),
-        _cd(constant_forward), _addr(xint_at_top), ptr(gw) if gw is not None else None,
-        ptr(tw) if tw is not None else None, _addr(albedo)), ctx)
+        ctx, nlevel, nwno, numg, numt, *[addr(planes.get(k)) for k in REFLECTED_PLANES],
+        addr(surf_reflect), ptr(u0), ptr(u1), cos_theta, addr(F0PI), single_phase,
+        multi_phase, frac_a, frac_b, frac_c, constant_back,
+        constant_forward, addr(xint_at_top), ptr(gw) if gw is not None else None,
+        ptr(tw) if tw is not None else None, addr(albedo)), ctx)
 
 
 def thermal_3d(ctx, nlevel, wno, nwno, numg, numt, tlevel_3d, dtau_3d, w0_3d, cosb_3d, plevel_3d, ubar1,
@@ -424,10 +395,10 @@ def thermal_3d(ctx, nlevel, wno, nwno, numg, numt, tlevel_3d, dtau_3d, w0_3d, co
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_thermal_3d_dev(
-        ctx, _ci(nlevel), _addr(wno), _ci(nwno), _ci(numg), _ci(numt), ptr(tl), _addr(dtau_3d),
-        _addr(w0_3d), _addr(cosb_3d), ptr(pl), ptr(u1), _addr(surf_reflect), _ci(int(hard_surface)),
-        _addr(int_at_top), ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None,
-        _addr(flux_disk)), ctx)
+        ctx, nlevel, addr(wno), nwno, numg, numt, ptr(tl), addr(dtau_3d),
+        addr(w0_3d), addr(cosb_3d), ptr(pl), ptr(u1), addr(surf_reflect), int(hard_surface),
+        addr(int_at_top), ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None,
+        addr(flux_disk)), ctx)
 
 
 def reflected_3d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -445,23 +416,21 @@ def reflected_3d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar
     ct = f64(np.zeros(nspec) + np.asarray(cos_theta, dtype=np.float64), (nspec,))
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
-    keep, cols = [], []
+    cols = []
     for k in REFLECTED_PLANES:
         if planes[0].get(k) is None:
             cols.append(None)
             continue
-        a, p = _ptr_array([pl[k] for pl in planes])
-        keep.append(a)
-        cols.append(p)
-    a_rs, p_rs = _ptr_array(_per_spectrum(surf_reflect, nspec))
-    a_f0, p_f0 = _ptr_array(_per_spectrum(F0PI, nspec))
-    a_x, p_x = _ptr_array(_per_spectrum(xint_at_top, nspec))
+        cols.append(ptr_array([pl[k] for pl in planes]))
+    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
+    p_f0 = ptr_array(_per_spectrum(F0PI, nspec))
+    p_x = ptr_array(_per_spectrum(xint_at_top, nspec))
     fuse = albedo is not None and gw is not None and tw is not None
-    a_al, p_al = _ptr_array(_per_spectrum(albedo, nspec)) if fuse else (None, None)
+    p_al = ptr_array(_per_spectrum(albedo, nspec)) if fuse else None
     check(load().picaso_get_reflected_3d_batch_dev(
-        ctx, _ci(nspec), _ci(nlevel), _ci(nwno), _ci(numg), _ci(numt), *cols, p_rs, ptr(u0), ptr(u1), ptr(ct), p_f0,
-        _ci(single_phase), _ci(multi_phase), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back),
-        _cd(constant_forward), p_x, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
+        ctx, nspec, nlevel, nwno, numg, numt, *cols, p_rs, ptr(u0), ptr(u1), ptr(ct), p_f0,
+        single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back,
+        constant_forward, p_x, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
 
 
 def reflected_3d_fm_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -523,16 +492,16 @@ def thermal_3d_batch(ctx, nlevel, wno, nwno, numg, numt, tlevel_3d, dtau_3d, w0_
     tl, pl = f64(tlevel_3d, (nspec, nlevel, numg, numt)), f64(plevel_3d, (nspec, nlevel, numg, numt))
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
-    a_dt, p_dt = _ptr_array(list(dtau_3d))
-    a_w0, p_w0 = _ptr_array(list(w0_3d))
-    a_cb, p_cb = _ptr_array(list(cosb_3d)) if cosb_3d is not None else (None, None)
-    a_rs, p_rs = _ptr_array(_per_spectrum(surf_reflect, nspec))
-    a_fx, p_fx = _ptr_array(_per_spectrum(int_at_top, nspec))
+    p_dt = ptr_array(list(dtau_3d))
+    p_w0 = ptr_array(list(w0_3d))
+    p_cb = ptr_array(list(cosb_3d)) if cosb_3d is not None else None
+    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
+    p_fx = ptr_array(_per_spectrum(int_at_top, nspec))
     fuse = flux_disk is not None and gw is not None and tw is not None
-    a_fd, p_fd = _ptr_array(_per_spectrum(flux_disk, nspec)) if fuse else (None, None)
+    p_fd = ptr_array(_per_spectrum(flux_disk, nspec)) if fuse else None
     check(load().picaso_get_thermal_3d_batch_dev(
-        ctx, _ci(nspec), _ci(nlevel), _addr(wno), _ci(nwno), _ci(numg), _ci(numt), ptr(tl), p_dt, p_w0, p_cb, ptr(pl),
-        ptr(u1), p_rs, _ci(int(hard_surface)), p_fx, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_fd), ctx)
+        ctx, nspec, nlevel, addr(wno), nwno, numg, numt, ptr(tl), p_dt, p_w0, p_cb, ptr(pl),
+        ptr(u1), p_rs, int(hard_surface), p_fx, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_fd), ctx)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -553,13 +522,13 @@ def reflected_SH_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect,
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_reflected_SH_ck_dev(
-        ctx, _ci(nlevel), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt), *[_addr(planes.get(k)) for k in SH_PLANES],
-        _addr(surf_reflect), ptr(u0), ptr(u1), _cd(cos_theta), _addr(F0PI), _ci(int(w_single_form)),
-        _ci(int(w_multi_form)), _ci(int(psingle_form)), _ci(int(w_single_rayleigh)), _ci(int(w_multi_rayleigh)),
-        _ci(int(psingle_rayleigh)), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back), _cd(constant_forward),
-        _ci(int(stream)), _cd(b_top), _ci(int(single_form)), _ci(1 if compound_f_deltaM else 0),
-        _ci(int(cloud_free_above)), ptr(f64(gauss_wts, (ngauss,))), _addr(xint_at_top), _opt(gw), _opt(tw),
-        _addr(albedo)), ctx)
+        ctx, nlevel, nwno, ngauss, numg, numt, *[addr(planes.get(k)) for k in SH_PLANES],
+        addr(surf_reflect), ptr(u0), ptr(u1), cos_theta, addr(F0PI), int(w_single_form),
+        int(w_multi_form), int(psingle_form), int(w_single_rayleigh), int(w_multi_rayleigh),
+        int(psingle_rayleigh), frac_a, frac_b, frac_c, constant_back, constant_forward,
+        int(stream), b_top, int(single_form), 1 if compound_f_deltaM else 0,
+        int(cloud_free_above), ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), _opt(gw), _opt(tw),
+        addr(albedo)), ctx)
 
 
 def thermal_SH_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, cosb_og, plevel, ubar1, surf_reflect,
@@ -571,10 +540,10 @@ def thermal_SH_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, 
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_thermal_SH_ck_dev(
-        ctx, _ci(nlevel), _addr(wno), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt), ptr(f64(tlevel, (nlevel,))),
-        _addr(dtau), _addr(tau), _addr(w0), _addr(cosb_og), ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))),
-        _addr(surf_reflect), _ci(int(stream)), _ci(int(hard_surface)), _ci(1 if cosb_differs_from_cosb_og else 0),
-        ptr(f64(gauss_wts, (ngauss,))), _addr(xint_at_top), _opt(gw), _opt(tw), _addr(flux_disk)), ctx)
+        ctx, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(f64(tlevel, (nlevel,))),
+        addr(dtau), addr(tau), addr(w0), addr(cosb_og), ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))),
+        addr(surf_reflect), int(stream), int(hard_surface), 1 if cosb_differs_from_cosb_og else 0,
+        ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), _opt(gw), _opt(tw), addr(flux_disk)), ctx)
 
 
 def reflected_3d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -586,10 +555,10 @@ def reflected_3d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect,
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_reflected_3d_ck_dev(
-        ctx, _ci(nlevel), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt), *[_addr(planes.get(k)) for k in REFLECTED_PLANES],
-        _addr(surf_reflect), ptr(f64(ubar0, (numg, numt))), ptr(f64(ubar1, (numg, numt))), _cd(cos_theta), _addr(F0PI),
-        _ci(single_phase), _ci(multi_phase), _cd(frac_a), _cd(frac_b), _cd(frac_c), _cd(constant_back),
-        _cd(constant_forward), ptr(f64(gauss_wts, (ngauss,))), _addr(xint_at_top), _opt(gw), _opt(tw), _addr(albedo)), ctx)
+        ctx, nlevel, nwno, ngauss, numg, numt, *[addr(planes.get(k)) for k in REFLECTED_PLANES],
+        addr(surf_reflect), ptr(f64(ubar0, (numg, numt))), ptr(f64(ubar1, (numg, numt))), cos_theta, addr(F0PI),
+        single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back,
+        constant_forward, ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), _opt(gw), _opt(tw), addr(albedo)), ctx)
 
 
 def thermal_3d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel_3d, dtau, w0, cosb, plevel_3d, ubar1, surf_reflect,
@@ -600,8 +569,8 @@ def thermal_3d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel_3d, dtau, w
     gw = f64(gweight) if gweight is not None else None
     tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_thermal_3d_ck_dev(
-        ctx, _ci(nlevel), _addr(wno), _ci(nwno), _ci(ngauss), _ci(numg), _ci(numt),
-        ptr(f64(tlevel_3d, (nlevel, numg, numt))), _addr(dtau), _addr(w0), _addr(cosb),
-        ptr(f64(plevel_3d, (nlevel, numg, numt))), ptr(f64(ubar1, (numg, numt))), _addr(surf_reflect),
-        _ci(int(hard_surface)), ptr(f64(gauss_wts, (ngauss,))), _addr(int_at_top), _opt(gw), _opt(tw),
-        _addr(flux_disk)), ctx)
+        ctx, nlevel, addr(wno), nwno, ngauss, numg, numt,
+        ptr(f64(tlevel_3d, (nlevel, numg, numt))), addr(dtau), addr(w0), addr(cosb),
+        ptr(f64(plevel_3d, (nlevel, numg, numt))), ptr(f64(ubar1, (numg, numt))), addr(surf_reflect),
+        int(hard_surface), ptr(f64(gauss_wts, (ngauss,))), addr(int_at_top), _opt(gw), _opt(tw),
+        addr(flux_disk)), ctx)

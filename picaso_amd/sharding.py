@@ -251,10 +251,6 @@ class HostGroup:
 # ---------------------------------------------------------------------------------------------
 # device collectives: RCCL inside the library
 # ---------------------------------------------------------------------------------------------
-def _addr(x):
-    return ctypes.c_void_p(int(x.addr if hasattr(x, "addr") else x))
-
-
 class Comm:
     """RCCL communicator of the library bound to one context (one GPU).  ``Comm.from_launcher`` is the
     one-process-per-GPU form; ``Comm.init_all`` the single-process form."""
@@ -275,7 +271,7 @@ class Comm:
         if uid is None or len(uid) != COMM_ID_BYTES:
             raise _lib.PicasoHipError("picaso_amd.sharding: bad RCCL id at the rendezvous")
         h = ctypes.c_void_p()
-        _lib.check(lib.picaso_comm_init_rank(ctx, ctypes.c_int(group.world), ctypes.c_int(group.rank),
+        _lib.check(lib.picaso_comm_init_rank(ctx, group.world, group.rank,
                                              ctypes.c_char_p(uid), ctypes.byref(h)), ctx)
         return cls(h, ctx, group.rank, group.world, group)
 
@@ -285,18 +281,17 @@ class Comm:
         n = len(ctxs)
         arr = (ctypes.c_void_p * n)(*[c.value if hasattr(c, "value") else c for c in ctxs])
         out = (ctypes.c_void_p * n)()
-        _lib.check(lib.picaso_comm_init_all(ctypes.c_int(n), arr, out), ctxs[0])
+        _lib.check(lib.picaso_comm_init_all(n, arr, out), ctxs[0])
         return [cls(ctypes.c_void_p(out[i]), ctxs[i], i, n) for i in range(n)]
 
     def all_gather(self, send, recv, count):
         """recv[r*count + i] = rank r's send[i] (device buffers; asynchronous on the context's stream)"""
-        _lib.check(_lib.load().picaso_all_gather_dev(self.handle, _addr(send), _addr(recv),
-                                                     ctypes.c_size_t(int(count))), self.ctx)
+        _lib.check(_lib.load().picaso_all_gather_dev(self.handle, _lib.addr(send), _lib.addr(recv), int(count)), self.ctx)
 
     def all_gatherv(self, send, recv, counts, displs):
         c = (ctypes.c_size_t * self.world)(*[int(x) for x in counts])
         d = (ctypes.c_size_t * self.world)(*[int(x) for x in displs])
-        _lib.check(_lib.load().picaso_all_gatherv_dev(self.handle, _addr(send), _addr(recv), c, d), self.ctx)
+        _lib.check(_lib.load().picaso_all_gatherv_dev(self.handle, _lib.addr(send), _lib.addr(recv), c, d), self.ctx)
 
     def all_gather_spectrum(self, local, full, nwno):
         """Per-rank shard (this rank's block of ``shard_bounds(nwno, world)``, device) -> ``full`` (nwno,
@@ -319,8 +314,7 @@ class Comm:
         else:
             c = (ctypes.c_size_t * self.world)(*counts)
             d = (ctypes.c_size_t * self.world)(*[lo for lo, _ in bounds])
-        _lib.check(_lib.load().picaso_all_gather_async_dev(self.handle, _addr(local), _addr(full),
-                                                           ctypes.c_size_t(counts[0]), c, d, ctypes.c_int(slot)),
+        _lib.check(_lib.load().picaso_all_gather_async_dev(self.handle, _lib.addr(local), _lib.addr(full), counts[0], c, d, slot),
                    self.ctx)
 
     def all_gather_spectra_async(self, locals_, fulls, nwno, slot):
@@ -335,12 +329,11 @@ class Comm:
         n = len(locals_)
         snd = (ctypes.c_void_p * n)(*[int(x.addr) for x in locals_])
         rcv = (ctypes.c_void_p * n)(*[int(x.addr) for x in fulls])
-        _lib.check(_lib.load().picaso_all_gather_multi_async_dev(self.handle, ctypes.c_int(n), snd, rcv,
-                                                                 ctypes.c_size_t(counts[0]), c, d, ctypes.c_int(slot)),
+        _lib.check(_lib.load().picaso_all_gather_multi_async_dev(self.handle, n, snd, rcv, counts[0], c, d, slot),
                    self.ctx)
 
     def wait_slot(self, slot=-1):
-        _lib.check(_lib.load().picaso_comm_wait_slot(self.handle, ctypes.c_int(slot)), self.ctx)
+        _lib.check(_lib.load().picaso_comm_wait_slot(self.handle, slot), self.ctx)
 
     def max(self, value):
         v = ctypes.c_double(float(value))
@@ -374,7 +367,7 @@ class DeviceGroup:
         n = len(self.ctxs)
         arr = (ctypes.c_void_p * n)(*[c.value for c in self.ctxs])
         out = (ctypes.c_void_p * n)()
-        _lib.check(lib.picaso_comm_init_all(ctypes.c_int(n), arr, out), self.ctxs[0])
+        _lib.check(lib.picaso_comm_init_all(n, arr, out), self.ctxs[0])
         self._handles = (ctypes.c_void_p * n)(*[out[i] for i in range(n)])
         self.world = n
 
@@ -390,23 +383,22 @@ class DeviceGroup:
             d = (ctypes.c_size_t * n)(*[lo for lo, _ in bounds])
         snd = (ctypes.c_void_p * n)(*[int(x.addr) for x in locals_])
         rcv = (ctypes.c_void_p * n)(*[int(x.addr) for x in fulls])
-        _lib.check(_lib.load().picaso_all_gather_group_dev(ctypes.c_int(n), self._handles, snd, rcv,
-                                                           ctypes.c_size_t(counts[0]), c, d), self.ctxs[0])
+        _lib.check(_lib.load().picaso_all_gather_group_dev(n, self._handles, snd, rcv, counts[0], c, d), self.ctxs[0])
 
     def max(self, values):
         n = self.world
         v = (ctypes.c_double * n)(*[float(x) for x in values])
-        _lib.check(_lib.load().picaso_comm_group_max(ctypes.c_int(n), self._handles, v), self.ctxs[0])
+        _lib.check(_lib.load().picaso_comm_group_max(n, self._handles, v), self.ctxs[0])
         return [v[i] for i in range(n)]
 
     def barrier(self):
-        _lib.check(_lib.load().picaso_comm_group_barrier(ctypes.c_int(self.world), self._handles), self.ctxs[0])
+        _lib.check(_lib.load().picaso_comm_group_barrier(self.world, self._handles), self.ctxs[0])
 
     def destroy(self):
         if self._handles is not None:
             for h in self._handles:
                 if h:
-                    _lib.load().picaso_comm_destroy(ctypes.c_void_p(h))
+                    _lib.load().picaso_comm_destroy(h)
             self._handles = None
 
 

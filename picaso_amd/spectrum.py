@@ -887,18 +887,16 @@ def _postprocess(raw, wno, stellar, sa, radius_star, planet_radius, opa=None):
 def _reflected(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta, F0PI, single_phase,
                multi_phase, frac_a, frac_b, frac_c, constant_back, constant_forward,
                toon_coefficients, b_top, xint, lvl, gweight, tweight, albedo):
-    import ctypes
     from ._lib import check, f64, load, ptr
     u0, u1 = f64(ubar0, (ng, nt)), f64(ubar1, (ng, nt))
     gw, tw = f64(gweight), f64(tweight)
-    ci, cd = ctypes.c_int, ctypes.c_double
     check(load().picaso_get_reflected_1d_dev(
-        ctx, ci(nlevel), ci(nwno), ctypes.c_long(nwno), ci(ng), ci(nt),
+        ctx, nlevel, nwno, nwno, ng, nt,
         *[ptr(planes[k].addr) if planes.get(k) is not None else None for k in resident.REFLECTED_PLANES],
         ptr(rs.addr), ptr(u0), ptr(u1),
-        cd(cos_theta), ptr(F0PI.addr), ci(single_phase), ci(multi_phase), cd(frac_a), cd(frac_b),
-        cd(frac_c), cd(constant_back), cd(constant_forward), ci(1), ci(1 if lvl else 0),
-        ci(toon_coefficients), cd(b_top), ptr(xint.addr),
+        cos_theta, ptr(F0PI.addr), single_phase, multi_phase, frac_a, frac_b,
+        frac_c, constant_back, constant_forward, 1, 1 if lvl else 0,
+        toon_coefficients, b_top, ptr(xint.addr),
         *[ptr(l.addr) if lvl else None for l in (lvl or [None] * 4)], ptr(gw), ptr(tw),
         ptr(albedo.addr) if albedo is not None else None), ctx)
 
@@ -906,19 +904,17 @@ def _reflected(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta, F
 def _reflected_sh(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta, F0PI, sh, frac_a,
                   frac_b, frac_c, constant_back, constant_forward, stream, b_top, xint, gweight,
                   tweight, albedo, flux=None, cloud_free_above=0):
-    import ctypes
     from ._lib import check, f64, load, ptr
     u0, u1 = f64(ubar0, (ng, nt)), f64(ubar1, (ng, nt))
     gw, tw = f64(gweight), f64(tweight)
-    ci, cd = ctypes.c_int, ctypes.c_double
     check(load().picaso_get_reflected_SH_top_dev(
-        ctx, ci(nlevel), ci(nwno), ctypes.c_long(nwno), ci(ng), ci(nt),
+        ctx, nlevel, nwno, nwno, ng, nt,
         *[ptr(planes[k].addr) if planes.get(k) is not None else None for k in resident.SH_PLANES], ptr(rs.addr), ptr(u0),
-        ptr(u1), cd(cos_theta),
-        ptr(F0PI.addr), ci(sh["w_single_form"]), ci(sh["w_multi_form"]), ci(sh["psingle_form"]),
-        ci(sh["w_single_rayleigh"]), ci(sh["w_multi_rayleigh"]), ci(sh["psingle_rayleigh"]),
-        cd(frac_a), cd(frac_b), cd(frac_c), cd(constant_back), cd(constant_forward), ci(stream),
-        cd(b_top), ci(1 if flux is not None else 0), ci(sh["single_form"]), ci(1), ci(int(cloud_free_above)),
+        ptr(u1), cos_theta,
+        ptr(F0PI.addr), sh["w_single_form"], sh["w_multi_form"], sh["psingle_form"],
+        sh["w_single_rayleigh"], sh["w_multi_rayleigh"], sh["psingle_rayleigh"],
+        frac_a, frac_b, frac_c, constant_back, constant_forward, stream,
+        b_top, 1 if flux is not None else 0, sh["single_form"], 1, int(cloud_free_above),
         ptr(xint.addr),
         ptr(flux.addr) if flux is not None else None, ptr(gw), ptr(tw),
         ptr(albedo.addr)), ctx)
@@ -926,12 +922,10 @@ def _reflected_sh(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta
 
 def _thermal_sh(ctx, nlevel, d_wno, nwno, ng, nt, tlevel, planes, plevel, ubar1, rs, stream,
                 hard_surface, delta_eddington, flux, gweight, tweight, disk):
-    import ctypes
     from ._lib import check, f64, load, ptr
     u1 = f64(ubar1, (ng, nt))
     gw, tw = f64(gweight), f64(tweight)
     tl, pl = f64(tlevel), f64(plevel)
-    ci = ctypes.c_int
     # ff = 0 if np.array_equal(cosb, cosb_og) else cosb_og**stream (fluxes.py:3072-3075).  Without delta-Eddington
     # scaling the two planes are the same array; with it they are equal only where cosb_og**stream vanishes against
     # cosb_og, and there `cosb_og**stream` IS the reference's 0 (exactly for a cloud-free atmosphere, to < 1e-21 in the
@@ -939,8 +933,8 @@ def _thermal_sh(ctx, nlevel, d_wno, nwno, ng, nt, tlevel, planes, plevel, ubar1,
     # f_deltaM per call used to sit here: 9.5 of the 11.7 ms of an SH4 spectrum at 1e5 wavelengths).
     differs = 1 if delta_eddington else 0
     check(load().picaso_get_thermal_SH_dev(
-        ctx, ci(nlevel), ptr(d_wno.addr), ci(nwno), ctypes.c_long(nwno), ci(ng), ci(nt), ptr(tl),
+        ctx, nlevel, ptr(d_wno.addr), nwno, nwno, ng, nt, ptr(tl),
         ptr(planes["dtau"].addr), ptr(planes["tau"].addr) if planes.get("tau") is not None else None,   # tau: never read
         ptr(planes["w0"].addr),
-        ptr(planes["cosb_og"].addr), ptr(pl), ptr(u1), ptr(rs.addr), ci(stream), ci(int(hard_surface)),
-        ci(differs), ci(0), ptr(flux.addr), ptr(gw), ptr(tw), ptr(disk.addr)), ctx)
+        ptr(planes["cosb_og"].addr), ptr(pl), ptr(u1), ptr(rs.addr), stream, int(hard_surface),
+        differs, 0, ptr(flux.addr), ptr(gw), ptr(tw), ptr(disk.addr)), ctx)
