@@ -271,20 +271,21 @@ def get_reflected_SH(nlevel, nwno, numg, numt, dtau, tau, w0, cosb, ftau_cld, ft
 
 def get_thermal_SH(nlevel, wno, nwno, numg, numt, tlevel, dtau, tau, w0, cosb, dtau_og, tau_og,
                    w0_og, w0_no_raman, cosb_og, plevel, ubar1, surf_reflect, stream, hard_surface,
-                   flx=0):
-    """Signature of reference ``fluxes.get_thermal_SH`` (fluxes.py:2979-2981)."""
+                   flx=0, x80=False):
+    """Signature of reference ``fluxes.get_thermal_SH`` (fluxes.py:2979-2981); ``x80`` as in ``get_reflected_SH``."""
     if flx:
         raise Exception("oracle: flx=1 is broken in the reference (fluxes.py:3102) and not restated")
-    arrs = [_a(p) for p in (wno, tlevel, dtau, tau, w0, cosb, cosb_og, plevel, ubar1)]
-    sr = _per_wave(surf_reflect, nwno)
-    xint = np.zeros((numg, numt, nwno))
-    ci = ctypes.c_int
+    P = _X80_SH if x80 else _F64
+    arrs = [P.a(p) for p in (wno, tlevel, dtau, tau, w0, cosb, cosb_og, plevel, ubar1)]
+    sr = P.per_wave(surf_reflect, nwno)
+    xint = P.zeros((numg, numt, nwno))
+    ci, p = ctypes.c_int, P.p
     wno_, tl, dt, ta, w0_, cb, cbo, pl, u1 = arrs
-    rc = lib().orc_thermal_SH(ci(nlevel), _p(wno_), ci(nwno), ci(numg), ci(numt), _p(tl), _p(dt),
-                              _p(ta), _p(w0_), _p(cb), _p(cbo), _p(pl), _p(u1), _p(sr), ci(stream),
-                              ci(int(hard_surface)), _p(xint))
+    rc = P.lib().orc_thermal_SH(ci(nlevel), p(wno_), ci(nwno), ci(numg), ci(numt), p(tl), p(dt),
+                                p(ta), p(w0_), p(cb), p(cbo), p(pl), p(u1), p(sr), ci(stream),
+                                ci(int(hard_surface)), p(xint))
     _check(rc, "thermal_SH")
-    return xint, np.zeros((numg, numt, stream * nlevel, nwno))
+    return P.out(xint), np.zeros((numg, numt, stream * nlevel, nwno))
 
 
 def get_transit_1d(z, dz, nlevel, nwno, rstar, mmw, k_b, amu, player, tlayer, colden, DTAU):

@@ -263,3 +263,85 @@ def test_3d_inside_the_correlated_k_loop(fam, oracle):
         key = "%s/therm_hs%d" % (fam, hs)
         assert rel_err(acc, r[key + "/flux_at_top"]) < TOL, key
         assert rel_err(oracle.compress_thermal(nwno, acc, geo["gweight"], geo["tweight"]), r[key + "/thermal"]) < TOL
+
+
+# ---- get_thermal_SH in x87 extended precision: the arbiter of the GPU fuzz and edge tests (tests/sh_thermal_cases.py) ----
+@pytest.mark.parametrize("path", FILES_SH, ids=scene_id)
+def test_thermal_SH_extended_precision_build(path, oracle):
+    """oracle.get_thermal_SH(x80=True) (sh_oracle_x80.c) against the reference's own results, at the fp64 oracle's
+    tolerance."""
+    g = Golden(path)
+    nlevel, nwno = g.inp("tau").shape
+    assert g.cases("thermsh")
+    for case in g.cases("thermsh"):
+        stream, hs = int(case[1]), int(case[-1])
+        rs = np.zeros(nwno) + g.inp("surf_reflect")
+        xint, _ = oracle.get_thermal_SH(nlevel, g.inp("wno"), nwno, g.geo("numg"), g.geo("numt"), g.inp("tlevel"),
+                                        g.inp("dtau"), g.inp("tau"), g.inp("w0"), g.inp("cosb"), g.inp("dtau_og"),
+                                        g.inp("tau_og"), g.inp("w0_og"), g.inp("w0_no_raman"), g.inp("cosb_og"),
+                                        g.inp("plevel"), g.geo("ubar1"), rs, stream, hs, x80=True)
+        assert xint.dtype == np.float64
+        assert rel_err(xint, g["thermsh/%s/xint" % case]) < 1e-10, case
+
+
+def _sh_thermal_x87_distance(oracle, args, floor=None):
+    xo, _ = oracle.get_thermal_SH(*args)
+    xx, _ = oracle.get_thermal_SH(*args, x80=True)
+    assert np.isfinite(xo).all() and np.isfinite(xx).all()
+    return rel_err(xo, xx, 1e-4 * np.abs(xo).max() if floor is None else floor(xo)), xo
+
+
+@pytest.mark.parametrize("block", range(4))
+def test_thermal_SH_draws_are_well_conditioned(block, oracle):
+    """Every committed draw of the GPU fuzz (offset 0): the fp64 oracle is finite and within 1e-9 of its x87 build (observed
+    at most 5.8e-12), which is what makes the GPU test's 1e-9 against the fp64 oracle meaningful.  And the draws reach
+    what they are there for: three or more per block beyond one launch's 16 angles, one of them a short second launch."""
+    import sh_thermal_cases as cases
+    nang = []
+    for it in range(cases.NDRAW):
+        args, tag = cases.draw(block, it, 0)
+        e, _ = _sh_thermal_x87_distance(oracle, args)
+        assert e < 1e-9, (tag, e)
+        nang.append(args[3] * args[4])
+    assert sum(n > cases.SH_MAX_ANG for n in nang) >= 3 and any(n in (17, 18) for n in nang)
+
+
+def test_thermal_SH_draws_cover_the_options():
+    """Over the four blocks: one layer, one wavelength, last blocks of 255 / 257, both streams, surfaces, delta settings,
+    scalar and per-wavelength reflectivity, and layers thick enough for the kernel's clipped exponentials.
+    A snapshot of what the recipe gives at offset 0: an edit of the recipe in tests/sh_thermal_cases.py that turns this red
+    has changed the committed draws, not broken anything -- check that the new ones still cover the list and adjust."""
+    import sh_thermal_cases as cases
+    draws = [cases.draw(b, it, 0) for b in range(cases.NBLOCK) for it in range(cases.NDRAW)]
+    tags = np.array([t for _, t in draws])
+    assert {1, 2, 90} <= set(tags[:, 2]) and {1, 5, 255, 257} <= set(tags[:, 3])
+    for col in (6, 7, 8, 9):
+        assert len(set(tags[:, col])) == 2, col
+    assert {np.ndim(a[17]) for a, _ in draws} == {0, 1}
+    assert any(t[2] == 1 and t[4] * t[5] > cases.SH_MAX_ANG for t in tags)
+    n_clip = sum(cases.reaches_clip(a) for a, _ in draws)
+    assert 8 <= n_clip < len(draws)
+
+
+@pytest.mark.parametrize("stream", [2, 4])
+def test_thermal_SH_edge_inputs_are_well_conditioned(stream, oracle):
+    """The hand-made inputs of tests/test_sh_thermal_gpu.py.  Planck overflow: the oracle is finite and non-zero in every
+    column and 5e-13 from x87, each wavelength on its own scale.  An eigenvalue at (1/u1)(1 + d): the reference's own
+    loss of digits grows like 1/d -- observed 8e-13, 2e-10 and 1.8e-8 (SH2), 3e-13, 7e-11 and 6.5e-9 (SH4) -- and stays
+    a factor 50 below the 1e-6 contract (the bound asserted: 20 eps / d); sh_close allows the kernel 30 x that distance from x87, at most its cap of 3e-7."""
+    import sh_thermal_cases as cases
+    for hard in (0, 1):
+        args = cases.planck_overflow(stream, hard)
+        e, xo = _sh_thermal_x87_distance(oracle, args, floor=lambda x: 1e-4 * np.abs(x).max(axis=(0, 1)))
+        assert (xo != 0).all() and e < 1e-11, (hard, e)
+    todo = cases.resonance_cases(stream)
+    assert {(r, d) for r, _, d, _ in todo} == {(stream // 2 - 1, d) for d in cases.RESONANCE_D}
+    for root, k, d, args in todo:
+        assert 0.0 < args[8][cases.RESONANCE_LAYER, 0] < 1.0
+        u = args[16].ravel()[k]
+        lam = cases._sh_lambdas(args[8][cases.RESONANCE_LAYER, 0], stream)[root]
+        assert abs(lam * u - 1.0 - d) < 1e-3 * d, (root, k, d)
+        e, _ = _sh_thermal_x87_distance(oracle, args)
+        # 1/u1 - lambda = d / u1 is a difference of two rounded numbers: eps / d of relative error, times the share of the
+        # resonant term in the result (observed 0.5 - 8 x eps / d)
+        assert e < 20 * np.finfo(float).eps / d + 1e-12, (root, k, d, e)

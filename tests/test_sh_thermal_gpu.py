@@ -108,3 +108,145 @@ def test_full_size_blocks_are_the_whole(hip, oracle):
     sub = {k: (np.ascontiguousarray(v[..., idx]) if np.ndim(v) and np.shape(v)[-1] == nwno else v) for k, v in sc.items()}
     want, _ = oracle.get_thermal_SH(*_args(sub, nlayer, idx.size, ng, nt, u1, 0.0, 4, 0))
     assert rel_err(whole[..., idx], want) < 1e-9
+
+
+# ---- branches of k_sh_thermal and launch_sh_thermal at the smallest shapes that reach them ----
+# (inputs shared with the CPU side: tests/sh_thermal_cases.py; judged through helpers.sh_close like the fuzz draws)
+def _close(oracle, got, want, args, tag, floor=None):
+    import sh_thermal_cases as cases
+    from helpers import sh_close
+    assert np.isfinite(got).all(), tag
+    return sh_close(lambda: oracle.get_thermal_SH(*args, x80=True)[0], got, want, cases.w0max(args), tag, floor=floor)
+
+
+@pytest.mark.parametrize("stream", [2, 4])
+@pytest.mark.parametrize("ng,nt", [(6, 3), (5, 4), (6, 4)])
+def test_more_angles_than_one_launch_holds(hip, oracle, monkeypatch, stream, ng, nt):
+    """18, 20 and 24 disk angles: launch_sh_thermal loops over launches of at most 16 angles, refills the angle table and
+    offsets the output each time round (18 angles: a second launch of 2 or 3; five angles per lane: a last chunk of 3)."""
+    import sh_thermal_cases as cases
+    monkeypatch.delenv("PICASO_AMD_SH_THERMAL_PER_ANGLE", raising=False)
+    monkeypatch.delenv("PICASO_AMD_SHT_ANGLES", raising=False)
+    nlayer, nwno = 3, 65
+    sc = _scene(nlayer, nwno, 610 + ng * nt, stream)
+    u1, _, _ = cases.geometry(ng, nt, 0.7)
+    rs = 0.3 * np.random.default_rng(ng * nt).random(nwno)
+    args = cases.sh_args(sc, ng, nt, u1, rs, stream, 0)
+    got, _ = hip.fluxes.get_thermal_SH(*args)
+    want, _ = oracle.get_thermal_SH(*args)
+    _close(oracle, got, want, args, (stream, ng, nt))
+    for m in (1, 2, 3, 4, 5):
+        monkeypatch.setenv("PICASO_AMD_SHT_ANGLES", str(m))
+        alt, _ = hip.fluxes.get_thermal_SH(*args)
+        assert np.array_equal(alt, got), m
+    monkeypatch.delenv("PICASO_AMD_SHT_ANGLES")
+    if ng * nt == 24:
+        # an angle's result depends on nothing but its own u1: first launch, the last angle of it, the last of all
+        flat = u1.ravel()
+        for k in (3, 15, 16, 23):
+            one = list(args)
+            one[3], one[4], one[16] = 1, 1, np.array([[flat[k]]])
+            alone, _ = hip.fluxes.get_thermal_SH(*one)
+            assert np.array_equal(alone[0, 0], got.reshape(24, nwno)[k]), k
+
+
+@pytest.mark.parametrize("stream", [2, 4])
+def test_plane_pitch_wider_than_the_call(hip, oracle, monkeypatch, stream):
+    """picaso_get_thermal_SH_dev on columns 117..181 of planes 300 wide (plane_pitch = 300, nwno = 65): the same bits as the
+    host entry on the sliced arrays, nothing written outside the result, and flux_disk = compress_thermal of it.  The
+    per-angle kernel (PICASO_AMD_SH_THERMAL_PER_ANGLE) through the same call: its own host-entry bits as well."""
+    import sh_thermal_cases as cases
+    from picaso_amd import _lib
+    from picaso_amd._lib import check, f64, load, ptr
+    from picaso_amd.device import DeviceArray
+    nlayer, wide, nwno, c0, ng, nt = 3, 300, 65, 117, 6, 3
+    sc = _scene(nlayer, wide, 640, stream)
+    u1, gw, tw = cases.geometry(ng, nt, 0.7)
+    rs = 0.3 * np.random.default_rng(5).random(wide)
+    cut = {k: (np.ascontiguousarray(v[..., c0:c0 + nwno]) if np.ndim(v) and np.shape(v)[-1] == wide else v)
+           for k, v in sc.items()}
+    args = cases.sh_args(cut, ng, nt, u1, rs[c0:c0 + nwno], stream, 1)
+    monkeypatch.delenv("PICASO_AMD_SH_THERMAL_PER_ANGLE", raising=False)
+    monkeypatch.delenv("PICASO_AMD_SHT_ANGLES", raising=False)
+    want, _ = hip.fluxes.get_thermal_SH(*args)
+    _close(oracle, want, oracle.get_thermal_SH(*args)[0], args, stream)
+    monkeypatch.setenv("PICASO_AMD_SH_THERMAL_PER_ANGLE", "1")
+    want_old, _ = hip.fluxes.get_thermal_SH(*args)
+    monkeypatch.delenv("PICASO_AMD_SH_THERMAL_PER_ANGLE")
+    assert rel_err(want, want_old) < 1e-11
+    ctx = _lib.context()
+    d = {k: DeviceArray.from_host(sc[k], ctx) for k in ("dtau", "w0", "cosb_og", "wno")}
+    d_rs = DeviceArray.from_host(rs, ctx)
+    mark = -7.0
+    d_x = DeviceArray.from_host(np.full((ng * nt, wide), mark), ctx)
+    d_disk = DeviceArray.from_host(np.full(wide, mark), ctx)
+    off = 8 * c0
+    tl, pl = f64(sc["tlevel"]), f64(sc["plevel"])
+    check(load().picaso_get_thermal_SH_dev(
+        ctx, nlayer + 1, ptr(d["wno"].addr + off), nwno, wide, ng, nt, ptr(tl), ptr(d["dtau"].addr + off),
+        None, ptr(d["w0"].addr + off), ptr(d["cosb_og"].addr + off), ptr(pl), ptr(u1), ptr(d_rs.addr + off),
+        stream, 1, 1, 0, ptr(d_x.addr + off), ptr(gw), ptr(tw), ptr(d_disk.addr + off)), ctx)
+    x = d_x.to_host().ravel()
+    got = x[c0:c0 + ng * nt * nwno].reshape(ng, nt, nwno)               # the result is (angles, nwno), contiguous
+    assert np.array_equal(got, want)
+    assert np.all(x[:c0] == mark) and np.all(x[c0 + ng * nt * nwno:] == mark)
+    disk = d_disk.to_host()
+    assert np.all(disk[:c0] == mark) and np.all(disk[c0 + nwno:] == mark)
+    assert rel_err(disk[c0:c0 + nwno], hip.disco.compress_thermal(nwno, got, gw, tw)) < 1e-13
+    monkeypatch.setenv("PICASO_AMD_SH_THERMAL_PER_ANGLE", "1")
+    d_y = DeviceArray.from_host(np.full((ng * nt, wide), mark), ctx)
+    check(load().picaso_get_thermal_SH_dev(
+        ctx, nlayer + 1, ptr(d["wno"].addr + off), nwno, wide, ng, nt, ptr(tl), ptr(d["dtau"].addr + off),
+        None, ptr(d["w0"].addr + off), ptr(d["cosb_og"].addr + off), ptr(pl), ptr(u1), ptr(d_rs.addr + off),
+        stream, 1, 1, 0, ptr(d_y.addr + off), None, None, None), ctx)
+    y = d_y.to_host().ravel()
+    assert np.array_equal(y[c0:c0 + ng * nt * nwno].reshape(ng, nt, nwno), want_old)
+    assert np.all(y[:c0] == mark) and np.all(y[c0 + ng * nt * nwno:] == mark)
+
+
+@pytest.mark.parametrize("stream", [2, 4])
+@pytest.mark.parametrize("nlayer", [1, 2])
+@pytest.mark.parametrize("ng,nt", [(5, 1), (5, 4)])
+def test_one_column(hip, oracle, stream, nlayer, ng, nt):
+    """nwno = 1 (one lane of one wave) with one layer -- top and bottom boundary in the same layer -- and two."""
+    import sh_thermal_cases as cases
+    sc = _scene(nlayer, 1, 660 + nlayer, stream)
+    u1, _, _ = cases.geometry(ng, nt, 0.4)
+    for hard in (0, 1):
+        args = cases.sh_args(sc, ng, nt, u1, 0.2, stream, hard)
+        got, _ = hip.fluxes.get_thermal_SH(*args)
+        _close(oracle, got, oracle.get_thermal_SH(*args)[0], args, (stream, nlayer, ng, nt, hard))
+
+
+@pytest.mark.parametrize("stream", [2, 4])
+@pytest.mark.parametrize("hard", [0, 1])
+def test_planck_overflow_is_zero_not_nan(hip, oracle, stream, hard):
+    """Levels down to 25 K at up to 33 000 cm^-1: exp(hc wno / kT) overflows and the reference's Planck function is
+    1 / (inf - 1) = 0 there; the kernel must give the same finite column.  Every wavelength against its own scale (1e-4 of
+    the column's maximum over the angles): the columns span hundreds of decades and a global floor would hide the blue
+    ones.  The scene also has layers with (1/u1 + lambda) dtau > 35 (the `!noclip` branch)."""
+    import sh_thermal_cases as cases
+    args = cases.planck_overflow(stream, hard)
+    assert oracle.blackbody([25.0], [1.0 / 33000.0])[0, 0] == 0.0 and cases.reaches_clip(args)
+    got, _ = hip.fluxes.get_thermal_SH(*args)
+    want, _ = oracle.get_thermal_SH(*args)
+    assert np.isfinite(want).all() and (want != 0).all()
+    _close(oracle, got, want, args, (stream, hard), floor=1e-4 * np.abs(want).max(axis=(0, 1)))
+
+
+@pytest.mark.parametrize("stream", [2, 4])
+def test_eigenvalue_next_to_an_inverse_angle(hip, oracle, stream):
+    """lambda = (1/u1)(1 + d), d = 1e-3, 1e-5, 1e-7, in one layer: the source-function integral's (1 - exp(-(1/u1 - lambda)
+    dtau)) / (1/u1 - lambda) with the kernel's exponential a product of two rounded ones.  The reference loses digits there
+    too (fp64 oracle vs x87 up to 2e-8 at d = 1e-7, tests/test_oracle_golden.py), which sh_close allows the kernel 30 x of,
+    up to its cap.  SH4's larger eigenvalue lies in (1.97, 2.94) and meets none of the table's 1/u1.
+    Observed, kernel vs x87 / fp64 oracle vs x87: d = 1e-3 at most 4.4e-12 / 7.6e-13; d = 1e-5 at most 3.2e-10 / 2.0e-10;
+    d = 1e-7 SH2 1.62e-8 / 1.62e-8, 1.75e-8 / 1.75e-8 (the two table angles whose allowance reaches the 3e-7 cap: the
+    kernel is as far from x87 as the reference and 4.6e-9 and 6.7e-9 from the reference), 4.6e-9 / 4.6e-9, 4.9e-10 / 1.3e-10;
+    d = 1e-7 SH4 6.5e-9 / 6.5e-9 and 5.3e-9 / 5.3e-9.  The kernel loses no more digits here than the reference does."""
+    import sh_thermal_cases as cases
+    todo = cases.resonance_cases(stream)
+    assert {d for _, _, d, _ in todo} == set(cases.RESONANCE_D)
+    for root, k, d, args in todo:
+        got, _ = hip.fluxes.get_thermal_SH(*args)
+        _close(oracle, got, oracle.get_thermal_SH(*args)[0], args, (stream, root, k, d))
