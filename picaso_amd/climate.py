@@ -708,3 +708,331 @@ def t_start(nofczns, nstr, convergence_criteria, rfaci, rfacv, tidal, Atmosphere
     if verbose:
         print("Iterations exceeded it_max ! sorry ")
     return finish(True)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The driver around t_start (reference climate.py: get_kzz :331-493, update_kzz :56-124, profile :2926-3249, find_strat
+# :2542-2839, run_chemeq_climate_workflow :217-326).  Host code on nlevel-sized vectors; the device work is what
+# calculate_atm, t_start and get_fluxes do.  profile and find_strat reach those three through this module's names, so a
+# test may replace them.
+# ---------------------------------------------------------------------------------------------------------------------
+SIGMA_SB = 0.56687e-4                                            # erg cm^-2 s^-1 K^-4, the reference's value
+
+
+def get_kzz(grav, tidal, flux_net_ir_layer, flux_plus_ir_attop, Adiabat, nstr, Atmosphere, moist=False):
+    """Eddy diffusion coefficient (cm^2/s) at every level from mixing-length theory (reference climate.py:331-493).
+
+    The convective heat flux of a layer is the emergent flux minus the radiative net flux there, built from the bottom
+    layer (which carries everything) upward and never falling faster than ``1/3 p_i / p_{i+1}`` per layer; it is rescaled so
+    that the bottom layer carries ``|tidal[0]|`` and floored at the flux of 5 % of the target effective temperature.  The
+    mixing length is the scale height times ``max(0.1, min(1, dtdp / grad_ad))``.  ``kz[-1]`` is appended for the last level.
+    Inside the radiative zone(s) (``nstr[0]:nstr[1]`` and, when ``nstr[3] != 0``, ``nstr[3]:nstr[4]``) every value is then
+    replaced by the mean over two scale heights either side, clipped to the zone.
+
+    Kept from the reference: the altitude ``z`` is filled up to index ``nlevel - 3`` only, its last element stays 0 (and
+    takes part in the nearest-altitude searches); the averages of the lower zone are taken after the upper zone has been
+    overwritten; ``grav`` is in m/s^2.  ``moist=True`` is not implemented."""
+    if moist:
+        raise NotImplementedError("get_kzz: the moist adiabat (moist=True) is not implemented")
+    pressure, temp = f64(Atmosphere.p_level), f64(Atmosphere.t_level)
+    mmw, dtdp = f64(Atmosphere.mmw_layer), f64(Atmosphere.dtdp)
+    tidal, net_layer = f64(tidal), f64(flux_net_ir_layer)
+    nstr = [int(x) for x in nstr]
+    nlevel = len(temp)
+    nz = nlevel - 1
+    grav_cgs = grav * 1e2
+    r_atmos = 8.3143e7 / mmw
+    p_layer = np.sqrt(pressure[1:] * 1e6 * (pressure[:-1] * 1e6))
+    t_layer = 0.5 * (temp[1:] + temp[:-1])
+    p_layer_bar = np.sqrt(pressure[1:] * pressure[:-1])
+    f_sum = np.sum(f64(flux_plus_ir_attop))
+    target_teff = (abs(tidal[0]) / SIGMA_SB) ** 0.25
+    flx_min = SIGMA_SB * ((target_teff * 0.05) ** 4)
+
+    chf = np.zeros(tidal.shape)
+    chf[nz - 1] = f_sum                                           # the bottom layer: all convective
+    for iz in range(nz - 2, -1, -1):
+        chf[iz] = max(f_sum - net_layer[iz], (1.0 / 3.0) * p_layer[iz] / p_layer[iz + 1] * chf[iz + 1])
+    ratio = abs(tidal[0]) / chf[nz - 1]
+    chf[:nz] = np.maximum(chf[:nz] * ratio, flx_min)
+
+    grad_x = np.array([did_grad_cp(t, p, Adiabat)[0] for t, p in zip(t_layer, p_layer_bar)])     # per layer, as the reference
+    lapse_ratio = np.minimum(1.0, dtdp / grad_x)
+    rho_atmos = p_layer / (r_atmos * t_layer)
+    c_p = (7.0 / 2.0) * r_atmos
+    scale_h = r_atmos * t_layer / grav_cgs
+    mixl = np.maximum(0.1, lapse_ratio) * scale_h
+    kz = (1.0 / 3.0) * scale_h * (mixl / scale_h) ** (4.0 / 3.0) * ((r_atmos * chf[:-1]) / (rho_atmos * c_p)) ** (1.0 / 3.0)
+    kz = np.append(kz, kz[-1])
+
+    dz = scale_h[1:] * np.log((p_layer[:-1] / 1e6) / (p_layer[1:] / 1e6))
+    z = np.zeros(nlevel - 1)
+    z[:nlevel - 2] = np.cumsum(dz[:nlevel - 2])                  # z[nlevel-2] stays 0, as in the reference
+
+    def zone_means(lo, hi):
+        out = []
+        for i in range(lo, hi):
+            above = abs(i - int(np.abs(z - (z[i] + 2 * scale_h[i])).argmin()))
+            below = abs(i - int(np.abs(z - (z[i] - 2 * scale_h[i])).argmin()))
+            out.append(np.mean(kz[max(lo, i - above):min(hi, i + below)]))
+        return np.array(out)
+    kz[nstr[0]:nstr[1]] = zone_means(nstr[0], nstr[1])
+    if nstr[3] != 0:
+        kz[nstr[3]:nstr[4]] = zone_means(nstr[3], nstr[4])
+    return kz
+
+
+def update_kzz(grav, tidal, AdiabatBundle, nstr, Atmosphere, OpacityWEd=None, OpacityNoEd=None, ScatteringPhase=None,
+               Disco=None, Opagrid=None, F0PI=None, OpacityWEd_clear=None, OpacityNoEd_clear=None, flux_net_ir_layer=None,
+               flux_plus_ir_attop=None, moist=False, do_holes=False, fhole=None, verbose=True, _fluxes=None):
+    """``get_kzz`` with the fluxes handed in, or -- when neither ``flux_net_ir_layer`` nor ``flux_plus_ir_attop`` is given --
+    with those of one thermal ``get_fluxes`` call at ``Atmosphere`` (reference climate.py:56-124).  ``_fluxes``: as in
+    ``t_start``; its first callable stands in for ``get_fluxes``."""
+    if verbose:
+        print("update_kzz: mixing-length kzz profile")
+    if flux_plus_ir_attop is None and flux_net_ir_layer is None:
+        single = get_fluxes if _fluxes is None else _fluxes[0]
+        holes = {}
+        if do_holes:
+            holes = dict(do_holes=True, fhole=fhole, hole_OpacityWEd=OpacityWEd_clear, hole_OpacityNoEd=OpacityNoEd_clear)
+        out = single(Atmosphere, OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Opagrid, F0PI, False, True, **holes)
+        flux_net_ir_layer, flux_plus_ir_attop = out[4], out[6][0, :]
+    return get_kzz(grav, tidal, flux_net_ir_layer, flux_plus_ir_attop, AdiabatBundle, nstr, Atmosphere, moist=moist)
+
+
+def profile(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid,
+            CloudParameters, save_profile, all_profiles, all_opd, convergence_criteria, final, flux_net_ir_layer=None,
+            flux_plus_ir_attop=None, first_call_ever=False, verbose=True, moist=None, save_kzz=False,
+            self_consistent_kzz=True, diseq=False, all_kzz=[], _fluxes=None):
+    """One outer step of the climate solve with the convective zones ``nstr`` held fixed (reference ``climate.profile``,
+    climate.py:2926-3249; same positional arguments): lay the adiabat through every convective zone of ``temp``, refresh the
+    chemistry and the opacities, then call ``t_start`` up to ``convergence_criteria.itmx`` times, each from the profile the
+    last one returned, until the mean temperature change falls below ``convt``.  Returns the reference's list
+    ``[conv_flag, pressure, temp, dtdp, CloudParameters, cld_out, flux_net_ir_layer, flux_net_v_layer, flux_plus_ir_attop,
+    all_profiles, all_opd, all_kzz]`` (``cld_out`` is NaN: no clouds).
+
+    Kept from the reference:
+    * ``egp_stepmax`` (the small fixed step cap of ``t_start``) when the coldest level of the ENTRY profile is <= 250 K;
+    * the adiabat uses ``did_grad_cp`` at the level above and ``sqrt(p[j-1] p[j])``, level by level;
+    * ``bundle.add_pt``, ``bundle.premix_atmosphere`` and ``calculate_atm`` run once before the loop; inside it only the
+      chemistry of the bundle follows the new profile -- cloud-free equilibrium chemistry needs no refresh, so every
+      ``t_start`` call of one ``profile`` call sees the SAME opacity planes (the DeviceArrays of ``calculate_atm``, handed on
+      as they are);
+    * each ``t_start`` call starts from the temperatures the previous one returned (the reference's ``t_start`` works in
+      ``Atmosphere.t_level`` itself), and ``Atmosphere.dtdp`` stays that of the entry profile, which is what ``get_kzz`` reads;
+    * the kzz profile is computed only with ``save_kzz`` (before the loop from a fresh thermal ``get_fluxes`` call, inside it
+      from the fluxes ``t_start`` returned) and is booked in ``bundle.inputs['atmosphere']['kzz']['sc_kzz']``;
+    * converged means ``iii > 0 and sum|dT| / (1.5 nlevel) < convt`` (the cloud term ``taudif = 0 < 0.1`` always holds); the
+      reference then sets ``itmx`` of its local copy of the criteria, which nobody reads;
+    * with ``CloudParameters.cloudy`` false ``do_holes`` is false whatever ``bundle.inputs['clouds']`` says, so the hole
+      planes ``calculate_atm`` may return are not used;
+    * ``flux_net_ir_layer`` / ``flux_plus_ir_attop`` / ``first_call_ever`` are accepted and not read.
+
+    ``temp`` is not modified (the reference lays the adiabat into the caller's array; its callers use the returned one).
+    Not implemented, each a ``NotImplementedError``: ``CloudParameters.cloudy`` (virga), ``diseq=True`` (the quench
+    chemistry), ``moist=True`` (the moist adiabat), a photochem ``chem_method``.
+
+    ``_fluxes``: handed to every ``t_start`` call and to ``update_kzz``."""
+    if "photochem" in str(bundle.inputs["approx"].get("chem_method", None)):
+        raise NotImplementedError("profile: chem_method='photochem' needs the photochem package, which is not part of this "
+                                  "package")
+    if diseq:
+        raise NotImplementedError("profile: diseq=True needs the quench chemistry (update_quench_levels, "
+                                  "adjust_quench_chemistry), which is not implemented")
+    if CloudParameters.cloudy:
+        raise NotImplementedError("profile: CloudParameters.cloudy needs virga (update_clouds), which is not implemented")
+    if moist:
+        raise NotImplementedError("profile: the moist adiabat (moist=True) is not implemented")
+    F0PI = opacityclass.relative_flux
+    convt, itmx = convergence_criteria.convt, int(convergence_criteria.itmx)
+    do_holes, fhole = False, None                                 # climate.py:3020-3022: no clouds, no holes
+    temp, pressure = np.array(temp, dtype=np.float64), f64(pressure)
+    nstr = [int(x) for x in nstr]
+    egp_stepmax = bool(np.min(temp) <= 250)
+    conv_flag = 0
+
+    for nb in range(0, 3 * int(nofczns), 3):                      # the adiabat through every convective zone
+        for j1 in range(nstr[nb + 1] + 1, nstr[nb + 2] + 2):
+            grad_x, _ = did_grad_cp(temp[j1 - 1], np.sqrt(pressure[j1 - 1] * pressure[j1]), AdiabatBundle)
+            temp[j1] = np.exp(np.log(temp[j1 - 1]) + grad_x * (np.log(pressure[j1]) - np.log(pressure[j1 - 1])))
+    temp_old = temp.copy()
+    if save_profile == 1:
+        all_profiles = np.append(all_profiles, temp_old)
+
+    bundle.add_pt(temp, pressure)
+    bundle.premix_atmosphere(opa=opacityclass, quench_levels=None, verbose=verbose)
+    OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Atmosphere, _ = calculate_atm(bundle, opacityclass)
+    if save_kzz:
+        kz = update_kzz(grav, tidal, AdiabatBundle, nstr, Atmosphere, OpacityWEd=OpacityWEd, OpacityNoEd=OpacityNoEd,
+                        ScatteringPhase=ScatteringPhase, Disco=Disco, Opagrid=Opagrid, F0PI=F0PI, moist=False,
+                        do_holes=do_holes, fhole=fhole, verbose=verbose, _fluxes=_fluxes)
+        bundle.inputs["atmosphere"].setdefault("kzz", {})["sc_kzz"] = kz
+        all_kzz = np.append(all_kzz, kz)
+
+    RETURNS = None
+    dtdp = Atmosphere.dtdp
+    for iii in range(itmx):
+        Atmosphere = Atmosphere._replace(t_level=temp)            # the reference's t_start left its result in this array
+        temp, dtdp, all_profiles, flux_net_ir_layer, flux_net_v_layer, flux_plus_ir_attop = t_start(
+            nofczns, nstr, convergence_criteria, rfaci, rfacv, tidal, Atmosphere, OpacityWEd, OpacityNoEd, ScatteringPhase,
+            Disco, Opagrid, AdiabatBundle, F0PI, save_profile, all_profiles, verbose=verbose, moist=False,
+            egp_stepmax=egp_stepmax, _fluxes=_fluxes)
+        bundle.add_pt(temp, pressure)
+        bundle.premix_atmosphere(opa=opacityclass, quench_levels=None, verbose=verbose)
+        if save_kzz:
+            kz = update_kzz(grav, tidal, AdiabatBundle, nstr, Atmosphere._replace(t_level=temp),
+                            flux_net_ir_layer=flux_net_ir_layer, flux_plus_ir_attop=flux_plus_ir_attop, moist=False,
+                            do_holes=do_holes, fhole=fhole, verbose=verbose)
+            all_kzz = np.append(all_kzz, kz)
+        RETURNS = [conv_flag, pressure, temp, dtdp, CloudParameters, np.nan, flux_net_ir_layer, flux_net_v_layer,
+                   flux_plus_ir_attop, all_profiles, all_opd, all_kzz]
+        ert = np.sum(np.abs(temp - temp_old)) / (float(len(temp)) * 1.5)
+        temp_old = temp.copy()
+        if iii > 0 and ert < convt:
+            if verbose:
+                print("profile: converged at outer iteration", iii)
+            RETURNS[0] = 1
+            return RETURNS
+        if verbose:
+            print("profile: outer iteration", iii, "coldest level", min(temp))
+    if RETURNS is None:
+        raise ValueError("profile: convergence_criteria.itmx must be at least 1")
+    if verbose:
+        print("profile: itmx reached without convergence")
+    return RETURNS
+
+
+def find_strat(bundle, nofczns, nstr, temp, pressure, dtdp, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid,
+               CloudParameters, save_profile, all_profiles, all_opd, flux_net_ir_layer, flux_plus_ir_attop, verbose=1,
+               moist=None, save_kzz=False, self_consistent_kzz=True, diseq=False, all_kzz=[], _fluxes=None):
+    """Find the convective zones (reference ``climate.find_strat``, climate.py:2542-2839; same positional arguments): grow
+    the convective zone upward while the layer above it is steeper than 0.98 of the adiabat, look for a detached second
+    zone, grow both, merge them when they meet, calling ``profile`` with the criteria ``(8, 5, 5.0, 3.0, 7.0)`` after every
+    change and with ``(10, 6, 2.0, 2.0, 3.5)`` and ``final=True`` at the end.  Returns ``profile_flag, pressure, temp, dtdp,
+    nstr, flux_net_ir_layer, flux_net_v_layer, flux_plus_ir_attop, chem, cld_out, all_profiles, all_opd, all_kzz``.
+
+    ``nstr`` must be a list (or array) of six integers and IS MODIFIED IN PLACE, as the reference does; the returned one is
+    the same object.
+
+    Kept from the reference:
+    * ``subad = 0.98``, and the search for a second zone ends at level ``ifirst = 9``;
+    * the adiabatic gradient ``grad_x`` is computed ONCE, at the entry profile, and never refreshed, while ``dtdp`` follows
+      every ``profile`` call (the ``dtdp`` argument itself is replaced at once by that of ``calculate_atm``);
+    * the first zone grows by 2 levels while ``dtdp / grad_x > 1.8``, else by 1; it may not pass level 5
+      (later, in the grow phase, level 3): ``ValueError``;
+    * the second zone is put at the FIRST layer from below, ``nstr[1] - 1`` down to 9, whose excess over the adiabat is at
+      least 2 % (the loop breaks there; it does not look for the largest);
+    * ``nstr[3] = i_max``, not ``i_max + 1``; ``nstr[3] >= nstr[4]`` raises "Overlap happened !";
+    * in the grow phase the upper zone grows up when its excess is the larger one (or one zone is left), else it grows down
+      towards the lower zone; the lower zone then grows up; when ``nstr[2] == nstr[4]`` the two become one zone and the
+      phase runs again."""
+    criteria = convergence_criteriaT(it_max=8, itmx=5, conv=5.0, convt=3.0, x_max_mult=7.0)
+    subad, ifirst = 0.98, 10 - 1
+    state = dict(flux_net_ir_layer=flux_net_ir_layer, flux_plus_ir_attop=flux_plus_ir_attop, all_profiles=all_profiles,
+                 all_opd=all_opd, all_kzz=all_kzz, CloudParameters=CloudParameters, temp=temp, pressure=pressure)
+
+    def step(nofczns, criteria, final):
+        out = profile(bundle, nofczns, nstr, state["temp"], state["pressure"], AdiabatBundle, opacityclass, grav, rfaci,
+                      rfacv, tidal, Opagrid, state["CloudParameters"], save_profile, state["all_profiles"],
+                      state["all_opd"], criteria, final, flux_net_ir_layer=state["flux_net_ir_layer"],
+                      flux_plus_ir_attop=state["flux_plus_ir_attop"], verbose=verbose, moist=moist, save_kzz=save_kzz,
+                      self_consistent_kzz=self_consistent_kzz, diseq=diseq, all_kzz=state["all_kzz"], _fluxes=_fluxes)
+        (state["flag"], state["pressure"], state["temp"], dtdp, state["CloudParameters"], state["cld_out"],
+         state["flux_net_ir_layer"], state["flux_net_v_layer"], state["flux_plus_ir_attop"], state["all_profiles"],
+         state["all_opd"], state["all_kzz"]) = out
+        return dtdp
+
+    bundle.add_pt(temp, pressure)
+    bundle.premix_atmosphere(opacityclass, verbose=verbose)
+    Atmosphere = calculate_atm(bundle, opacityclass, only_atmosphere=True)
+    dtdp = Atmosphere.dtdp
+    grad_x, _ = convec(temp, pressure, AdiabatBundle, Atmosphere, moist=moist)          # once: never refreshed
+
+    while dtdp[nstr[1] - 1] >= subad * grad_x[nstr[1] - 1]:
+        ngrow = 2 if dtdp[nstr[1] - 1] / grad_x[nstr[1] - 1] > 1.8 else 1
+        if verbose and ngrow == 2:
+            print("find_strat: lapse rate above 1.8 x adiabatic, growing by two levels")
+        growup(1, nstr, ngrow)
+        if nstr[1] < 5:
+            raise ValueError("Convection zone grew to Top of atmosphere, Need to Stop")
+        dtdp = step(nofczns, criteria, False)
+
+    dt_max, i_max = 0.0, 0
+    for i in range(nstr[1] - 1, ifirst - 1, -1):                  # the first super-adiabatic layer from below: `break`
+        add = dtdp[i] - grad_x[i]
+        if add > dt_max and add / grad_x[i] >= 0.02:
+            dt_max, i_max = add, i
+            break
+
+    if not (i_max == 0 or dt_max / grad_x[i_max] < 0.02):
+        if verbose:
+            print("find_strat: second convective zone at layer", i_max, "zones before", nstr)
+        nofczns = 2
+        nstr[4], nstr[5] = nstr[1], nstr[2]
+        nstr[1] = nstr[2] = nstr[3] = i_max                       # nstr[3]: i_max, not i_max + 1
+        if nstr[3] >= nstr[4]:
+            raise ValueError("Overlap happened !")
+        dtdp = step(nofczns, criteria, False)
+
+        def merge():
+            nstr[2], nstr[3] = nstr[5], 0
+            return 1, 1
+        i_change = 1
+        while i_change == 1:
+            if verbose:
+                print("find_strat: grow phase")
+            i_change = 0
+            d1, d2, c1, c2 = dtdp[nstr[1] - 1], dtdp[nstr[3]], grad_x[nstr[1] - 1], grad_x[nstr[3]]
+            while d1 > subad * c1 or d2 > subad * c2:
+                if (d1 - c1) >= (d2 - c2) or nofczns == 1:
+                    growup(1, nstr, 1)
+                    if nstr[1] < 3:
+                        raise ValueError("Convection zone grew to Top of atmosphere, Need to Stop")
+                else:
+                    growdown(1, nstr, 1)
+                    if nstr[2] == nstr[4]:                        # the two zones met: one zone
+                        nofczns, i_change = merge()
+                if verbose:
+                    print(nstr)
+                dtdp = step(nofczns, criteria, False)
+                d1, d2, c1, c2 = dtdp[nstr[1] - 1], dtdp[nstr[3]], grad_x[nstr[1] - 1], grad_x[nstr[3]]
+            while dtdp[nstr[4] - 1] >= subad * grad_x[nstr[4] - 1] and nofczns > 1:      # the lower zone
+                growup(2, nstr, 1)
+                if nstr[2] == nstr[4]:
+                    nofczns, i_change = merge()
+                if verbose:
+                    print(nstr)
+                dtdp = step(nofczns, criteria, False)
+
+    criteria = convergence_criteriaT(10, 6, 2.0, 2.0, 7.0 / 2.0)
+    if verbose:
+        print("find_strat: final profile call with zones", nstr)
+    dtdp = step(nofczns, criteria, True)
+    if verbose:
+        print("find_strat: converged" if state["flag"] == 1 else "find_strat: ended without convergence")
+    chem = bundle.inputs["atmosphere"]["profile"]
+    return (state["flag"], state["pressure"], state["temp"], dtdp, nstr, state["flux_net_ir_layer"],
+            state["flux_net_v_layer"], state["flux_plus_ir_attop"], chem, state["cld_out"], state["all_profiles"],
+            state["all_opd"], state["all_kzz"])
+
+
+def run_chemeq_climate_workflow(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal,
+                                Opagrid, CloudParameters, save_profile, all_profiles, all_opd, verbose=True, moist=None,
+                                save_kzz=True, self_consistent_kzz=True, _fluxes=None):
+    """The equilibrium-chemistry climate solve (reference climate.py:217-326): ``profile`` with the loose criteria
+    ``(10, 7, 10.0, 5.0, 7.0)``, again with ``(7, 5, 5.0, 4.0, 7.0)``, then ``find_strat``.  Returns ``find_strat``'s 13 values.
+    As in the reference ``find_strat`` is called WITHOUT ``save_kzz`` (it keeps its default, False): kzz profiles are
+    collected during the two ``profile`` calls only.  ``nstr`` is modified in place."""
+    common = (AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid)
+    out = profile(bundle, nofczns, nstr, temp, pressure, *common, CloudParameters, save_profile, all_profiles, all_opd,
+                  convergence_criteriaT(10, 7, 10.0, 5.0, 7.0), False, first_call_ever=True, verbose=verbose, moist=moist,
+                  save_kzz=save_kzz, self_consistent_kzz=self_consistent_kzz, _fluxes=_fluxes)
+    _, pressure, temperature, dtdp, CloudParameters, _, net_layer, _, plus_top, all_profiles, all_opd, all_kzz = out
+    out = profile(bundle, nofczns, nstr, temperature, pressure, *common, CloudParameters, save_profile, all_profiles,
+                  all_opd, convergence_criteriaT(7, 5, 5.0, 4.0, 7.0), False, flux_net_ir_layer=net_layer,
+                  flux_plus_ir_attop=plus_top, verbose=verbose, moist=moist, save_kzz=save_kzz, all_kzz=all_kzz,
+                  self_consistent_kzz=self_consistent_kzz, _fluxes=_fluxes)
+    _, pressure, temperature, dtdp, CloudParameters, _, net_layer, _, plus_top, all_profiles, all_opd, all_kzz = out
+    return find_strat(bundle, nofczns, nstr, temperature, pressure, dtdp, *common, CloudParameters, save_profile,
+                      all_profiles, all_opd, net_layer, plus_top, verbose=verbose, moist=moist,
+                      self_consistent_kzz=self_consistent_kzz, all_kzz=all_kzz, _fluxes=_fluxes)

@@ -9,9 +9,13 @@ the return-dict keys and the post-processing formulas.  Quantities are plain cgs
 reference's astropy-unit arguments are not reproduced) and everything between ``get_opacities`` and
 ``compress_disco`` stays in HBM.
 
-Out of scope here: chemistry, virga clouds, stellar grids (``star()`` takes a
-relative flux vector), xarray I/O, climate, retrievals, phase curves, 3-D regridding.
+The climate solve (``setup_climate`` / ``inputs_climate`` / ``climate``, cloud-free with equilibrium chemistry from the
+table the opacity object carries) drives ``picaso_amd.climate``.
+
+Out of scope here: chemistry models, virga clouds, stellar grids (``star()`` takes a
+relative flux vector), xarray I/O, retrievals.
 """
+import collections
 import copy
 
 import os
@@ -449,11 +453,11 @@ class inputs:
 
     def __init__(self, calculation="planet", climate=False):
         """``calculation='browndwarf'``: no star and no Raman scattering (``setup_nostar``), as in the reference
-        (justdoit.py:1446-1451).  ``climate=True`` would start the T(P) iteration, which is outside this package
-        (its radiative-transfer call is ``picaso_amd.climate.get_fluxes``)."""
+        (justdoit.py:1446-1451).  ``climate=True`` raises: a climate run is set up with the reference's own method,
+        ``setup_climate()``, then ``inputs_climate()`` and ``climate()``."""
         if climate:
-            raise Exception("inputs(climate=True): the climate solver's T(P) iteration is outside this package; its "
-                            "radiative-transfer call is picaso_amd.climate.calculate_atm / get_fluxes")
+            raise Exception("inputs(climate=True) is not the entry of the climate solve here: build inputs(calculation=...) "
+                            "and call setup_climate(), inputs_climate(), climate()")
         self.inputs = copy.deepcopy(_DEFAULTS)
         self.inputs["calculation"] = calculation
         if "brown" in calculation:
@@ -645,12 +649,16 @@ class inputs:
         and volume mixing ratios.  As in the reference: levels are sorted by pressure; ``exclude_mol`` (a name or a list
         of names) switches molecules off in the opacities only; and Raman scattering is switched off
         (``raman='none'``) for an atmosphere without H2 or with less than 70 % of it anywhere (:2033-2040).
-        The chemistry keywords (``mh``, ``cto_*``, ``chem_method``, photochemistry, the climate hacks) belong to
-        subsystems outside this package and raise."""
+        The chemistry keywords (``mh``, ``cto_*``, ``chem_method``, photochemistry) belong to subsystems outside this
+        package and raise; ``quench, no_ph3, cold_trap, vol_rainout`` raise too unless this is a climate set-up
+        (``setup_climate()``), where they are stored in ``inputs['approx']['chem_params']`` for ``premix_atmosphere``."""
         if any(x is not None for x in (mh, cto_absolute, cto_relative, chem_method, photochem_init_args)):
             raise Exception("atmosphere(mh=, cto_*=, chem_method=, photochem_init_args=): chemistry is outside this package; "
                             "give the mixing ratios as columns of df / filename")
-        if any((quench, no_ph3, cold_trap, vol_rainout)):
+        if self.inputs.get("calculation") == "climate":                  # justdoit.py:2076-2080
+            self.inputs["approx"]["chem_params"] = dict(quench=quench, no_ph3=no_ph3, cold_trap=cold_trap,
+                                                        vol_rainout=vol_rainout)
+        elif any((quench, no_ph3, cold_trap, vol_rainout)):
             raise Exception("'quench','no_ph3','cold_trap','vol_rainout' are a climate kwargs and climate calculation is "
                             "not specified so this will not do anything")
         if df is not None:
@@ -1051,6 +1059,277 @@ class inputs:
         t["toon_coefficients"] = toon_phase_coefficients(False).index(toon_coefficients)
         t["multi_phase"] = multi_phase_options(False).index(multi_phase)
         t["single_phase"] = single_phase_options(False).index(single_phase)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # the climate solve (reference justdoit.py: setup_climate :1705, chem_interp :3106, add_pt :3201, premix_atmosphere
+    # :2237, effective_temp :4842, inputs_climate :4883, energy_injection :4953, climate :4982)
+    # ------------------------------------------------------------------------------------------------------------------
+    def setup_climate(self):
+        """Prepare this object for ``climate()`` (reference justdoit.py:1705-1735): ``calculation = 'climate'``, Raman
+        scattering off, zero phase with 10 Gauss angles, and the H/He adiabat tables (``climate.load_adiabat``: log10 T,
+        log10 P, the adiabatic gradient and log10 cp, from ``$picaso_refdata/climate_INPUTS``) in ``inputs['climate']``.
+        A caller without that file puts ``t_table, p_table, grad, cp`` into ``inputs['climate']`` before this call; they
+        are kept."""
+        from . import climate as _climate
+        self.inputs["calculation"] = "climate"
+        self.inputs["approx"]["rt_params"]["common"]["raman"] = 2
+        self.phase_angle(0, num_gangle=10, num_tangle=1)
+        cl = self.inputs.setdefault("climate", {})
+        if not all(k in cl for k in ("t_table", "p_table", "grad", "cp")):
+            cl.update(_climate.load_adiabat()._asdict())
+        self.inputs["approx"].setdefault("chem_params", dict(quench=False, no_ph3=False, cold_trap=False, vol_rainout=False))
+        self.inputs["approx"].setdefault("chem_method", None)
+
+    def _climate_inputs(self):
+        if "climate" not in self.inputs or self.inputs.get("calculation") != "climate":
+            raise Exception("this is not a climate set-up: call setup_climate() first (inputs(climate=True) is not the entry "
+                            "of this package)")
+        return self.inputs["climate"]
+
+    def effective_temp(self, teff=None):
+        """Same as ``T_eff`` (reference justdoit.py:4842-4851)."""
+        return self.T_eff(teff)
+
+    def T_eff(self, Teff=None):
+        """Effective temperature (K) of the climate run; ``None`` stores 0 (reference justdoit.py:4853-4866)."""
+        self.inputs["planet"]["T_eff"] = Teff if Teff is not None else 0
+
+    def add_pt(self, T=None, P=None, P_config=None):
+        """Replace the atmosphere profile by temperature (K) and pressure (bar) alone, sorted by pressure; every
+        abundance column goes (reference justdoit.py:3201-3247).  ``P_config`` (the reference's ``pressure_grid``) is not
+        implemented."""
+        if P_config is not None:
+            raise NotImplementedError("add_pt(P_config=): pressure_grid is not implemented; give the pressure levels as P")
+        cols = {}
+        if T is not None:
+            cols["temperature"] = np.array(T, dtype=float)
+            self.nlevel = len(cols["temperature"])
+        if P is not None:
+            cols["pressure"] = np.array(P, dtype=float)
+            self.nlevel = len(cols["pressure"])
+        if "pressure" not in cols:
+            raise KeyError("pressure")                               # as sorting the reference's frame by it
+        order = np.argsort(cols["pressure"], kind="stable")
+        self.inputs["atmosphere"]["profile"] = {k: v[order] for k, v in cols.items()}
+
+    def pressure_grid(self, P_config):
+        raise NotImplementedError("pressure_grid is not implemented; give the pressure levels to inputs_climate / add_pt")
+
+    def energy_injection(self, inject_energy=False, total_energy_injection=0, press_max_energy=1, injection_scalehight=1,
+                         inject_beam=False, beam_profile=0):
+        """Energy injected into the atmosphere on top of ``sigma T_eff^4`` (reference justdoit.py:4953-4980): a Chapman
+        profile of ``total_energy_injection`` erg/cm^2/s around ``press_max_energy`` bar, or a numerical ``beam_profile`` on
+        the climate pressure grid (``inject_beam``).  Read by ``climate()`` through ``fluxes.tidal_flux``."""
+        self._climate_inputs().update(inject_energy=inject_energy, total_energy_injection=total_energy_injection,
+                                      press_max_energy=press_max_energy, injection_scaleheight=injection_scalehight,
+                                      inject_beam=inject_beam, beam_profile=beam_profile)
+
+    def inputs_climate(self, temp_guess=None, pressure=None, rfaci=1, rcb_guess=None, rfacv=None, moistgrad=False):
+        """Starting point of the climate run (reference justdoit.py:4883-4931): the guess T(P) on the pressure grid the
+        run keeps, ``rcb_guess`` = the level index of the radiative-convective boundary (``nstr = [0, rcb_guess,
+        nlevel - 2, 0, 0, 0]``, one convective zone), ``rfaci`` / ``rfacv`` the weights of the IR and the visible net flux
+        (``rfacv``: 0 no star, 0.5 full redistribution, 1 dayside)."""
+        cl = self._climate_inputs()
+        if self.inputs["planet"].get("T_eff", 0.0) == 0.0:
+            raise Exception("Need to specify Teff with jdi.input for climate run")
+        if self.inputs["planet"]["gravity"] in (None, 0.0):
+            raise Exception("Need to specify gravity with jdi.input for climate run")
+        temp_guess, pressure = np.array(temp_guess, dtype=float), np.array(pressure, dtype=float)
+        cl.update(guess_temp=temp_guess, pressure=pressure, nstr=[0, rcb_guess, len(pressure) - 2, 0, 0, 0], nofczns=1,
+                  rfacv=rfacv, rfaci=rfaci, moistgrad=moistgrad)
+        self.add_pt(temp_guess, pressure)
+
+    def chem_interp(self, chem_grid):
+        """Abundances of every level from a chemistry table (reference justdoit.py:3106-3199): ``chem_grid`` (a dictionary
+        of columns or a DataFrame) has ``pressure`` (bar), ``temperature`` (K) and one column per species, rows
+        temperature-major with ascending temperatures and, per temperature, the first ``nc_p[it]`` pressures of one
+        ascending grid.  Bilinear in ``(1/T, log10 P)`` of the log10 abundance.
+
+        As in the reference: the lower temperature index is the last table temperature below the level's (0 below the
+        table, ``ntemp - 2`` at or above its top, so both ends extrapolate along 1/T); the lower pressure index is the last
+        table pressure at or below the level's (0 below the table), held to ``nc_p[t_hi] - 3`` of the UPPER temperature's
+        column, whose ragged edge therefore also extrapolates.  The species columns are added to the profile."""
+        prof = self.inputs["atmosphere"]["profile"]
+        plevel, tlevel = np.asarray(prof["pressure"], dtype=float), np.asarray(prof["temperature"], dtype=float)
+        t_inv, p_log = 1 / tlevel, np.log10(plevel)
+        tab_t, tab_p = np.asarray(chem_grid["temperature"], dtype=float), np.asarray(chem_grid["pressure"], dtype=float)
+        species = [k for k in chem_grid.keys() if k not in ("pressure", "temperature")]
+        with np.errstate(divide="ignore"):
+            log_abunds = np.log10(np.stack([np.asarray(chem_grid[k], dtype=float) for k in species], axis=1))
+        nc_p = np.unique(tab_t, return_counts=True)[1]               # per temperature, in ascending temperature
+        _, first = np.unique(tab_t, return_index=True)
+        temps = tab_t[np.sort(first)]                                # in order of appearance, as the reference reads them
+        p_grid = np.unique(tab_p)
+        p_log_grid = np.log10(p_grid[p_grid > 0])
+        t_inv_grid = 1 / temps
+        nt = len(t_inv_grid)
+
+        def last_where(mask):                                        # last true index of every row, 0 when none
+            idx = mask.shape[1] - 1 - np.argmax(mask[:, ::-1], axis=1)
+            return np.where(mask.any(axis=1), idx, 0)
+        t_low = last_where(t_inv_grid[None, :] > t_inv[:, None])
+        t_low[t_low == nt - 1] = nt - 2
+        t_hi = t_low + 1
+        p_low = np.minimum(last_where(p_log_grid[None, :] <= p_log[:, None]), nc_p[t_hi] - 3)
+        p_hi = p_low + 1
+        start = np.concatenate(([0], np.cumsum(nc_p)))               # first row of every temperature
+        t_i = ((t_inv - t_inv_grid[t_low]) / (t_inv_grid[t_hi] - t_inv_grid[t_low]))[:, None]
+        p_i = ((p_log - p_log_grid[p_low]) / (p_log_grid[p_hi] - p_log_grid[p_low]))[:, None]
+        abunds = 10 ** (((1 - t_i) * (1 - p_i) * log_abunds[start[t_low] + p_low, :])
+                        + (t_i * (1 - p_i) * log_abunds[start[t_hi] + p_low, :])
+                        + (t_i * p_i * log_abunds[start[t_hi] + p_hi, :])
+                        + ((1 - t_i) * p_i * log_abunds[start[t_low] + p_hi, :]))
+        for i, k in enumerate(species):
+            prof[k] = abunds[:, i]
+
+    def chemeq_visscher_1060(self, *a, **k):
+        raise NotImplementedError("chemeq_visscher_1060 (the chemistry grids shipped with the reference) is not implemented: "
+                                  "use an opacity object that carries full_abunds")
+
+    chemeq_visscher_2121 = chemeq_visscher_1060
+
+    def premix_atmosphere_photochem(self, *a, **k):
+        raise NotImplementedError("premix_atmosphere_photochem needs the photochem package, which is not part of this package")
+
+    def virga(self, *a, **k):
+        raise NotImplementedError("virga clouds are not implemented; give fixed cloud tables through clouds()")
+
+    def premix_atmosphere(self, opa=None, quench_levels=None, verbose=True):
+        """Chemistry of the current T(P) profile (reference justdoit.py:2237-2281 with its ``chemistry_handler``,
+        :2082-2133): with a chemistry table on the opacity object (``opa.full_abunds``, a dictionary of columns or a
+        DataFrame) the abundances are interpolated from it (``chem_interp``); ``chem_params['no_ph3']`` then zeroes PH3.
+        Without a table and without a ``chem_method`` the reference's exception is raised.  Not implemented: the
+        ``visscher`` grids, photochem, and ``quench`` / ``vol_rainout`` / ``cold_trap`` (which need virga's vapour-pressure
+        curves)."""
+        table = getattr(opa, "full_abunds", None)
+        approx = self.inputs["approx"]
+        chem_method = approx.get("chem_method", None)
+        params = approx.get("chem_params", {})
+        if "visscher" in str(chem_method):
+            self.chemeq_visscher_1060()
+        if "photochem" in str(chem_method):
+            self.premix_atmosphere_photochem()
+        for key in ("quench", "vol_rainout", "cold_trap"):
+            if params.get(key, False):
+                raise NotImplementedError("premix_atmosphere: chem_params[%r] is not implemented (it needs the quench "
+                                          "chemistry / virga's vapour-pressure curves)" % key)
+        prof = self.inputs["atmosphere"]["profile"]
+        if table is not None:
+            approx["chem_method"] = "chemistry table loaded through opannection"
+            if prof is not None and "temperature" in prof.keys() and "pressure" in prof.keys():
+                self.chem_interp(table)
+        else:
+            raise Exception("A chem option %s is not valid. Likely you specified method='resrotrebin' in opannection but did "
+                            "not run `atmosphere()` function after inputs_climate." % chem_method)
+        if params.get("no_ph3", False):
+            if verbose:
+                print("premix_atmosphere: no_ph3 is set, PH3 goes to zero")
+            if "PH3" in prof.keys():
+                prof["PH3"] = np.zeros(len(prof["pressure"]))
+
+    def interpret_run(self):
+        """One line on what the run is set up to do (reference justdoit.py:4868-4881)."""
+        cl = self.inputs["climate"]
+        print("climate run: clouds %s, moist adiabat %s, chemistry switches %s"
+              % (cl.get("cloudy", False), cl["moistgrad"], self.inputs["approx"].get("chem_params", {})))
+
+    def climate(self, opacityclass, save_all_profiles=False, with_spec=False, save_all_kzz=False, diseq_chem=False,
+                self_consistent_kzz=True, verbose=True):
+        """Radiative-convective equilibrium T(P) profile (reference justdoit.py:4982-5280): ``tidal_flux`` for the flux
+        every level carries, then ``climate.run_chemeq_climate_workflow`` (two ``profile`` calls and ``find_strat``).
+        Returns a dictionary: ``pressure, temperature, ptchem_df`` (the profile with the abundances, a dictionary of
+        columns), ``dtdp, cvz_locs`` (the final ``nstr``), ``flux_ir_attop, fnet/fnetir, converged, flux_balance``;
+        ``all_profiles, all_opd, all_kzz`` with ``save_all_profiles``; ``spectrum_output`` with ``with_spec`` (the thermal
+        spectrum at the converged profile, ``full_output=True``).
+
+        As in the reference the trial temperatures stay inside the opacity table's range widened by 30 % (``tmin = 10`` for
+        ``T_eff <= 300``, ``tmax = 10000`` for ``T_eff > 1600``), and without a star ``rfacv = 0`` and ``F0PI = 1``.
+        Not implemented: ``diseq_chem=True``, a cloudy set-up (``inputs['climate']['cloudy']``, virga), the moist adiabat,
+        and ``save_all_profiles`` as an HDF5 path."""
+        from . import climate as _climate
+        from .fluxes import tidal_flux
+        cl = self._climate_inputs()
+        if "guess_temp" not in cl:
+            raise Exception("climate(): call inputs_climate() first")
+        if diseq_chem:
+            raise NotImplementedError("climate(diseq_chem=True): the disequilibrium workflow (run_diseq_climate_workflow, "
+                                      "the quench chemistry) is not implemented")
+        if cl.get("cloudy", False):
+            raise NotImplementedError("climate(): a cloudy set-up needs virga (update_clouds), which is not implemented")
+        if isinstance(save_all_profiles, str):
+            raise NotImplementedError("climate(save_all_profiles=<path>): HDF5 profile dumps are not implemented; pass True")
+        if not hasattr(opacityclass, "delta_wno"):
+            raise Exception("climate(): the opacity object has no delta_wno (the bin widths of its wavenumber grid)")
+        nwno = opacityclass.nwno
+        min_temp, max_temp = min(opacityclass.temps), max(opacityclass.temps)
+        Teff = self.inputs["planet"]["T_eff"]
+        extension = 0.3
+        tmin = min_temp * (1 - extension) if Teff > 300 else 10
+        tmax = 10000 if Teff > 1600 else max_temp * (1 + extension)
+        Opagrid = _climate.Opagrid_Tuple(nwno, opacityclass.delta_wno, opacityclass.wno, opacityclass.ngauss,
+                                         opacityclass.gauss_wts, tmin, tmax)
+        nofczns, nstr, rfaci = cl["nofczns"], cl["nstr"], cl["rfaci"]
+        if "nostar" in str(self.inputs["star"]["database"]):
+            rfacv = 0.0
+            opacityclass.relative_flux = np.zeros(nwno) + 1.0
+        else:
+            rfacv = cl["rfacv"]
+        save_profile = 1 if save_all_profiles else 0
+        pressure, TEMP1 = cl["pressure"], cl["guess_temp"]
+        all_profiles = np.append([], TEMP1)
+        all_opd = np.append([], np.zeros(len(TEMP1) - 1))
+        moist = cl["moistgrad"]
+        AdiabatBundle = _climate.AdiabatBundle_Tuple(cl["t_table"], cl["p_table"], cl["grad"], cl["cp"])
+
+        inject_energy, inject_beam = cl.get("inject_energy", False), cl.get("inject_beam", False)
+        if inject_energy == True:                                    # noqa: E712
+            wave_in, pm, hratio = cl["total_energy_injection"], cl["press_max_energy"], cl["injection_scaleheight"]
+            beam_profile = cl["beam_profile"]
+            if inject_beam == True and len(beam_profile) != len(pressure):      # noqa: E712
+                raise Exception("Beam profile must on the same pressure grid as the climate profile")
+        else:
+            wave_in, pm, hratio, beam_profile = 0, 1, 1, 0
+        InjectionBundle = collections.namedtuple("InjectionBundle", ["inject_energy", "inject_beam", "wave_in", "pm",
+                                                                     "hratio", "beam_profile"])(
+            inject_energy, inject_beam, wave_in, pm, hratio, beam_profile)
+        grav = 0.01 * self.inputs["planet"]["gravity"]               # cgs to SI
+        col_den = 1e6 * (pressure[1:] - pressure[:-1]) / (grav / 0.01)
+        nlevel = len(pressure)
+        tidal = tidal_flux(Teff, nlevel, pressure, col_den, InjectionBundle)
+
+        if save_all_kzz:
+            self.inputs["atmosphere"]["kzz"] = {}
+            if not self_consistent_kzz:
+                kzz = self.inputs["atmosphere"]["profile"].get("kz", False)
+                if isinstance(kzz, bool):
+                    raise Exception("self_consistent_kzz=False but no kzz profile was supplised. Please add to "
+                                    "self.inputs['atmosphere']['profile'] ")
+                self.inputs["atmosphere"]["kzz"]["constant_kzz"] = np.asarray(kzz)
+            else:
+                self.inputs["atmosphere"]["kzz"]["sc_kzz"] = 0
+        zeros = [np.zeros((self.nlevel - 1, nwno, 4)) for _ in range(3)]
+        CloudParameters = collections.namedtuple("CloudParameters", ["cloudy", "OPD", "G0", "W0"])(False, *zeros)
+        if verbose:
+            self.interpret_run()
+
+        (final_conv_flag, pressure, temp, dtdp, nstr_new, flux_net_ir_final, flux_net_v_final, flux_plus_final, chem_out,
+         cld_out, all_profiles, all_opd, all_kzz) = _climate.run_chemeq_climate_workflow(
+            self, nofczns, nstr, TEMP1, pressure, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid,
+            CloudParameters, save_profile, all_profiles, all_opd, verbose=verbose, moist=moist, save_kzz=save_all_kzz,
+            self_consistent_kzz=self_consistent_kzz)
+
+        flux_net_final = rfacv * flux_net_v_final + rfaci * flux_net_ir_final + tidal
+        all_out = {"pressure": pressure, "temperature": temp, "ptchem_df": chem_out, "dtdp": dtdp, "cvz_locs": nstr_new,
+                   "flux_ir_attop": flux_plus_final, "fnet/fnetir": flux_net_final / flux_net_ir_final,
+                   "converged": final_conv_flag,
+                   "flux_balance": dict(flux_net_ir=flux_net_ir_final, flux_net_v=flux_net_v_final, tidal=tidal, rfacv=rfacv,
+                                        rfaci=rfaci, flux_net=flux_net_final)}
+        if save_all_profiles:
+            all_out.update(all_profiles=all_profiles, all_opd=all_opd, all_kzz=all_kzz)
+        if with_spec:
+            self.atmosphere(df=chem_out, **self.inputs["approx"]["chem_params"])
+            all_out["spectrum_output"] = self.spectrum(opacityclass, full_output=True, calculation="thermal")
+        return all_out
 
     def spectrum(self, opacityclass, calculation="reflected", dimension="1d", full_output=False,
                  plot_opacity=False, as_dict=True, devices=None, gather="host", options=None, regrid=None, convolve=None):
