@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib, resident
 from ._lib import f64
+from .deq_chem import get_quench_levels
 from .device import DeviceArray, PinnedArray
 
 # the reference's containers (climate.py:1962-1966)
@@ -711,10 +712,10 @@ def t_start(nofczns, nstr, convergence_criteria, rfaci, rfacv, tidal, Atmosphere
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The driver around t_start (reference climate.py: get_kzz :331-493, update_kzz :56-124, profile :2926-3249, find_strat
-# :2542-2839, run_chemeq_climate_workflow :217-326).  Host code on nlevel-sized vectors; the device work is what
-# calculate_atm, t_start and get_fluxes do.  profile and find_strat reach those three through this module's names, so a
-# test may replace them.
+# The driver around t_start (reference climate.py: get_kzz :331-493, update_kzz :56-124, update_quench_levels :23-54, profile
+# :2926-3249, find_strat :2542-2839, run_chemeq_climate_workflow :217-326, run_diseq_climate_workflow :126-214).  Host code
+# on nlevel-sized vectors; the device work is what calculate_atm, t_start and get_fluxes do.  profile and find_strat reach
+# those three through this module's names, so a test may replace them.
 # ---------------------------------------------------------------------------------------------------------------------
 SIGMA_SB = 0.56687e-4                                            # erg cm^-2 s^-1 K^-4, the reference's value
 
@@ -800,6 +801,26 @@ def update_kzz(grav, tidal, AdiabatBundle, nstr, Atmosphere, OpacityWEd=None, Op
     return get_kzz(grav, tidal, flux_net_ir_layer, flux_plus_ir_attop, AdiabatBundle, nstr, Atmosphere, moist=moist)
 
 
+def update_quench_levels(bundle, Atmosphere, kz, grav, verbose=False):
+    """Quench levels of the bundle's current (equilibrium) chemistry (reference climate.py:23-54): ``get_quench_levels`` with
+    the metallicity ``bundle.inputs['atmosphere']['mh']`` (1, with the reference's warning, when it was not set).  PH3 is
+    quenched only when ``H2``, ``H2O`` and ``PH3`` are all columns of the profile."""
+    prof = bundle.inputs["atmosphere"]["profile"]
+    if all(m in prof.keys() for m in ("H2", "H2O", "PH3")):
+        H2O, H2, PH3 = np.asarray(prof["H2O"], dtype=float), np.asarray(prof["H2"], dtype=float), True
+    else:
+        H2O, H2, PH3 = None, None, False
+    mh_linear = bundle.inputs["atmosphere"].get("mh", None)
+    if mh_linear is None:
+        print("User warning: mh was not explicitly set so we are assuming no metallicity dependence (e.g., M/H=1xSolar) for "
+              "the quench approximations published in Zahnle and Marley 2014")
+        mh_linear = 1
+    quench_levels, _ = get_quench_levels(Atmosphere, kz, grav, mh_linear, PH3=PH3, H2O=H2O, H2=H2)
+    if verbose:
+        print("Computed quenched levels at", quench_levels)
+    return quench_levels
+
+
 def profile(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid,
             CloudParameters, save_profile, all_profiles, all_opd, convergence_criteria, final, flux_net_ir_layer=None,
             flux_plus_ir_attop=None, first_call_ever=False, verbose=True, moist=None, save_kzz=False,
@@ -817,28 +838,42 @@ def profile(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, 
     * ``bundle.add_pt``, ``bundle.premix_atmosphere`` and ``calculate_atm`` run once before the loop; inside it only the
       chemistry of the bundle follows the new profile -- cloud-free equilibrium chemistry needs no refresh, so every
       ``t_start`` call of one ``profile`` call sees the SAME opacity planes (the DeviceArrays of ``calculate_atm``, handed on
-      as they are);
+      as they are).  With ``diseq`` the planes ARE refreshed, before the loop and after every ``t_start`` call (below);
     * each ``t_start`` call starts from the temperatures the previous one returned (the reference's ``t_start`` works in
       ``Atmosphere.t_level`` itself), and ``Atmosphere.dtdp`` stays that of the entry profile, which is what ``get_kzz`` reads;
-    * the kzz profile is computed only with ``save_kzz`` (before the loop from a fresh thermal ``get_fluxes`` call, inside it
-      from the fluxes ``t_start`` returned) and is booked in ``bundle.inputs['atmosphere']['kzz']['sc_kzz']``;
+    * the kzz profile is computed with ``save_kzz`` or with ``self_consistent_kzz and diseq`` (before the loop from a fresh
+      thermal ``get_fluxes`` call, inside it from the fluxes ``t_start`` returned); the one before the loop is booked in
+      ``bundle.inputs['atmosphere']['kzz']['sc_kzz']``; ``all_kzz`` collects them only with ``save_kzz``;
     * converged means ``iii > 0 and sum|dT| / (1.5 nlevel) < convt`` (the cloud term ``taudif = 0 < 0.1`` always holds); the
       reference then sets ``itmx`` of its local copy of the criteria, which nobody reads;
     * with ``CloudParameters.cloudy`` false ``do_holes`` is false whatever ``bundle.inputs['clouds']`` says, so the hole
       planes ``calculate_atm`` may return are not used;
     * ``flux_net_ir_layer`` / ``flux_plus_ir_attop`` / ``first_call_ever`` are accepted and not read.
 
+    ``diseq=True`` (the quench approximation, climate.py:3083-3124 and :3153-3209): before the loop and after every ``t_start``
+    call the equilibrium chemistry of the new profile (``premix_atmosphere(quench_levels=None)``) is followed by
+    ``update_kzz`` (self-consistent kzz) or the bundle's ``['kzz']['constant_kzz']`` (``self_consistent_kzz=False``),
+    ``update_quench_levels``, ``premix_atmosphere(quench_levels=...)`` and a fresh ``calculate_atm``, whose planes replace the
+    old DeviceArrays (they are freed with their last reference: device memory stays flat).  Before the loop that is a
+    second ``calculate_atm`` and the kzz comes from the planes of the first, the equilibrium ones.  Inside the loop the
+    ``Atmosphere`` handed to ``update_kzz`` / ``update_quench_levels`` is that of the last ``calculate_atm`` with the new
+    temperatures: its ``dtdp``, ``mmw_layer`` and ``scale_height`` are the older ones, as in the reference, whose ``t_start``
+    writes into ``Atmosphere.t_level``.  The bundle must have ``chem_params['quench']`` set (``atmosphere(quench=True)``):
+    without it ``premix_atmosphere`` ignores the levels and the run would silently be the equilibrium one with the cost of
+    the refreshes, which is refused.
+
     ``temp`` is not modified (the reference lays the adiabat into the caller's array; its callers use the returned one).
-    Not implemented, each a ``NotImplementedError``: ``CloudParameters.cloudy`` (virga), ``diseq=True`` (the quench
-    chemistry), ``moist=True`` (the moist adiabat), a photochem ``chem_method``.
+    Not implemented, each a ``NotImplementedError``: ``CloudParameters.cloudy`` (virga), ``moist=True`` (the moist
+    adiabat), a photochem ``chem_method``.
 
     ``_fluxes``: handed to every ``t_start`` call and to ``update_kzz``."""
     if "photochem" in str(bundle.inputs["approx"].get("chem_method", None)):
         raise NotImplementedError("profile: chem_method='photochem' needs the photochem package, which is not part of this "
                                   "package")
-    if diseq:
-        raise NotImplementedError("profile: diseq=True needs the quench chemistry (update_quench_levels, "
-                                  "adjust_quench_chemistry), which is not implemented")
+    if diseq and not bundle.inputs["approx"].get("chem_params", {}).get("quench", False):
+        raise NotImplementedError("profile: diseq=True without chem_params['quench'] is not implemented: premix_atmosphere "
+                                  "would ignore the quench levels and the run would be the equilibrium one; call "
+                                  "atmosphere(quench=True) after inputs_climate")
     if CloudParameters.cloudy:
         raise NotImplementedError("profile: CloudParameters.cloudy needs virga (update_clouds), which is not implemented")
     if moist:
@@ -850,6 +885,11 @@ def profile(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, 
     nstr = [int(x) for x in nstr]
     egp_stepmax = bool(np.min(temp) <= 250)
     conv_flag = 0
+    sc_kzz_and_diseq = bool(self_consistent_kzz and diseq)
+    do_kzz_calc = sc_kzz_and_diseq or bool(save_kzz)              # climate.py:3006-3012, without clouds
+    kz_chem = None
+    if diseq and not self_consistent_kzz:
+        kz_chem = bundle.inputs["atmosphere"]["kzz"].get("constant_kzz")
 
     for nb in range(0, 3 * int(nofczns), 3):                      # the adiabat through every convective zone
         for j1 in range(nstr[nb + 1] + 1, nstr[nb + 2] + 2):
@@ -862,12 +902,23 @@ def profile(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, 
     bundle.add_pt(temp, pressure)
     bundle.premix_atmosphere(opa=opacityclass, quench_levels=None, verbose=verbose)
     OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Atmosphere, _ = calculate_atm(bundle, opacityclass)
-    if save_kzz:
+    if do_kzz_calc:
         kz = update_kzz(grav, tidal, AdiabatBundle, nstr, Atmosphere, OpacityWEd=OpacityWEd, OpacityNoEd=OpacityNoEd,
                         ScatteringPhase=ScatteringPhase, Disco=Disco, Opagrid=Opagrid, F0PI=F0PI, moist=False,
                         do_holes=do_holes, fhole=fhole, verbose=verbose, _fluxes=_fluxes)
         bundle.inputs["atmosphere"].setdefault("kzz", {})["sc_kzz"] = kz
-        all_kzz = np.append(all_kzz, kz)
+        if save_kzz:
+            all_kzz = np.append(all_kzz, kz)
+        if sc_kzz_and_diseq:
+            kz_chem = kz
+
+    def quench_and_refresh(Atmosphere):
+        """Quench the bundle's equilibrium chemistry at the levels of `Atmosphere` and `kz_chem`; the new planes."""
+        quench_levels = update_quench_levels(bundle, Atmosphere, kz_chem, grav, verbose=verbose)
+        bundle.premix_atmosphere(opa=opacityclass, quench_levels=quench_levels, verbose=verbose)
+        return calculate_atm(bundle, opacityclass)[:5]
+    if diseq:
+        OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Atmosphere = quench_and_refresh(Atmosphere)
 
     RETURNS = None
     dtdp = Atmosphere.dtdp
@@ -879,11 +930,17 @@ def profile(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, 
             egp_stepmax=egp_stepmax, _fluxes=_fluxes)
         bundle.add_pt(temp, pressure)
         bundle.premix_atmosphere(opa=opacityclass, quench_levels=None, verbose=verbose)
-        if save_kzz:
+        if do_kzz_calc:
             kz = update_kzz(grav, tidal, AdiabatBundle, nstr, Atmosphere._replace(t_level=temp),
                             flux_net_ir_layer=flux_net_ir_layer, flux_plus_ir_attop=flux_plus_ir_attop, moist=False,
                             do_holes=do_holes, fhole=fhole, verbose=verbose)
-            all_kzz = np.append(all_kzz, kz)
+            if save_kzz:
+                all_kzz = np.append(all_kzz, kz)
+            if sc_kzz_and_diseq:
+                kz_chem = kz
+        if diseq:
+            OpacityWEd, OpacityNoEd, ScatteringPhase, Disco, Atmosphere = quench_and_refresh(
+                Atmosphere._replace(t_level=temp))
         RETURNS = [conv_flag, pressure, temp, dtdp, CloudParameters, np.nan, flux_net_ir_layer, flux_net_v_layer,
                    flux_plus_ir_attop, all_profiles, all_opd, all_kzz]
         ert = np.sum(np.abs(temp - temp_old)) / (float(len(temp)) * 1.5)
@@ -1036,3 +1093,20 @@ def run_chemeq_climate_workflow(bundle, nofczns, nstr, temp, pressure, AdiabatBu
     return find_strat(bundle, nofczns, nstr, temperature, pressure, dtdp, *common, CloudParameters, save_profile,
                       all_profiles, all_opd, net_layer, plus_top, verbose=verbose, moist=moist,
                       self_consistent_kzz=self_consistent_kzz, all_kzz=all_kzz, _fluxes=_fluxes)
+
+
+def run_diseq_climate_workflow(bundle, nofczns, nstr, temp, pressure, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal,
+                               Opagrid, CloudParameters, save_profile, all_profiles, all_opd, verbose=True, moist=None,
+                               save_kzz=False, self_consistent_kzz=True, _fluxes=None):
+    """The climate solve with quench ("disequilibrium") chemistry (reference climate.py:126-214): one ``profile`` call with
+    the criteria ``(10, 7, 5.0, 4.0, 7.0)``, then ``find_strat``, both with ``diseq=True`` and -- unlike the equilibrium
+    workflow -- both with ``save_kzz``.  Returns ``find_strat``'s 13 values; ``nstr`` is modified in place."""
+    common = (AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid)
+    out = profile(bundle, nofczns, nstr, temp, pressure, *common, CloudParameters, save_profile, all_profiles, all_opd,
+                  convergence_criteriaT(it_max=10, itmx=7, conv=5.0, convt=4.0, x_max_mult=7.0), False, flux_net_ir_layer=None,
+                  flux_plus_ir_attop=None, first_call_ever=False, verbose=verbose, moist=moist, save_kzz=save_kzz,
+                  self_consistent_kzz=self_consistent_kzz, diseq=True, _fluxes=_fluxes)
+    _, pressure, temperature, dtdp, CloudParameters, _, net_layer, _, plus_top, all_profiles, all_opd, all_kzz = out
+    return find_strat(bundle, nofczns, nstr, temperature, pressure, dtdp, *common, CloudParameters, save_profile,
+                      all_profiles, all_opd, net_layer, plus_top, verbose=verbose, moist=moist, save_kzz=save_kzz,
+                      self_consistent_kzz=self_consistent_kzz, diseq=True, all_kzz=all_kzz, _fluxes=_fluxes)

@@ -651,10 +651,24 @@ class inputs:
         (``raman='none'``) for an atmosphere without H2 or with less than 70 % of it anywhere (:2033-2040).
         The chemistry keywords (``mh``, ``cto_*``, ``chem_method``, photochemistry) belong to subsystems outside this
         package and raise; ``quench, no_ph3, cold_trap, vol_rainout`` raise too unless this is a climate set-up
-        (``setup_climate()``), where they are stored in ``inputs['approx']['chem_params']`` for ``premix_atmosphere``."""
-        if any(x is not None for x in (mh, cto_absolute, cto_relative, chem_method, photochem_init_args)):
+        (``setup_climate()``), where they are stored in ``inputs['approx']['chem_params']`` for ``premix_atmosphere``.
+        In a climate set-up ``mh`` (linear: 3 for 3 x solar) with ``cto_relative`` or ``cto_absolute`` (= 0.549
+        ``cto_relative``) is stored in ``inputs['atmosphere']`` as the reference does (:2043-2055): the quench time scales
+        of ``climate(diseq_chem=True)`` read ``mh``."""
+        climate_setup = self.inputs.get("calculation") == "climate"
+        if any(x is not None for x in (chem_method, photochem_init_args)) or (
+                not climate_setup and any(x is not None for x in (mh, cto_absolute, cto_relative))):
             raise Exception("atmosphere(mh=, cto_*=, chem_method=, photochem_init_args=): chemistry is outside this package; "
                             "give the mixing ratios as columns of df / filename")
+        if mh is not None:
+            if cto_absolute is None and isinstance(cto_relative, (float, int)):
+                cto_absolute = cto_relative * 0.549
+            elif cto_relative is None and isinstance(cto_absolute, (float, int)):
+                cto_relative = cto_absolute / 0.549
+            elif "cto" in pd_kwargs:
+                raise Exception("cto is not an acceptance argument. need to input either cto_relative or cto_absolute.")
+            else:
+                raise Exception("mh was specified but cto_relative or cto_absolute was not. need to input one of these. ")
         if self.inputs.get("calculation") == "climate":                  # justdoit.py:2076-2080
             self.inputs["approx"]["chem_params"] = dict(quench=quench, no_ph3=no_ph3, cold_trap=cold_trap,
                                                         vol_rainout=vol_rainout)
@@ -698,6 +712,8 @@ class inputs:
         if len(df.keys()) > 2 and common["raman"] != 2:
             if "H2" not in df.keys() or float(np.min(np.asarray(df["H2"], dtype=float))) < 0.7:
                 common["raman"] = 2
+        if mh is not None:
+            self.inputs["atmosphere"].update(mh=mh, cto_relative=cto_relative, cto_absolute=cto_absolute)
 
     def clouds(self, filename=None, g0=None, w0=None, opd=None, p=None, dp=None, df=None, do_holes=False,
                fhole=None, fthin_cld=None, wavenumber=None, **pd_kwargs):
@@ -1096,8 +1112,9 @@ class inputs:
 
     def add_pt(self, T=None, P=None, P_config=None):
         """Replace the atmosphere profile by temperature (K) and pressure (bar) alone, sorted by pressure; every
-        abundance column goes (reference justdoit.py:3201-3247).  ``P_config`` (the reference's ``pressure_grid``) is not
-        implemented."""
+        abundance column goes (reference justdoit.py:3201-3247).  A ``kz`` column (the Kzz profile a
+        ``self_consistent_kzz=False`` run reads) of the same length is kept, reordered with the pressures.  ``P_config``
+        (the reference's ``pressure_grid``) is not implemented."""
         if P_config is not None:
             raise NotImplementedError("add_pt(P_config=): pressure_grid is not implemented; give the pressure levels as P")
         cols = {}
@@ -1110,6 +1127,9 @@ class inputs:
         if "pressure" not in cols:
             raise KeyError("pressure")                               # as sorting the reference's frame by it
         order = np.argsort(cols["pressure"], kind="stable")
+        old = self.inputs["atmosphere"].get("profile", None)
+        if old is not None and "kz" in old.keys() and len(old["kz"]) == len(order):
+            cols["kz"] = np.array(old["kz"], dtype=float)
         self.inputs["atmosphere"]["profile"] = {k: v[order] for k, v in cols.items()}
 
     def pressure_grid(self, P_config):
@@ -1197,10 +1217,15 @@ class inputs:
     def premix_atmosphere(self, opa=None, quench_levels=None, verbose=True):
         """Chemistry of the current T(P) profile (reference justdoit.py:2237-2281 with its ``chemistry_handler``,
         :2082-2133): with a chemistry table on the opacity object (``opa.full_abunds``, a dictionary of columns or a
-        DataFrame) the abundances are interpolated from it (``chem_interp``); ``chem_params['no_ph3']`` then zeroes PH3.
+        DataFrame) the abundances are interpolated from it (``chem_interp``).  With ``chem_params['quench']`` and a
+        dictionary ``quench_levels`` (``climate.update_quench_levels``) the quenched gases are then held constant above
+        their levels (``adjust_quench_chemistry``; an empty dictionary: a note that nothing has quenched, and nothing is
+        done).  ``quench_levels=None`` is the equilibrium chemistry, whatever ``chem_params['quench']`` says: the
+        disequilibrium climate loop asks for it before every quench.  The quench switch without any Kzz (``find_kzz()`` is
+        ``None``: not a disequilibrium run, which prepares ``inputs['atmosphere']['kzz']``) stays a ``NotImplementedError``:
+        the switch could not be honoured.  ``chem_params['no_ph3']`` then zeroes PH3.
         Without a table and without a ``chem_method`` the reference's exception is raised.  Not implemented: the
-        ``visscher`` grids, photochem, and ``quench`` / ``vol_rainout`` / ``cold_trap`` (which need virga's vapour-pressure
-        curves)."""
+        ``visscher`` grids, photochem, and ``vol_rainout`` / ``cold_trap`` (which need virga's vapour-pressure curves)."""
         table = getattr(opa, "full_abunds", None)
         approx = self.inputs["approx"]
         chem_method = approx.get("chem_method", None)
@@ -1209,10 +1234,35 @@ class inputs:
             self.chemeq_visscher_1060()
         if "photochem" in str(chem_method):
             self.premix_atmosphere_photochem()
-        for key in ("quench", "vol_rainout", "cold_trap"):
+        for key in ("vol_rainout", "cold_trap"):
             if params.get(key, False):
-                raise NotImplementedError("premix_atmosphere: chem_params[%r] is not implemented (it needs the quench "
-                                          "chemistry / virga's vapour-pressure curves)" % key)
+                raise NotImplementedError("premix_atmosphere: chem_params[%r] is not implemented (it needs virga's "
+                                          "vapour-pressure curves, which are not part of this package)" % key)
+        if params.get("quench", False) and self.find_kzz() is None:
+            raise NotImplementedError("premix_atmosphere: chem_params['quench'] without a Kzz is not implemented: the quench "
+                                      "chemistry needs inputs['atmosphere']['kzz'] (climate(diseq_chem=True) prepares it) or "
+                                      "a kz column of the profile; without one the result would silently be the "
+                                      "equilibrium chemistry")
+        self._chemistry_from_table(table, chem_method)
+        if params.get("quench", False) and isinstance(quench_levels, dict):
+            if verbose:
+                print("Quench=True; Adjusting quench chemistry")
+            if len(quench_levels.keys()) == 0:
+                if verbose:
+                    print("Quench=True; But nothing has quenched. Might suggest increasing kzz if it is too low or switching "
+                          "to chemical equilibrium if deq chemistry is not needed.")
+            else:
+                self.adjust_quench_chemistry(quench_levels, table)
+        prof = self.inputs["atmosphere"]["profile"]
+        if params.get("no_ph3", False):
+            if verbose:
+                print("premix_atmosphere: no_ph3 is set, PH3 goes to zero")
+            if "PH3" in prof.keys():
+                prof["PH3"] = np.zeros(len(prof["pressure"]))
+
+    def _chemistry_from_table(self, table, chem_method=None):
+        """The table branch of the reference's ``chemistry_handler`` (justdoit.py:2082-2133)."""
+        approx = self.inputs["approx"]
         prof = self.inputs["atmosphere"]["profile"]
         if table is not None:
             approx["chem_method"] = "chemistry table loaded through opannection"
@@ -1221,22 +1271,96 @@ class inputs:
         else:
             raise Exception("A chem option %s is not valid. Likely you specified method='resrotrebin' in opannection but did "
                             "not run `atmosphere()` function after inputs_climate." % chem_method)
-        if params.get("no_ph3", False):
-            if verbose:
-                print("premix_atmosphere: no_ph3 is set, PH3 goes to zero")
-            if "PH3" in prof.keys():
-                prof["PH3"] = np.zeros(len(prof["pressure"]))
+
+    def find_kzz(self):
+        """The Kzz profile (cm^2/s) the chemistry uses (reference justdoit.py:2325-2338), in this order:
+        ``inputs['atmosphere']['kzz']['constant_kzz']``, ``['kzz']['sc_kzz']``, the profile's ``kz`` column, ``None``."""
+        atm = self.inputs["atmosphere"]
+        kzz = atm.get("kzz", None) or {}
+        prof = atm.get("profile", None)
+        for src, key in ((kzz, "constant_kzz"), (kzz, "sc_kzz"), (prof if prof is not None else {}, "kz")):
+            if key in src.keys():
+                return np.array(src[key])
+        return None
+
+    def adjust_quench_chemistry(self, quench_levels, chemistry_table=None):
+        """Hold the quenched gases of the profile constant above their quench levels (reference justdoit.py:2340-2444).
+        ``quench_levels``: ``{name: level}`` of ``deq_chem.get_quench_levels``.  In the order ``PH3, CO-CH4-H2O, CO2, NH3-N2,
+        HCN`` every molecule of a name that is a column of the profile takes, at the levels ``0 .. q + 1`` INCLUSIVE, its
+        value at level ``q`` (the reference writes ``df.loc[0:q+1]``, a label slice).  Every change is booked against H2
+        (``H2 += old - new``), which is written back once at the end, so the sum of the columns of a level is kept.  (Run under
+        pandas 2.x the reference's ``old`` is a view of the column it then writes into, its ``old - new`` is zero and its H2
+        comes back unchanged; the bookkeeping its code spells out is what is done here.)
+
+        With a ``CO2`` level, CO2 is then replaced at ALL levels by its kinetic value (Zahnle & Marley 2014, eq. 43)
+        ``fCO2 = CO H2O / (K H2)``, ``K = 18.3 exp(-2376/T - (932/T)^2)``, of the already-quenched CO and H2O and of the H2
+        column AS IT STOOD ON ENTRY, with the levels ``0 .. q - 1`` holding ``fCO2[q]``; H2 is adjusted for it too.
+
+        A level ``>= nlevel`` (a cold profile, which ``get_quench_levels`` continued downward) extends the profile the same
+        way: ten levels ``logspace(log10(p[-1] + 100), 6, 10)`` along the lapse rate of the last layer, the chemistry
+        redone on the extended P-T from ``chemistry_table``, quenched, and the ten levels dropped again."""
+        prof = self.inputs["atmosphere"]["profile"]
+        self.find_kzz()                                              # as the reference: looked up, not used
+        temperature = np.asarray(prof["temperature"], dtype=float)
+        pressure = np.asarray(prof["pressure"], dtype=float)
+        nlevel = len(temperature)
+        extend_deeper = any(quench_levels[key] >= nlevel for key in quench_levels)
+        if extend_deeper:
+            print("Extending atmosphere profile deeper to accommodate deep quench levels.")
+            dtdp = (np.log(temperature[-2]) - np.log(temperature[-1])) / (np.log(pressure[-2]) - np.log(pressure[-1]))
+            pressure = np.append(pressure, np.logspace(np.log10(pressure[-1] + 100), 6, 10))
+            for i in range(nlevel, nlevel + 10):
+                temperature = np.append(temperature, np.exp(np.log(temperature[i - 1])
+                                                            - dtdp * (np.log(pressure[i - 1]) - np.log(pressure[i]))))
+            prof = self.inputs["atmosphere"]["profile"] = {"pressure": pressure, "temperature": temperature}
+            self._chemistry_from_table(chemistry_table, self.inputs["approx"].get("chem_method", None))
+        cols = {k: np.array(prof[k], dtype=float) for k in prof.keys()}
+        H2_entry = cols["H2"]
+        H2 = H2_entry.copy()
+        for name in ("PH3", "CO-CH4-H2O", "CO2", "NH3-N2", "HCN"):
+            if name not in quench_levels:
+                continue
+            q = int(quench_levels[name])
+            for mol in name.split("-"):
+                if mol in cols:
+                    old = cols[mol].copy()
+                    cols[mol][0:q + 2] = old[q]
+                    H2 = H2 + (old - cols[mol])
+        if "CO2" in quench_levels:
+            q = int(quench_levels["CO2"])
+            T = cols["temperature"]
+            K = 18.3 * np.exp(-2376 / T - (932 / T) ** 2)
+            fCO2 = (cols["CO"] * cols["H2O"]) / (K * H2_entry)
+            fCO2[:q] = fCO2[q]
+            old = cols["CO2"]
+            cols["CO2"] = fCO2
+            H2 = H2 + (old - fCO2)
+        cols["H2"] = H2
+        if extend_deeper:
+            cols = {k: v[:-10] for k, v in cols.items()}
+        self.inputs["atmosphere"]["profile"] = cols
 
     def interpret_run(self):
-        """One line on what the run is set up to do (reference justdoit.py:4868-4881)."""
+        """What the run is set up to do (reference justdoit.py:4868-4881), and which Kzz its chemistry uses."""
         cl = self.inputs["climate"]
         print("climate run: clouds %s, moist adiabat %s, chemistry switches %s"
               % (cl.get("cloudy", False), cl["moistgrad"], self.inputs["approx"].get("chem_params", {})))
+        kzz = self.inputs["atmosphere"].get("kzz", None)
+        if kzz is not None:
+            print("climate run: Kzz for the chemistry: %s"
+                  % ("the constant profile given as the column kz" if "constant_kzz" in kzz
+                     else "self-consistent, from mixing-length theory"))
 
     def climate(self, opacityclass, save_all_profiles=False, with_spec=False, save_all_kzz=False, diseq_chem=False,
                 self_consistent_kzz=True, verbose=True):
         """Radiative-convective equilibrium T(P) profile (reference justdoit.py:4982-5280): ``tidal_flux`` for the flux
-        every level carries, then ``climate.run_chemeq_climate_workflow`` (two ``profile`` calls and ``find_strat``).
+        every level carries, then ``climate.run_chemeq_climate_workflow`` (two ``profile`` calls and ``find_strat``) or, with
+        ``diseq_chem=True``, ``climate.run_diseq_climate_workflow`` (one ``profile`` call and ``find_strat`` with quench
+        chemistry: CO/CH4/H2O, CO2, NH3/N2, HCN and PH3 held constant above the level where mixing at Kzz outruns their
+        chemistry, the opacities re-mixed at those abundances after every ``t_start`` call).  ``diseq_chem`` needs an
+        opacity object that mixes per-gas tables on the fly (``opannection(method='resortrebin')``,
+        ``RetrieveCKs(kappas=...)``) and ``atmosphere(quench=True, mh=, cto_relative=)`` after ``inputs_climate``; Kzz is
+        the mixing-length profile (``self_consistent_kzz=True``) or the ``kz`` column of the profile.
         Returns a dictionary: ``pressure, temperature, ptchem_df`` (the profile with the abundances, a dictionary of
         columns), ``dtdp, cvz_locs`` (the final ``nstr``), ``flux_ir_attop, fnet/fnetir, converged, flux_balance``;
         ``all_profiles, all_opd, all_kzz`` with ``save_all_profiles``; ``spectrum_output`` with ``with_spec`` (the thermal
@@ -1244,16 +1368,18 @@ class inputs:
 
         As in the reference the trial temperatures stay inside the opacity table's range widened by 30 % (``tmin = 10`` for
         ``T_eff <= 300``, ``tmax = 10000`` for ``T_eff > 1600``), and without a star ``rfacv = 0`` and ``F0PI = 1``.
-        Not implemented: ``diseq_chem=True``, a cloudy set-up (``inputs['climate']['cloudy']``, virga), the moist adiabat,
-        and ``save_all_profiles`` as an HDF5 path."""
+        Not implemented: a cloudy set-up (``inputs['climate']['cloudy']``, virga), the moist adiabat, and
+        ``save_all_profiles`` as an HDF5 path."""
         from . import climate as _climate
         from .fluxes import tidal_flux
         cl = self._climate_inputs()
         if "guess_temp" not in cl:
             raise Exception("climate(): call inputs_climate() first")
-        if diseq_chem:
-            raise NotImplementedError("climate(diseq_chem=True): the disequilibrium workflow (run_diseq_climate_workflow, "
-                                      "the quench chemistry) is not implemented")
+        if diseq_chem and not getattr(opacityclass, "on_fly", False):
+            raise NotImplementedError("climate(diseq_chem=True) is not implemented for an opacity object that does not mix "
+                                      "per-gas tables on the fly: quenched abundances cannot change a premixed table and the "
+                                      "run would be the equilibrium one.  Build the opacity object with "
+                                      "opannection(method='resortrebin') or RetrieveCKs(kappas=..., gauss_pts=...)")
         if cl.get("cloudy", False):
             raise NotImplementedError("climate(): a cloudy set-up needs virga (update_clouds), which is not implemented")
         if isinstance(save_all_profiles, str):
@@ -1297,7 +1423,7 @@ class inputs:
         nlevel = len(pressure)
         tidal = tidal_flux(Teff, nlevel, pressure, col_den, InjectionBundle)
 
-        if save_all_kzz:
+        if diseq_chem or save_all_kzz:                               # the reference's need_kzz, without clouds
             self.inputs["atmosphere"]["kzz"] = {}
             if not self_consistent_kzz:
                 kzz = self.inputs["atmosphere"]["profile"].get("kz", False)
@@ -1312,8 +1438,9 @@ class inputs:
         if verbose:
             self.interpret_run()
 
+        workflow = _climate.run_diseq_climate_workflow if diseq_chem else _climate.run_chemeq_climate_workflow
         (final_conv_flag, pressure, temp, dtdp, nstr_new, flux_net_ir_final, flux_net_v_final, flux_plus_final, chem_out,
-         cld_out, all_profiles, all_opd, all_kzz) = _climate.run_chemeq_climate_workflow(
+         cld_out, all_profiles, all_opd, all_kzz) = workflow(
             self, nofczns, nstr, TEMP1, pressure, AdiabatBundle, opacityclass, grav, rfaci, rfacv, tidal, Opagrid,
             CloudParameters, save_profile, all_profiles, all_opd, verbose=verbose, moist=moist, save_kzz=save_all_kzz,
             self_consistent_kzz=self_consistent_kzz)
