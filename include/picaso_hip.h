@@ -1044,6 +1044,35 @@ int picaso_lsf_convolve_dev(picaso_ctx *ctx, long nwno, const double *wl, int no
                             const double *den, const int *lo, const int *hi, int nrows, const picaso_regrid_row *rows,
                             double *out /* (nrows, nobs) */);
 
+/* ---- model grids fitted to data (reference analyze.py:305-388 fit_grid, :923-1000 custom_interp) ------------------------
+ * grid: device (nrows, nwave), the spectra of a grid of models.  Sample s is a table of kcount[s] (row, weight) pairs and
+ * a divisor, and its column i is
+ *   v_s[i] = (((0.0 + wts[s][0] grid[rows[s][0]][i]) + wts[s][1] grid[rows[s][1]][i]) + ...) / div[s]
+ * with the products and additions in table order, each rounded (no contraction): custom_interp's corner loop, its
+ * three-neighbour fallback (div = the sum of the weights), or one model as it is (one pair, weight 1, div 1).
+ * rows (nsamp, kmax) int32, wts (nsamp, kmax), kcount (nsamp) int32 in [1, kmax], div (nsamp): device; kmax in
+ * [1, PICASO_GRID_MAX_K]; nwave < 2^31.  The caller checks rows against [0, nrows) and kcount against [1, kmax] before it
+ * uploads them (picaso_amd/analyze.py); the kernels clamp both, so a broken table reads no memory outside grid.
+ * out_full (nsamp, nwave), or NULL: v_s.  out_binned (nsamp, nbins), or NULL: the mean of v_s over the columns
+ * [start[j], start[j + 1]) -- picaso_mean_regrid_dev's sum and bits, of columns formed in registers (no (nsamp, nwave)
+ * array in HBM); an empty bin is NaN.  start: device, nbins + 1 entries, as for picaso_mean_regrid_dev.
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+#define PICASO_GRID_MAX_K 64
+int picaso_grid_rows_dev(picaso_ctx *ctx, int nrows, long nwave, const double *grid, int nsamp, int kmax,
+                         const int *rows, const double *wts, const int *kcount, const double *div, double *out_full,
+                         int nbins, const int *start, double *out_binned);
+/* One number per sample from its binned model m = binned[s] (nsamp, ndata) and the data y, e (ndata), all on the device.
+ * mode 0, the retrieval likelihood (reference driver.py:296-326), offset / scaling / err_inf (nsamp) per sample:
+ *   out[s] = -0.5 sum_i(((y_i + offset) scaling - m_i)^2 / (e_i^2 + err_inf) + ln(2 pi (e_i^2 + err_inf)))
+ * mode 1, fit_grid's pair: shift[s] = mean(y - m) when fit_offset is set (the constant the reference's unweighted
+ * curve_fit solves for), else 0; best[s] (ndata) = m + shift; chi2[s] = sum_i(((y_i - best_i) / e_i)^2) / (ndata - numparams).
+ * The sums go through a tree that depends on ndata alone: a sample's bits depend neither on nsamp nor on its place.
+ * The arrays of the other mode may be NULL.  Bad arguments (mode 1: ndata - numparams <= 0): an error code, nothing is
+ * launched. */
+int picaso_grid_loglike_dev(picaso_ctx *ctx, int nsamp, int ndata, const double *binned, const double *y, const double *e,
+                            int mode, const double *offset, const double *scaling, const double *err_inf, double *out,
+                            int fit_offset, int numparams, double *shift, double *chi2, double *best);
+
 /* ---- correlated-k tables from line-by-line cross sections (reference opacity_factory.py:1927-1955) --------------------
  * replaces the bin loop of compute_ck_molecular for ONE P-T point.  xsec: device, the row of n_lbl cross sections.  Bin b
  * takes the points [lo[b], lo[b] + n[b]) of the row (lo, n: host, nbins entries each; the caller turns the reference's
