@@ -1030,6 +1030,36 @@ int picaso_transit_cf_dev(picaso_ctx *ctx, const double *z, const double *dz, in
 int picaso_mean_regrid_plane_dev(picaso_ctx *ctx, int nrows, long nwno, long pitch, int nbins, const int *start,
                                  const double *in, double *out);
 
+/* ---- photon attenuation (reference justplotit.py:426-536 photon_attenuation, :1019-1131 taumap, :1197-1282) -----------
+ * For ncol columns and three components k = 0 gas, 1 cloud, 2 Rayleigh: the level whose cumulative optical depth
+ *   c[0] = 0,  c[i + 1] = c[i] + d_k[i] m_k[i]      (a sequential sum, np.cumsum's bits; the product is rounded, then added)
+ * lies nearest to at_tau by the reference's find_nearest_2d / find_nearest_1d (:848-869), restated as one walk down the
+ * column: level i replaces the best level so far when |c[i] - at_tau| is strictly smaller, or when c[i] equals the best
+ * value.  So the shallower value wins a tie in distance, the deepest level wins among equal values, and a column of zeros
+ * gives the bottom level nlayer.  A column that holds a NaN gets level -1 and pressure NaN.  Negative entries are outside
+ * the contract.
+ *   planes: host table of 6 device pointers, d_0 d_1 d_2 m_0 m_1 m_2.  d_1 NULL: zeros; m_k NULL: no multiplier.
+ *   layout: host table of 18 longs, (pitch, stride, offset) of the six planes in that order: element (l, c) of a plane lies
+ *           at l * pitch + c * stride + offset.  Monochromatic (nlayer, nwno): (nwno, 1, 0); Gauss point g of a
+ *           correlated-k plane (nlayer, nwno, ngauss): (nwno * ngauss, ngauss, g).
+ *   plevel: host, copied on the stream: nlayer + 1 level pressures for all columns (per_column 0), or ncol sets of them,
+ *           set c for column c (per_column 1; at most 4 MiB).
+ *   one_zero_is_bottom: taumap's line :1082-1083 -- a cloud column whose only zero is c[0] gets level nlayer.
+ *   level:  device int (4, ncol): the three level indices, then the dominance code -- 0, 1 or 2 for the component whose
+ *           pressure is strictly smaller than both others (the masks of :509-511), -1 when none is.
+ *   pressure: device (3, ncol): plevel at those levels.
+ * One launch on the context's stream, one column per lane, no synchronisation. */
+int picaso_tau_level_dev(picaso_ctx *ctx, int nlayer, long ncol, const double *const *planes, const long *layout,
+                         const double *plevel, int per_column, double at_tau, int one_zero_is_bottom, int *level,
+                         double *pressure);
+/* out[k][r] = the mean of plane_k[r * pitch + i], i in [lo, hi), for nplanes (1 to 3) device planes of nrows rows and
+ * ncols columns (replaces the np.mean lines of reference picaso/justplotit.py:1264-1274).  One wave per row and plane sums
+ * lane-strided partial sums and folds them by a butterfly: the order depends on the window alone, the sum lies within
+ * (n - 1) 2^-53 sum|x| of the exact one.  An empty window (hi <= lo) gives NaN, as np.mean of an empty slice; a window of
+ * one column is exact.  out: device (3, nrows), rows k >= nplanes are not written. */
+int picaso_band_mean_rows_dev(picaso_ctx *ctx, int nrows, long ncols, long pitch, long lo, long hi, int nplanes,
+                              const double *plane0, const double *plane1, const double *plane2, double *out);
+
 /* ---- spectra convolved with a line-spread function (reference driver.py:338-381, conv_non_uniform_R) -----------------
  * out[r][i] = sum_k v_r[k] g_ik / sum_k g_ik over the model columns k in [lo[i], hi[i]), g_ik = exp(-(wl[k] - centre[i])^2
  * / den[i]): a Gaussian of sigma_i = centre_i / R_i / 2.355 (den = 2 sigma^2, formed by the caller) evaluated at the

@@ -25,12 +25,14 @@ def cf_grid(opacityclass_or_wno, R):
     return wavenumber, regrid.regrid_plan(opacityclass_or_wno, newx=wavenumber)
 
 
-def _binned(ctx, cf, wno, R, grid_of):
-    """``cf``: a ``(nrows, nwno)`` DeviceArray -> ``(wavenumber, host array)``, binned on the device when ``R`` is given."""
+def _binned(ctx, cf, wno, R, grid_of, grid=cf_grid):
+    """``cf``: a ``(nrows, nwno)`` DeviceArray -> ``(wavenumber, host array)``, binned on the device when ``R`` is given.
+    ``grid(grid_of, R)`` -> ``(wavenumber, plan)``: ``cf_grid`` for the contribution functions, ``attenuation.r_grid`` for
+    the functions whose reference bins with ``mean_regrid(..., R=R)`` itself."""
     nrows, nwno = cf.shape
     if R is None:
         return wno, cf.to_host() if nrows else np.zeros((0, nwno))
-    wavenumber, plan = cf_grid(grid_of, R)
+    wavenumber, plan = grid(grid_of, R)
     if not nrows:
         return wavenumber, np.zeros((0, plan.nbins))
     out = DeviceArray((nrows, plan.nbins), ctx)
@@ -40,22 +42,30 @@ def _binned(ctx, cf, wno, R, grid_of):
     return wavenumber, out.to_host()
 
 
-def _plane(x, nlayer, nwno, ctx):
-    """One plane of a ``full_output`` dictionary -- ``(nlayer, nwno, 1)`` as the reference stores it -- in HBM."""
+NO_CK = ("contribution functions of correlated-k tables (ngauss > 1) are not defined: the reference takes one Gauss "
+         "point of the planes")
+
+
+def _plane(x, nlayer, nwno, ctx, igauss=None):
+    """One plane of a ``full_output`` dictionary -- ``(nlayer, nwno, ngauss)`` as the reference stores it -- in HBM.
+    ``igauss`` None: monochromatic planes only (``ngauss`` 1); else the Gauss point ``[:, :, igauss]``, cut out on the host."""
     a = np.asarray(x, dtype=float)
     if a.ndim == 3:
-        if a.shape[2] != 1:
-            raise NotImplementedError("contribution functions of correlated-k tables (ngauss > 1) are not defined: the "
-                                      "reference takes one Gauss point of the planes")
-        a = a[:, :, 0]
+        if igauss is None:
+            if a.shape[2] != 1:
+                raise NotImplementedError(NO_CK)
+            igauss = 0
+        if not 0 <= igauss < a.shape[2]:
+            raise Exception("igauss=%d, but the planes hold %d Gauss point(s)" % (igauss, a.shape[2]))
+        a = a[:, :, igauss]
     if a.shape != (nlayer, nwno):
         raise Exception("contribution: a plane of shape %s, expected %s" % (a.shape, (nlayer, nwno)))
     return DeviceArray.from_host(a, ctx)
 
 
-def _from_dictionary(x):
+def _from_dictionary(x, igauss=None):
     """``(profile, planes, wno, grid_of, ctx)`` of a ``full_output`` dictionary (or of the dictionary ``spectrum(...,
-    full_output=True)`` returns, which holds it under ``'full_output'``)."""
+    full_output=True)`` returns, which holds it under ``'full_output'``).  ``igauss``: as for ``_plane``."""
     full = x.get("full_output", x)
     for k in ("taugas", "taucld", "tauray"):
         if full.get(k) is None:
@@ -63,34 +73,42 @@ def _from_dictionary(x):
     wno = np.asarray(full["wavenumber"], dtype=float)
     nlayer, nwno = len(full["layer"]["pressure"]), wno.size
     ctx = _lib.context()
-    planes = [_plane(full[k], nlayer, nwno, ctx) for k in ("taugas", "taucld", "tauray")]
+    planes = [_plane(full[k], nlayer, nwno, ctx, igauss) for k in ("taugas", "taucld", "tauray")]
     return full, planes, wno, wno, ctx
 
 
-def _check_case(opa, dimension):
+def _check_case(opa, dimension, ck=False):
     if dimension != "1d":
         raise NotImplementedError("contribution functions: only dimension='1d' is supported")
     if opa is None:
         raise Exception("contribution: an inputs object needs the opacity object (opacityclass=)")
-    if opa.ngauss > 1:
-        raise NotImplementedError("contribution functions of correlated-k tables (ngauss > 1) are not defined: the "
-                                  "reference takes one Gauss point of the planes")
+    if opa.ngauss > 1 and not ck:
+        raise NotImplementedError(NO_CK)
 
 
-def _from_case(bundle, opa, dimension):
-    """The same from an ``inputs`` object: the atmosphere as ``get_contribution`` sets it up, TAUGAS / TAURAY from the gas
-    stage and TAUCLD from the cloud tables, all three on the device (``taucld`` None: no cloud).  Nothing that a later
-    ``spectrum()`` reads is written: the plan's coefficient cache is left alone, as in ``optics.species_opacity``."""
+def _case_planes(bundle, opa, dimension, ck=False):
+    """``(atm, planes, wno, grid_of, ctx)`` of an ``inputs`` object: the atmosphere as ``get_contribution`` sets it up,
+    TAUGAS / TAURAY from the gas stage and TAUCLD from the cloud tables, all three on the device (``taucld`` None: no
+    cloud).  ``ck``: correlated-k tables are allowed and TAUGAS is then ``(nlayer, nwno, ngauss)``, the Gauss index fastest;
+    TAURAY and TAUCLD have no Gauss axis.  Nothing that a later ``spectrum()`` reads is written: the plan's coefficient
+    cache is left alone, as in ``optics.species_opacity``."""
     from .spectrum import _setup_atmosphere
-    _check_case(opa, dimension)
+    _check_case(opa, dimension, ck)
     inp = bundle.inputs
     atm = _setup_atmosphere(inp, opa, opa.wno)
     opa.get_opacities(atm, exclude_mol=inp["atmosphere"]["exclude_mol"])
-    nlayer, nwno, ctx = atm.c.nlayer, opa.nwno, opa.ctx
-    taugas, tauray = DeviceArray((nlayer, nwno), ctx), DeviceArray((nlayer, nwno), ctx)
-    optics._gas_call(opa, nlayer, taugas=taugas, tauray=tauray, ngauss=1,
+    nlayer, nwno, ngauss, ctx = atm.c.nlayer, opa.nwno, opa.ngauss, opa.ctx
+    taugas = DeviceArray((nlayer, nwno) if ngauss == 1 else (nlayer, nwno, ngauss), ctx)
+    tauray = DeviceArray((nlayer, nwno), ctx)
+    optics._gas_call(opa, nlayer, taugas=taugas, tauray=tauray, ngauss=ngauss,
                      **optics._gas_tables(opa, optics._layer_factors(atm, opa)))
-    return atm.as_dict(), [taugas, optics._cloud_opd_device(atm, opa), tauray], opa.wno, opa, ctx
+    return atm, [taugas, optics._cloud_opd_device(atm, opa), tauray], opa.wno, opa, ctx
+
+
+def _from_case(bundle, opa, dimension):
+    """``_case_planes`` with the atmosphere as its ``full_output`` dictionary, as ``_from_dictionary`` returns it."""
+    atm, planes, wno, grid_of, ctx = _case_planes(bundle, opa, dimension)
+    return atm.as_dict(), planes, wno, grid_of, ctx
 
 
 def _source(x, opacityclass, dimension):

@@ -32,6 +32,7 @@ from .planes import cloud_free_top as _cloud_free_top                           
 from .convolve import ConvolvePlan, conv_non_uniform_R, convolve_plan               # noqa: F401  (jdi.convolve_plan)
 from .regrid import RegridPlan, regrid_plan                                         # noqa: F401  (jdi.regrid_plan)
 from .contribution import thermal_contribution, transmission_contribution           # noqa: F401  (jdi.thermal_contribution)
+from .attenuation import cloud_optics_1d, heatmap_taus, photon_attenuation, taumap   # noqa: F401  (jdi.photon_attenuation)
 from .opacity_factory import compute_ck, compute_ck_molecular                        # noqa: F401  (jdi.compute_ck)
 from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
                        _fetch, _interp_axis, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,

@@ -1535,18 +1535,20 @@ def species_names(opacityclass):
     return list(pl["cia_pairs"]) + mols + ["rayleigh", "cloud"]
 
 
-def _cloud_opd_device(atm, opa, fthin_cld=None, do_holes=False):
+def _cloud_opd_device(atm, opa, fthin_cld=None, do_holes=False, key="opd"):
     """TAUCLD (optics.py:309-315) as an ``(nlayer, nwno)`` device plane, or None for a cloud-free atmosphere (read as
-    zeros).  Tables on their own grid are regridded on the device (``regrid_rows``: numpy.interp's bits)."""
+    zeros).  Tables on their own grid are regridded on the device (``regrid_rows``: numpy.interp's bits).  ``key``: another
+    of the cloud tables (``'w0'``, ``'g0'``) by the same route; the thinning applies to ``'opd'`` alone."""
     if getattr(atm, "cloud_free", False):
         return None
     cld = atm.layer["cloud"]
     nlayer, nwno = atm.c.nlayer, opa.nwno
+    holes = do_holes and key == "opd"
     if isinstance(cld, CloudTables) and np.size(cld.wno) == nwno and not _options().host_regrid:
-        return regrid_rows(cld.in_wno, cld.compact["opd"], _wno_device(opa, cld.wno), opa.ctx,
-                           scale=fthin_cld if do_holes else None)
-    t = np.ascontiguousarray(np.broadcast_to(np.asarray(cld["opd"], dtype=float), (nlayer, nwno)))
-    return DeviceArray.from_host(fthin_cld * t if do_holes else t, opa.ctx)
+        return regrid_rows(cld.in_wno, cld.compact[key], _wno_device(opa, cld.wno), opa.ctx,
+                           scale=fthin_cld if holes else None)
+    t = np.ascontiguousarray(np.broadcast_to(np.asarray(cld[key], dtype=float), (nlayer, nwno)))
+    return DeviceArray.from_host(fthin_cld * t if holes else t, opa.ctx)
 
 
 def species_opacity(atmosphere, opacityclass, at_tau=None, fthin_cld=None, do_holes=False):
