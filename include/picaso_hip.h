@@ -180,6 +180,49 @@ int picaso_get_reflected_1d_dev(picaso_ctx *ctx, int nlevel, int nwno, long plan
 int picaso_reflected_1d_can_derive(int nlevel, long plane_pitch, int numg, int numt, const double *ubar0,
                                    const double *ubar1, double cos_theta, int single_phase, int multi_phase, double frac_c,
                                    int toon_coefficients, int get_lvl_flux);
+
+/* Seals: the level planes of a RESIDENT set of all eleven planes verified once instead of in every launch.
+ *
+ * A launch that is handed tau, tau_og and gcos2 tests in every wave of every layer that they are what the kernel would
+ * form itself, and reads the three planes (27 % of the plane bytes at 90 layers) to do so; the kernels that are told the
+ * planes are absent skip both.  picaso_reflected_planes_seal_dev makes the test once, with the solver's own unfused
+ * operations, over exactly the rows the solver reads:
+ *     PICASO_SEAL_TAU     tau[0] is +0.0 (the bit pattern) and tau[i+1] == tau[i] + dtau[i]           for i < nlayer
+ *     PICASO_SEAL_TAU_OG  tau_og[0] is +0.0 and tau_og[i+1] == tau_og[i] + dtau_og[i]                 for i + 1 < nlayer
+ *                         (row nlayer of tau_og is never read and not looked at)
+ *     PICASO_SEAL_GCOS2   gcos2[i] == 0.5 * ftau_ray[i]                                               for i < nlayer
+ * (a NaN fails its comparison), waits for the result, returns the flags in *flags_out (may be NULL) and records the set:
+ * its eleven addresses, nlevel, nwno, plane_pitch and the flags, per device, for every context of the process.  All or
+ * nothing: only a set with all three flags (PICASO_SEAL_LEVELS) is ever used; any other is recorded as not derivable.
+ * Bits 3 and up are reserved (the pattern of a set without cloud).
+ *
+ * picaso_get_reflected_1d_dev / _batch_dev then treat tau, tau_og and gcos2 of a sealed set as NULL when the same eleven
+ * addresses arrive with the same nlevel, nwno and plane_pitch, picaso_reflected_1d_can_derive holds for the call, and the
+ * launch takes a kernel that knows the pattern at compile time (five disk angles in the zero-phase geometry: the fused
+ * launch of the large grids, its batched form, the cooperative kernel of the small ones; a batch: every member sealed).
+ * Every other call is handed all eleven planes as before.  The results are the same bits either way.  PICASO_AMD_REFL_
+ * ALL_PLANES=1 or PICASO_AMD_REFL_GENERIC=1 in the environment switch the substitution off.
+ *
+ * THE CONTRACT.  A seal is the caller's promise that the planes are not written through any other path until they are
+ * unsealed or freed -- the role a `const` plays in C.  The library drops a seal by itself when it sees the bytes change
+ * or go away: picaso_dev_free of a block that holds one of the planes, a picaso_memcpy_h2d / _h2d_async / _h2d_2d /
+ * _d2d / picaso_memset whose destination overlaps one, picaso_pool_trim and picaso_ctx_destroy (every seal of the
+ * device / of the context's blocks).  It cannot see a kernel write them (an entry point given a sealed plane as its
+ * OUTPUT, the caller's own kernels, a peer device): call picaso_reflected_planes_unseal first, with the address of any
+ * byte of any plane of the set.  Unsealing what is not sealed is not an error.
+ *
+ * picaso_reflected_seal_stat: *seals = sets of the context's device that are sealed with all three flags right now,
+ * *hits = launches on that device that used one, since the process started (either may be NULL). */
+#define PICASO_SEAL_TAU 1
+#define PICASO_SEAL_TAU_OG 2
+#define PICASO_SEAL_GCOS2 4
+#define PICASO_SEAL_LEVELS 7
+int picaso_reflected_planes_seal_dev(picaso_ctx *ctx, int nlevel, int nwno, long plane_pitch, const double *dtau,
+                                     const double *tau, const double *w0, const double *cosb, const double *gcos2,
+                                     const double *ftau_cld, const double *ftau_ray, const double *dtau_og,
+                                     const double *tau_og, const double *w0_og, const double *cosb_og, int *flags_out);
+int picaso_reflected_planes_unseal(picaso_ctx *ctx, const void *any_plane_ptr);
+int picaso_reflected_seal_stat(picaso_ctx *ctx, long *seals, long *hits);
 /* `nspec` spectra of one shape and one option set in ONE launch (the reference runs the
  * spectra of a retrieval or the phases of a curve as separate processes -- driver.py:405-426,
  * justdoit.py:4741-4777 -- each calling get_reflected_1d, fluxes.py:1009-1413).  Every pointer argument of

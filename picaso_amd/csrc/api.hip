@@ -1,5 +1,6 @@
 // Host side of the C ABI (include/picaso_hip.h): context, memory plumbing, argument marshalling.
 #include "common.hpp"
+#include "planeseal.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -254,7 +255,10 @@ void picaso_ctx_destroy(picaso_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &kv : ctx->pool) (void)hipFree(kv.second);
-    for (auto &kv : ctx->live) (void)hipFree(kv.first);
+    for (auto &kv : ctx->live) {
+        seal_invalidate(ctx->device, kv.first, kv.second);
+        (void)hipFree(kv.first);
+    }
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->lvl_scratch) (void)hipFree(ctx->lvl_scratch);
     if (ctx->ck_scratch) (void)hipFree(ctx->ck_scratch);
@@ -317,6 +321,7 @@ int picaso_dev_free(picaso_ctx *ctx, void *dptr)
     if (it == ctx->live.end()) return fail(ctx, "picaso_dev_free: %p was not allocated by picaso_dev_malloc", dptr);
     const size_t size = it->second;
     ctx->live.erase(it);
+    seal_invalidate(ctx->device, dptr, size);            // the address may come back with other contents
     if (ctx->pool_bytes + size > picaso_ctx::POOL_CAP) {
         PZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
         PZ_HIP(ctx, hipFree(dptr));
@@ -345,6 +350,7 @@ int picaso_pool_trim(picaso_ctx *ctx)
 {
     if (!ctx) return fail(nullptr, "null context");
     PZ_HIP(ctx, hipSetDevice(ctx->device));
+    seal_drop_device(ctx->device);
     return pool_release_all(ctx);
 }
 // Host <-> device copies of up to STAGE_MAX_COPY bytes go through the context's pinned bounce buffer
@@ -366,6 +372,7 @@ int picaso_memcpy_h2d(picaso_ctx *ctx, void *dst, const void *src, size_t bytes)
     if (!ctx) return fail(nullptr, "null context");
     if (bytes == 0) return 0;
     PZ_HIP(ctx, hipSetDevice(ctx->device));
+    seal_invalidate(ctx->device, dst, bytes);
     if (bytes > picaso_ctx::STAGE_MAX_COPY) {
         PZ_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
         PZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -463,6 +470,7 @@ int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, 
     if (!ctx || !dst || !pinned_src) return fail(ctx, "picaso_memcpy_h2d_async: null argument");
     if (bytes == 0) return 0;
     PZ_HIP(ctx, hipSetDevice(ctx->device));
+    seal_invalidate(ctx->device, dst, bytes);
     PZ_HIP(ctx, hipMemcpyAsync(dst, pinned_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return 0;
 }
@@ -477,12 +485,14 @@ int picaso_mark_wait(picaso_ctx *ctx, void *mark)
 }
 int picaso_memcpy_d2d(picaso_ctx *ctx, void *dst, const void *src, size_t bytes)
 {
+    if (ctx) seal_invalidate(ctx->device, dst, bytes);
     PZ_HIP(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return 0;
 }
 int picaso_memcpy_h2d_2d(picaso_ctx *ctx, void *dst, size_t dpitch, const void *src, size_t spitch,
                          size_t width, size_t height)
 {
+    if (ctx && height) seal_invalidate(ctx->device, dst, (height - 1) * dpitch + width);
     PZ_HIP(ctx, hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyHostToDevice,
                                  ctx->stream));
     PZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -500,6 +510,7 @@ int picaso_memcpy_d2h_2d(picaso_ctx *ctx, void *dst, size_t dpitch, const void *
 }
 int picaso_memset(picaso_ctx *ctx, void *dst, int value, size_t bytes)
 {
+    if (ctx) seal_invalidate(ctx->device, dst, bytes);
     PZ_HIP(ctx, hipMemsetAsync(dst, value, bytes, ctx->stream));
     return 0;
 }
@@ -570,6 +581,49 @@ struct ReflBatchHost {
     const double *cos_theta;
 };
 
+// May this call (all eleven planes given, TOA intensity only, one column per wavelength) run as if tau, tau_og and gcos2
+// had been left out?  Yes when every spectrum's eleven addresses carry a seal with all flags (planeseal.hip) AND the
+// launch then takes a kernel that knows the pattern at compile time -- k_reflected_toa / _batch <5, false, true, true,
+// false, 3> or k_reflected_coop<true, 3>: five angles, zero-phase geometry, the reference's default options.  Every other
+// shape (other angle counts, angle groups, the one-wave-per-SIMD BIG form, other options) would get the RUN-TIME
+// derived form, which is slower than the eleven-plane kernel (0.264 ms against 0.224 ms), and
+// keeps its planes.  The shape tests restate what reflected_1d_core and launch1d (toon_reflected.hip) decide further
+// down; where they disagree the launch is still correct (a run-time derived kernel, same bits), only slower.
+static bool reflected_seal_applies(picaso_ctx *ctx, int nlevel, int nwno, long plane_pitch, int numg, int numt,
+                                   const double *const one[11], const double *ubar0, const double *ubar1, double cos_theta,
+                                   int single_phase, int multi_phase, double frac_c, int toon_coefficients,
+                                   const ReflBatchHost *bt)
+{
+    const int nang = numg * numt, nspec = bt ? bt->nspec : 1, ngeom = bt ? bt->ngeom : 1;
+    if (nang != 5) return false;
+    for (int s = 0; s < ngeom; ++s) {
+        const double ct = bt ? bt->cos_theta[s] : cos_theta;
+        const double *u0 = ubar0 + (size_t)s * nang, *u1 = ubar1 + (size_t)s * nang;
+        if (ct != 1.0) return false;
+        for (int k = 0; k < nang; ++k)
+            if (u0[k] != u1[k]) return false;
+        // (also where PICASO_AMD_REFL_ALL_PLANES / PICASO_AMD_REFL_GENERIC switch the substitution off)
+        if (!picaso_reflected_1d_can_derive(nlevel, plane_pitch, numg, numt, u0, u1, ct, single_phase, multi_phase, frac_c,
+                                            toon_coefficients, 0))
+            return false;
+    }
+    long coop_cols = 64L * ctx->ncu;
+    if (const char *e = getenv("PICASO_AMD_REFL_COOP_COLS")) coop_cols = atol(e);
+    const bool coop = !bt && nwno <= coop_cols && !getenv("PICASO_AMD_REFL_NO_COOP");
+    if (!coop) {
+        const int group = reflected_angle_group(ctx, nwno, nang, nspec);
+        if (group == 1 || (group > 1 && group < nang && ((nang + group - 1) / group) * group <= MAX_ANGLES)) return false;
+        if (angle_chunks(nang).size() != 1) return false;
+        if ((long)nspec * ((nwno + 255L) / 256) * 4 <= 1024 && !getenv("PICASO_AMD_REFL_NO_BIG")) return false;   // BIG
+    }
+    for (int s = 0; s < nspec; ++s) {
+        const double *pl[11];
+        for (int j = 0; j < 11; ++j) pl[j] = bt ? bt->plane[j][s] : one[j];
+        if (!seal_derivable(ctx->device, pl, nlevel, nwno, plane_pitch)) return false;
+    }
+    return true;
+}
+
 static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper, long plane_pitch, int numg,
                                 int numt, const double *dtau, const double *tau, const double *w0,
                                 const double *cosb, const double *gcos2, const double *ftau_cld,
@@ -610,6 +664,23 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
     PZ_TRY(check_phase_options(ctx, single_phase, multi_phase, toon_coefficients));
     PZ_HIP(ctx, hipSetDevice(ctx->device));
     const int nang = numg * numt;
+    // a sealed set: its level planes were verified when they entered the device, the launch forms them itself
+    ReflBatchHost bt_sealed;
+    std::vector<const double *> absent;
+    if (!derived && ncolper == 1 && get_toa_intensity && !get_lvl_flux) {
+        const double *const pl[11] = {dtau, tau, w0, cosb, gcos2, ftau_cld, ftau_ray, dtau_og, tau_og, w0_og, cosb_og};
+        if (reflected_seal_applies(ctx, nlevel, nwno, plane_pitch, numg, numt, pl, ubar0, ubar1, cos_theta, single_phase,
+                                   multi_phase, frac_c, toon_coefficients, bt)) {
+            tau = tau_og = gcos2 = nullptr;
+            if (bt) {
+                absent.assign((size_t)nspec, nullptr);
+                bt_sealed = *bt;
+                bt_sealed.plane[1] = bt_sealed.plane[4] = bt_sealed.plane[8] = absent.data();
+                bt = &bt_sealed;
+            }
+            seal_count_hit(ctx->device);
+        }
+    }
     if (get_lvl_flux) {
         if (!flux_minus_all || !flux_plus_all || !flux_minus_midpt_all || !flux_plus_midpt_all)
             return fail(ctx, "get_reflected_1d: get_lvl_flux=1 needs the four level-flux outputs");

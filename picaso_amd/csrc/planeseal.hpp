@@ -1,0 +1,17 @@
+// Seals of resident reflected plane sets (planeseal.hip): what the memory plumbing and the reflected launcher of
+// api.hip need from the registry.  Not part of the C ABI.
+#pragma once
+#include <cstddef>
+
+namespace pz {
+
+// true when the eleven addresses (REFLECTED_PLANES order) with these sizes carry a seal whose flags are all set
+bool seal_derivable(int device, const double *const planes[11], int nlevel, int nwno, long pitch);
+// a launch took the LEVELS variant because of a seal
+void seal_count_hit(int device);
+// drop every seal of the device with a plane that overlaps [p, p + bytes): the bytes are about to change or to go away
+void seal_invalidate(int device, const void *p, size_t bytes);
+// drop every seal of the device
+void seal_drop_device(int device);
+
+}  // namespace pz

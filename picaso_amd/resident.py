@@ -12,9 +12,10 @@ from ._lib import addr, check, f64, load, ptr, ptr_array
 from .device import DeviceArray
 from .planes import REFLECTED_PLANES, SH_PLANES
 
-def upload_scene(scene, keys, w_lo=None, w_hi=None, ctx=None):
+def upload_scene(scene, keys, w_lo=None, w_hi=None, ctx=None, seal=True):
     """Upload the named (rows, nwno) planes / (nwno) vectors of a host scene dict, optionally only
-    the wavelength shard [w_lo, w_hi)."""
+    the wavelength shard [w_lo, w_hi).  ``seal``: a set that holds all of ``REFLECTED_PLANES`` as ``(nlayer | nlevel,
+    nwno)`` planes is sealed (``seal_reflected_planes``): every array is this call's own, nothing else writes them."""
     out = {}
     for k in keys:
         a = f64(scene[k])
@@ -24,7 +25,36 @@ def upload_scene(scene, keys, w_lo=None, w_hi=None, ctx=None):
             out[k] = DeviceArray.from_host(a[w_lo:w_hi], ctx)
         else:
             out[k] = DeviceArray.from_host_columns(a, w_lo, w_hi, ctx)
+    if seal and all(k in out for k in REFLECTED_PLANES):
+        nlevel, nwno = out["tau"].shape[0], out["tau"].shape[-1]
+        rows = {k: (nlevel if k in ("tau", "tau_og") else nlevel - 1) for k in REFLECTED_PLANES}
+        if nlevel >= 2 and all(out[k].shape == (rows[k], nwno) for k in REFLECTED_PLANES):
+            seal_reflected_planes(out["tau"].ctx, nlevel, nwno, out)
     return out
+
+
+def seal_reflected_planes(ctx, nlevel, nwno, planes, plane_pitch=None):
+    """Verify once that ``tau`` / ``tau_og`` / ``gcos2`` of a resident set of all eleven planes are what the kernels would
+    form themselves, and record it (``picaso_reflected_planes_seal_dev``): later ``reflected_1d`` / ``reflected_1d_batch``
+    calls on the same DeviceArrays then skip the three planes where that is faster.  Returns the flags (7: sealed).  The
+    caller's promise: nothing writes the planes until they are freed or ``unseal_reflected_planes`` is called."""
+    flags = ctypes.c_int(0)
+    pitch = nwno if plane_pitch is None else plane_pitch
+    check(load().picaso_reflected_planes_seal_dev(ctx, nlevel, nwno, pitch, *[addr(planes[k]) for k in REFLECTED_PLANES],
+                                                  ctypes.byref(flags)), ctx)
+    return flags.value
+
+
+def unseal_reflected_planes(ctx, plane):
+    """Drop the seal of the set that ``plane`` (a DeviceArray or an address inside one) belongs to."""
+    check(load().picaso_reflected_planes_unseal(ctx, addr(plane)), ctx)
+
+
+def reflected_seal_stat(ctx):
+    """``(seals, hits)``: sealed sets alive on the context's device, launches that used one."""
+    n, h = ctypes.c_long(0), ctypes.c_long(0)
+    check(load().picaso_reflected_seal_stat(ctx, ctypes.byref(n), ctypes.byref(h)), ctx)
+    return n.value, h.value
 
 
 def reflected_can_derive(nlevel, nwno, numg, numt, ubar0, ubar1, cos_theta, single_phase, multi_phase, frac_c,
