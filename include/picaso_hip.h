@@ -1170,6 +1170,26 @@ int picaso_ck_from_xsec_dev(picaso_ctx *ctx, long n_lbl, const double *xsec, int
  * of the current one run; picaso_ctx_wait / picaso_sync order it. */
 int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, size_t bytes);
 
+/* ---- prediction bands: order statistics of every column (reference retrieval.py:199-310, get_evaluations) --------------
+ * The reference stacks the model at n_draws posterior samples and reduces the stack per wavelength (and per pressure level)
+ * through ultranest's PredictionBand.get_line(q) = scipy.stats.mstats.mquantiles(ys, q, axis=0)[0].  y: device, (nsamp,
+ * ncol) with a row stride of ld >= ncol doubles; it is read once and never written.  k, gamma: host, nq entries each, the
+ * rows of mquantiles' table for the nq levels (picaso_amd/retrieval.py: quantile_table).  For every column, with x the
+ * column in np.sort order (-inf < finite < +inf < NaN, every NaN last whatever its sign),
+ *   nsamp >= 2:  out[i][c] = (1. - gamma[i]) * x[k[i] - 1] + gamma[i] * x[k[i]]
+ *   nsamp == 1:  out[i][c] = x[0]
+ * two rounded products and one rounded addition, nothing contracted and no shortcut at gamma = 0 or 1 (0 * inf is NaN, as
+ * in numpy).  A NaN read back as an order statistic is a quiet NaN.  -0.0 and +0.0 compare equal, so out equals numpy's by
+ * value.  A workgroup sorts a tile of adjacent columns in LDS (csrc/quantile.hip); a column's bits depend on its own
+ * values alone, not on ncol, ld, its position or the launch geometry.  out: device, (nq, ncol).
+ * nsamp in [1, PICASO_BANDS_MAX_DRAWS] (one padded column fills the 128 KiB LDS array), nq in [1, PICASO_BANDS_MAX_Q],
+ * ncol in [1, 2^31 - 1]; for nsamp >= 2 every k[i] in [1, nsamp - 1]; every gamma[i] in [0, 1].
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+#define PICASO_BANDS_MAX_DRAWS 16384
+#define PICASO_BANDS_MAX_Q 32
+int picaso_column_quantiles_dev(picaso_ctx *ctx, int nsamp, long ncol, const double *y, long ld, int nq, const int *k,
+                                const double *gamma, double *out /* (nq, ncol) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,9 @@ The tables are built on the host with the reference's own expressions in vectori
 products and additions in table order with numpy's rounding, so an interpolated spectrum has ``custom_interp``'s bits,
 and its binned form those of ``mean_regrid`` of it.  Only the sums over the data points (the offset, chi squared, the log
 likelihood) run in another order than numpy's pairwise one; they differ from the reference by rounding.
+
+``bands_batch`` ends a gridtrieval: the quantile lines (median, 1, 2 and 3 sigma) over the spectra interpolated to the
+posterior's draws, read off the resident result by ``picaso_column_quantiles_dev`` (``picaso_amd/retrieval.py``).
 """
 import itertools
 
@@ -504,6 +507,33 @@ def loglike_batch(goals, fitter, grid_name, data_name, offset=0, scaling=1, err_
     data = fitter.data[data_name]
     logl = grid_loglike(ctx, binned, S, data['y_data'], data['e_data'], offset, scaling, err_inf)
     return (logl, binned.to_host()) if return_binned else logl
+
+
+@_lib.serialized
+def bands_batch(goals, fitter, grid_name, data_name=None, q=None):
+    """The prediction bands of a gridtrieval: the quantile lines ``q`` (levels or a dictionary of them; default
+    ``retrieval.SIGMA_QUANTILES``, the reference's seven) over the spectra interpolated to the posterior draws ``goals``
+    (S, d) -- ``retrieval.bands(interp_batch(goals, ...), q)`` bit for bit, (len(q), nwave), or with ``data_name`` the
+    bands of the spectra binned to that data set, ``bands`` of ``loglike_batch(..., return_binned=True)[1]``,
+    (len(q), ndata).  The interpolated spectra stay in HBM: ``picaso_column_quantiles_dev`` reads them there and only the
+    lines come back."""
+    from . import retrieval
+    p = retrieval._levels(retrieval.SIGMA_QUANTILES if q is None else q)
+    if not 1 <= p.size <= retrieval.MAX_Q:
+        raise Exception("bands_batch: %d levels; one call takes 1 to %d" % (p.size, retrieval.MAX_Q))
+    tables = interp_tables(goals, fitter, grid_name)
+    S = tables[0].shape[0]
+    if S > retrieval.MAX_DRAWS:
+        raise Exception("bands_batch: %d draws; a column is sorted in LDS and takes at most %d" % (S, retrieval.MAX_DRAWS))
+    k, gamma = retrieval.quantile_table(S, p)
+    dev = fitter._device(grid_name)
+    if data_name is None:
+        stack = grid_rows(dev["ctx"], dev["spectra"], dev["nrows"], dev["nwave"], *tables, full=True)
+    else:
+        stack = grid_rows(dev["ctx"], dev["spectra"], dev["nrows"], dev["nwave"], *tables,
+                          plan=fitter._plan(grid_name, data_name))
+    out = retrieval.column_quantiles(stack, k, gamma).to_host()
+    return np.ascontiguousarray(out[:, ::-1]) if data_name is None and dev["flip"] else out
 
 
 def custom_interp(final_goal, fitter, grid_name, to_interp='spectra', array_to_interp=None):
