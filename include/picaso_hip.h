@@ -1190,6 +1190,31 @@ int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, 
 int picaso_column_quantiles_dev(picaso_ctx *ctx, int nsamp, long ncol, const double *y, long ld, int nq, const int *k,
                                 const double *gamma, double *out /* (nq, ncol) */);
 
+/* ---- equilibrium chemistry from a table (reference justdoit.py:3106-3199 chem_interp; :3517-3664 premix_3d, chemeq_3d) ----
+ * replaces chem_interp for ANY number of points in one launch: the reference runs it once per profile and, for a 3-D run,
+ * once per (lon, lat) column in a joblib pool that re-reads the grid file per column.  log_abunds: device (nrow, nspecies)
+ * row-major, log10 of the abundances, rows temperature-major; temperature it owns the rows row_start[it] .. row_start[it] +
+ * nc_p[it] - 1, the first nc_p[it] pressures of p_log_grid.  t_inv_grid (ntemp) = 1 / T, p_log_grid (npres) = log10 P, nc_p,
+ * row_start (ntemp): device, formed by the caller as chem_interp forms them (picaso_amd/chemistry.py: table_grids).
+ * temperature, p_log (npoints): device; p_log = log10 P is taken on the host, so that it has numpy's bits.  Per point, with
+ * t_inv = 1 / T (a NaN makes every comparison false: index 0):
+ *   t_low = last i with t_inv_grid[i] > t_inv, else 0; ntemp - 1 becomes ntemp - 2;  t_hi = t_low + 1
+ *   p_low = min(last i with p_log_grid[i] <= p_log, else 0; nc_p[t_hi] - 3);          p_hi = p_low + 1
+ *   t_i = (t_inv - t_inv_grid[t_low]) / (t_inv_grid[t_hi] - t_inv_grid[t_low]),  p_i likewise on p_log_grid
+ *   x = ((((1 - t_i) (1 - p_i)) a + (t_i (1 - p_i)) b) + (t_i p_i) c) + ((1 - t_i) p_i) d
+ * a, b, c, d the rows [t_low, p_low], [t_hi, p_low], [t_hi, p_hi], [t_low, p_hi]; IEEE divisions, every product and sum
+ * rounded in this order, nothing contracted: x equals the numpy form's exponent bit for bit.  log10_out != 0 stores x, else
+ * 10**x, within 4 ulp of numpy's 10.0**x for |x| <= 300 (the rounding error of x log2(10) is carried along; -inf gives 0).
+ * sel: device, nsel column indices of the table in the caller's order, or NULL for all columns (nsel = nspecies).
+ * out: device (nsel, npoints), the point index fastest.  The caller checks the table (every nc_p in [3, npres], nrow = the sum
+ * of nc_p) and sel against [0, nspecies); the kernel clamps rows and columns, so a broken table reads no memory outside
+ * log_abunds.  npoints == 0: nothing is launched.  The grids travel through LDS: ntemp * 16 + npres * 8 <= 65 536 bytes.
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_chem_interp_dev(picaso_ctx *ctx, int nrow, int nspecies, const double *log_abunds, int ntemp, int npres,
+                           const double *t_inv_grid, const double *p_log_grid, const int *nc_p, const int *row_start,
+                           long npoints, const double *temperature, const double *p_log, int nsel, const int *sel,
+                           int log10_out, double *out /* (nsel, npoints) */);
+
 #ifdef __cplusplus
 }
 #endif

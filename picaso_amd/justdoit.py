@@ -19,6 +19,7 @@ import collections
 import copy
 
 import os
+import warnings
 
 import numpy as np
 
@@ -1170,38 +1171,87 @@ class inputs:
         table, ``ntemp - 2`` at or above its top, so both ends extrapolate along 1/T); the lower pressure index is the last
         table pressure at or below the level's (0 below the table), held to ``nc_p[t_hi] - 3`` of the UPPER temperature's
         column, whose ragged edge therefore also extrapolates.  The species columns are added to the profile."""
+        from . import chemistry
         prof = self.inputs["atmosphere"]["profile"]
-        plevel, tlevel = np.asarray(prof["pressure"], dtype=float), np.asarray(prof["temperature"], dtype=float)
-        t_inv, p_log = 1 / tlevel, np.log10(plevel)
-        tab_t, tab_p = np.asarray(chem_grid["temperature"], dtype=float), np.asarray(chem_grid["pressure"], dtype=float)
-        species = [k for k in chem_grid.keys() if k not in ("pressure", "temperature")]
-        with np.errstate(divide="ignore"):
-            log_abunds = np.log10(np.stack([np.asarray(chem_grid[k], dtype=float) for k in species], axis=1))
-        nc_p = np.unique(tab_t, return_counts=True)[1]               # per temperature, in ascending temperature
-        _, first = np.unique(tab_t, return_index=True)
-        temps = tab_t[np.sort(first)]                                # in order of appearance, as the reference reads them
-        p_grid = np.unique(tab_p)
-        p_log_grid = np.log10(p_grid[p_grid > 0])
-        t_inv_grid = 1 / temps
-        nt = len(t_inv_grid)
-
-        def last_where(mask):                                        # last true index of every row, 0 when none
-            idx = mask.shape[1] - 1 - np.argmax(mask[:, ::-1], axis=1)
-            return np.where(mask.any(axis=1), idx, 0)
-        t_low = last_where(t_inv_grid[None, :] > t_inv[:, None])
-        t_low[t_low == nt - 1] = nt - 2
-        t_hi = t_low + 1
-        p_low = np.minimum(last_where(p_log_grid[None, :] <= p_log[:, None]), nc_p[t_hi] - 3)
-        p_hi = p_low + 1
-        start = np.concatenate(([0], np.cumsum(nc_p)))               # first row of every temperature
-        t_i = ((t_inv - t_inv_grid[t_low]) / (t_inv_grid[t_hi] - t_inv_grid[t_low]))[:, None]
-        p_i = ((p_log - p_log_grid[p_low]) / (p_log_grid[p_hi] - p_log_grid[p_low]))[:, None]
-        abunds = 10 ** (((1 - t_i) * (1 - p_i) * log_abunds[start[t_low] + p_low, :])
-                        + (t_i * (1 - p_i) * log_abunds[start[t_hi] + p_low, :])
-                        + (t_i * p_i * log_abunds[start[t_hi] + p_hi, :])
-                        + ((1 - t_i) * p_i * log_abunds[start[t_low] + p_hi, :]))
+        species, abunds = chemistry.interp_numpy(prof["temperature"], prof["pressure"], chem_grid)
         for i, k in enumerate(species):
             prof[k] = abunds[:, i]
+
+    def channon_grid_low(self, filename=None):
+        """Abundances of the profile from ``chemistry/visscher_abunds_m+0.0_co1.0`` (reference justdoit.py:3097-3104): the
+        file reader (``chemistry.read_channon_grid_low``: a CSV whose leading index column is dropped), then ``chem_interp``,
+        on the host.  ``filename=None``: the file under ``$picaso_refdata``."""
+        from . import chemistry
+        if filename is None:
+            filename = os.path.join(chemistry._refdata(), "chemistry", "visscher_abunds_m+0.0_co1.0")
+        self.chem_interp(chemistry.read_channon_grid_low(filename))
+
+    def _profiles_3d(self, who):
+        """The profile dictionaries a 3-D chemistry call fills: ``profile_3d`` and every phase of ``profile_4d``."""
+        atm = self.inputs["atmosphere"]
+        profs = []
+        if atm.get("profile_3d") is not None:
+            profs.append(atm["profile_3d"])
+        for pr in (atm.get("profile_4d") or []):
+            if not any(pr is q for q in profs):
+                profs.append(pr)
+        if not profs:
+            raise Exception("%s: no 3-D profile to add chemistry to. You must run atmosphere_3d (or atmosphere_4d) before "
+                            "running this function" % who)
+        return profs
+
+    def _chemistry_3d(self, table, who):
+        """Every species of ``table`` at every (level, facet) of ``profile_3d`` -- and of every phase of ``profile_4d`` when
+        that is set -- in one launch of ``chemistry.chem_interp_batch``; the species are added to the profile
+        dictionaries, replacing columns of the same name."""
+        from . import chemistry
+        profs = self._profiles_3d(who)
+        temps, press = [], []
+        for pr in profs:
+            t = np.asarray(pr["temperature"], dtype=float)
+            p = np.asarray(pr["pressure"], dtype=float)
+            if t.shape[0] != p.shape[0]:
+                raise Exception("%s: temperature has %d levels, pressure %d" % (who, t.shape[0], p.shape[0]))
+            temps.append(t)
+            press.append(np.broadcast_to(p.reshape((-1,) + (1,) * (t.ndim - 1)), t.shape))
+        sizes = np.cumsum([0] + [t.size for t in temps])
+        out = chemistry.chem_interp_batch(np.concatenate([t.reshape(-1) for t in temps]),
+                                          np.concatenate([p.reshape(-1) for p in press]), table)
+        for i, pr in enumerate(profs):
+            for k, v in out.items():
+                pr[k] = np.ascontiguousarray(v[sizes[i]:sizes[i + 1]].reshape(temps[i].shape))
+        self.nlevel = len(profs[0]["pressure"])
+
+    @_lib.serialized
+    def chemeq_3d(self, c_o=None, log_mh=0.0, cto_absolute=0.55, n_cpu=1):
+        """Equilibrium chemistry of the 2121-point Visscher grid on the 3-D profiles (reference justdoit.py:3590-3664): the
+        file nearest to ``cto_absolute`` (solar 0.55) and ``log_mh`` (``chemistry.visscher_2121``) is read ONCE, and every
+        species is interpolated at every (level, facet) of ``inputs['atmosphere']['profile_3d']`` in one launch on the
+        device; the reference runs ``chemeq_visscher_2121`` -- file read included -- per (lon, lat) column in ``n_cpu``
+        joblib workers.  The species join the profile as ``(nlevel, ng, nt)`` arrays (``(nlevel,)`` for a temperature that
+        all facets share), replacing columns of the same name.  With ``profile_4d`` set (``atmosphere_4d``) all phases go
+        into the same launch.  ``c_o`` (the old input, relative to solar): ``cto_absolute = 0.55 * c_o`` with the reference's
+        warning.  ``n_cpu`` is accepted and ignored."""
+        from . import chemistry
+        if isinstance(c_o, (float, int)):
+            cto_absolute = c_o * 0.55
+            warnings.warn('I see you have entered keyword c_o. This value used to be assocated with a relative, not absolute '
+                          'c/o ratio. We have now switched to using cto_absolute, where solar=0.55. In picaso 4 we will still '
+                          'allow the old input c_o but in a future PICASO 5 we will discontinue that option and cto input '
+                          'will be defaulted to absolute values.')
+        self._profiles_3d("chemeq_3d")                                 # nothing to work on: say so before a file is read
+        self._chemistry_3d(chemistry.visscher_2121(cto_absolute, log_mh), "chemeq_3d")
+
+    @_lib.serialized
+    def premix_3d(self, opa, n_cpu=1):
+        """The chemistry table of the opacity object (``opa.full_abunds``) on the 3-D profiles (reference
+        justdoit.py:3517-3588): as ``chemeq_3d``, one launch for every (level, facet).  An opacity object without
+        ``full_abunds`` is an exception.  ``n_cpu`` is accepted and ignored."""
+        table = getattr(opa, "full_abunds", None)
+        if table is None:
+            raise Exception("premix_3d: the opacity object carries no chemistry table (full_abunds); use chemeq_3d, or an "
+                            "opacity object that was built with one")
+        self._chemistry_3d(table, "premix_3d")
 
     def chemeq_visscher_1060(self, *a, **k):
         raise NotImplementedError("chemeq_visscher_1060 (the chemistry grids shipped with the reference) is not implemented: "
