@@ -263,8 +263,8 @@ def setup(inp, opa, wno):
 def setup_facets(inp, opa, wno, prof_f):
     """The facet-form ATMSETUP of the 3-D path (``justdoit.picaso``: columns ``(nlevel, nfacets)`` for what depends on the
     facet, ``(nlevel, 1)`` for what does not; the pressure grid is shared) from ``picaso_host_setup_facets``, with the tall
-    plan and per-layer coefficients ``optics.gas_stage_facets`` would form (facet-major ``nfacets * nlayer`` layers) attached
-    as ``atm._fast_tall``.  ``None`` outside the C function's scope."""
+    plan and per-layer coefficients ``optics.tall_plan`` would form (facet-major ``nfacets * nlayer`` layers) attached as
+    ``atm._fast_tall``, which ``tall_plan`` hands to every 3-D opacity route.  ``None`` outside the C function's scope."""
     if _options().py_setup:
         return None
     if not _in_scope(opa) or inp["atmosphere"].get("exclude_mol", 1) != 1:

@@ -389,7 +389,7 @@ def prepare_3d(bundle, opa, subs, calculation, opt, slot=None, regrid=None):
             return None
         tabs_sig = first[3]
     nmol, ncont, nray = len(plan["molecules"]), len(plan["cia_pairs"]), len(factors[2])
-    if (nmol * 56 + ncont * 12 + nray * 8 + 8) * nfac * nlayer > 3600 * 1024:
+    if optics.gas_table_bytes(nmol, ncont, nray, nfac * nlayer) > optics.GAS_TABLE_BUDGET:
         return None                 # the per-layer tables of the tall atmosphere must fit ONE table slot (one launch)
     do_r, do_t = "reflected" in legs, "thermal" in legs
     linear = opa.query_method == "linear"

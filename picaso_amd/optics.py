@@ -23,13 +23,14 @@ import io
 import math
 import os
 import sqlite3
+import types
 
 import numpy as np
 
 from . import _lib
 from ._lib import check, f64, load, ptr, ptr_array
 from .atmsetup import CloudTables
-from .device import DeviceArray, regrid_rows
+from .device import DeviceArray, broadcast_facets, regrid_facets, regrid_rows
 from .options import current as _options
 from .planes import OUT_NAMES
 from .rayleigh import available_rayleigh
@@ -822,11 +823,16 @@ def gas_stage(atm, opa, taugas, tauray, mix=None):
     _gas_call(opa, nlayer, taugas=taugas, tauray=tauray, ngauss=ngauss, mix=mix, **_gas_tables(opa, fac[1]))
 
 
-def _gas_tables(opa, factors, molecules=True):
+def _gas_tables(opa, factors, molecules=True, sl=None):
     """The tables, rows, weights and per-layer coefficients of ``opa._plan`` as keyword arguments of ``_gas_call`` /
-    ``_gas_args``; ``factors`` = ``_layer_factors``.  ``molecules=False``: without the molecular term."""
+    ``_gas_args``; ``factors`` = ``_layer_factors``.  ``molecules=False``: without the molecular term.  ``sl``: only
+    these layers (one launch's facets of a tall atmosphere)."""
     pl = opa._plan
     mol_fac, cont_fac, ray_names, ray_fac = factors
+    if sl is not None:
+        pl = dict(pl, rows=pl["rows"][:, sl], wts=pl["wts"][:, sl],
+                  **{k: pl[k][sl] for k in ("cia_rows", "cia_wts") if k in pl})
+        mol_fac, cont_fac, ray_fac = mol_fac[:, sl], cont_fac[:, sl], ray_fac[:, sl]
     cont_tabs = [opa._cia[p] for p in pl["cia_pairs"]]
     if not molecules:
         mol_tabs, mol_mode = [], 0
@@ -846,7 +852,6 @@ def _gas_tables(opa, factors, molecules=True):
 
 def types_namespace_layer(atm_f, tlayer):
     """One facet's view of a facet-form atmosphere: what raman_plane_host reads."""
-    import types
     return types.SimpleNamespace(c=atm_f.c, layer={"temperature": tlayer})
 
 
@@ -947,6 +952,94 @@ def raman_pollack(nlayer, wave, table=None):
     return np.repeat(row[None, :], nlayer, axis=0)
 
 
+# The per-layer tables of ONE gas launch travel in one upload slot of the context: ``gas_launch`` (csrc/optics.hip) packs
+# them and ``picaso_ctx::SLOT_BYTES`` (csrc/common.hpp, 4 MiB) bounds what it may pack.  The budget leaves the rest of the
+# slot to the table pointers, the alignment padding and gas_launch's 64 spare bytes.
+GAS_TABLE_BUDGET = 3600 * 1024
+
+
+def gas_table_bytes(nmol, ncont, nray, nlayer, cont_wts=None):
+    """What the per-layer tables of a gas launch over ``nlayer`` layers count against ``GAS_TABLE_BUDGET``: the packing
+    of ``gas_launch`` -- per molecule 4 int rows, 4 weights and a coefficient; per continuum pair 1 int row and a
+    coefficient, or with ``cont_wts`` (correlated-k: two bracketing temperatures) 2 int rows, 2 weights and a coefficient;
+    per Rayleigh species a coefficient -- plus 8 spare bytes per layer."""
+    cont = (8 + 16 + 8) if cont_wts is not None else (4 + 8)
+    return (nmol * (16 + 32 + 8) + ncont * cont + nray * 8 + 8) * nlayer
+
+
+def _facet_major(a, nlayer, nfac):
+    """A layer column ``(nlayer, nfacets | 1)`` as the tall atmosphere's vector ``(nfacets * nlayer,)``, facet-major."""
+    a = np.asarray(a, dtype=float).reshape(nlayer, -1)
+    return np.ascontiguousarray(np.broadcast_to(a, (nlayer, nfac)).T).ravel()
+
+
+def _tall_atmosphere(atm_f, nfac, mixingratios=False):
+    """The facets of ONE facet-form atmosphere (``ATMSETUP`` with ``(nlevel, nfacets)`` columns) as a tall atmosphere of
+    ``nfacets * nlayer`` layers, facet-major: what the table search of ``get_opacities`` reads.  ``mixingratios``: with
+    the mixing ratios, which only the correlated-k search reads."""
+    nlayer = atm_f.c.nlayer
+    layer = {k: _facet_major(atm_f.layer[k], nlayer, nfac) for k in ("temperature", "pressure")}
+    if mixingratios:
+        mix = atm_f.layer["mixingratios"]
+        layer["mixingratios"] = {m: _facet_major(mix[m].values if hasattr(mix[m], "values") else mix[m], nlayer, nfac)
+                                 for m in atm_f.molecules}
+    return types.SimpleNamespace(c=types.SimpleNamespace(nlayer=nfac * nlayer, pconv=atm_f.c.pconv), layer=layer,
+                                 molecules=atm_f.molecules, continuum_molecules=atm_f.continuum_molecules)
+
+
+def tall_plan(atm_f, opa, nfac, exclude_mol=1, ck=False, monochromatic=False):
+    """Table rows / weights (``opa._plan``) and per-layer coefficients (``_layer_factors``) of the TALL atmosphere of a
+    3-D spectrum: the ``nfac * nlayer`` layers of all facets, facet-major.  From ``picaso_host_setup_facets`` when the
+    facet-form set-up went through it (``atm_f._fast_tall``; ``ck``: only its premixed plan), else with the mirror's
+    table search on the flattened layer columns; ``monochromatic``: that search must not find correlated-k tables."""
+    fast = getattr(atm_f, "_fast_tall", None)
+    if fast is not None and fast[2] is opa and exclude_mol == 1 and (not ck or fast[0].get("premixed")):
+        opa._plan = fast[0]
+        opa.molecular_opa, opa.continuum_opa = (None if ck else _LazyPlanes(opa, "mol")), _LazyPlanes(opa, "cia")
+        return fast[0], fast[1]
+    opa.get_opacities(_tall_atmosphere(atm_f, nfac, mixingratios=ck), exclude_mol=exclude_mol)
+    if monochromatic and opa._plan.get("premixed"):
+        raise Exception("the 3-D path takes monochromatic opacities")
+    return opa._plan, _layer_factors(atm_f, opa)
+
+
+def _tall_gas_launches(opa, factors, nlayer, nfac):
+    """The gas launches of a tall atmosphere (``tall_plan``) as ``(f0, f1, sl, tables)``: the facets ``[f0, f1)`` of one
+    launch, their layers ``sl`` and their ``_gas_tables``.  One launch takes as many whole facets as
+    ``GAS_TABLE_BUDGET`` holds per-layer tables of."""
+    whole = _gas_tables(opa, factors)
+    per_facet = gas_table_bytes(len(whole["mol_tabs"]), len(whole["cont_tabs"]), len(whole["ray_tabs"]), nlayer,
+                                whole["cont_wts"])
+    fchunk = max(1, GAS_TABLE_BUDGET // per_facet)
+    for f0 in range(0, nfac, fchunk):
+        f1 = min(nfac, f0 + fchunk)
+        sl = slice(f0 * nlayer, f1 * nlayer)
+        yield f0, f1, sl, (whole if f1 - f0 == nfac else _gas_tables(opa, factors, sl=sl))
+
+
+def _raman_factor_tall(atm_f, opa, raman, nfac):
+    """The Raman factor of a tall atmosphere on the device as ``(d_rf, rf_rows)``: none (the constant), Pollack's row for
+    every layer and facet (``rf_rows = 0``) or Oklopcic's facet-major plane ``(nfacets, nlayer, nwno)`` from one launch
+    (``rf_rows = nlayer``), of which every chunk of facets reads its own rows.  Pollack's factor is read as one row also
+    when ``raman_device`` hands over a host-made ``(nlayer, nwno)`` plane (PICASO_AMD_RAMAN_PLANES): all its rows are
+    that row, and the plane has no rows for the facets of a second chunk."""
+    if raman == 1:
+        return raman_device(atm_f, opa, 1)[0], 0
+    if raman == 0:
+        nlayer = atm_f.c.nlayer
+        d_rf = DeviceArray((nfac, nlayer, opa.nwno), opa.ctx)
+        raman_oklopcic_device(opa, _facet_major(atm_f.layer["temperature"], nlayer, nfac), d_rf)
+        return d_rf, nlayer
+    return None, 0
+
+
+def _test_mode_code(test_mode):
+    """``test_mode`` of the mixing launches: 0 off, 1 'rayleigh', 2 any other."""
+    if test_mode is None:
+        return 0
+    return 1 if test_mode == "rayleigh" else 2
+
+
 def gas_stage_facets(atm_f, opa, nfac, tg3, tr3, exclude_mol=1):
     """TAUGAS / TAURAY of every facet from ONE facet-form atmosphere (``ATMSETUP`` with
     ``(nlevel, nfacets)`` columns): the facet stack ``(nfacets, nlayer, nwno)`` is a tall atmosphere of
@@ -954,50 +1047,53 @@ def gas_stage_facets(atm_f, opa, nfac, tg3, tr3, exclude_mol=1):
     launch run once over all facets (chunked only so the per-layer tables fit one upload slot) instead
     of once per facet (reference loop: justdoit.py:437-471).  Same arithmetic per element as the
     per-facet path: the results are bit-identical (tests/test_ck_optics.py)."""
-    import types
     nlayer = atm_f.c.nlayer
-    ntot = nfac * nlayer
+    _, factors = tall_plan(atm_f, opa, nfac, exclude_mol, monochromatic=True)
+    for f0, f1, _, tables in _tall_gas_launches(opa, factors, nlayer, nfac):
+        _gas_call(opa, (f1 - f0) * nlayer, taugas=tg3.row_block(f0), tauray=tr3.row_block(f0), ngauss=1, **tables)
 
-    def flat(a):                      # (nlayer, nfacets | 1) -> facet-major (nfacets*nlayer,)
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=float), (nlayer, nfac)).T).ravel()
-    tall = types.SimpleNamespace(
-        c=types.SimpleNamespace(nlayer=ntot, pconv=atm_f.c.pconv),
-        layer={"temperature": flat(atm_f.layer["temperature"]), "pressure": flat(atm_f.layer["pressure"])},
-        molecules=atm_f.molecules, continuum_molecules=atm_f.continuum_molecules)
-    fast = getattr(atm_f, "_fast_tall", None)
-    if fast is not None and fast[2] is opa and exclude_mol == 1:       # formed with the atmosphere (fastsetup.setup_facets)
-        opa._plan = pl = fast[0]
-        opa.molecular_opa, opa.continuum_opa = _LazyPlanes(opa, "mol"), _LazyPlanes(opa, "cia")
-        mol_fac, cont_fac, ray_names, ray_fac = fast[1]
-    else:
-        opa.get_opacities(tall, exclude_mol=exclude_mol)
-        pl = opa._plan
-        if pl.get("premixed"):
-            raise Exception("the 3-D path takes monochromatic opacities")
-        mol_fac, cont_fac, ray_names, ray_fac = _layer_factors(atm_f, opa)
-    mol_tabs = [(opa._mol_log if opa.query_method == "linear" else opa._mol_raw)[m] for m in pl["molecules"]]
-    mol_mode = 1 if opa.query_method == "linear" else 0
-    cont_tabs = [opa._cia[p] for p in pl["cia_pairs"]]
-    ray_tabs = [opa._ray[m] for m in ray_names]
-    per_layer = len(mol_tabs) * (16 + 32 + 8) + len(cont_tabs) * (4 + 8) + len(ray_tabs) * 8 + 8
-    fchunk = max(1, int((3600 * 1024) // (per_layer * nlayer)))         # one 4 MB upload slot per launch (common.hpp SLOT_BYTES)
-    for f0 in range(0, nfac, fchunk):
-        f1 = min(nfac, f0 + fchunk)
-        sl = slice(f0 * nlayer, f1 * nlayer)
-        cont_rows = np.repeat(pl["cia_rows"][None, sl], len(cont_tabs), axis=0) if cont_tabs else None
-        _gas_call(opa, (f1 - f0) * nlayer, mol_tabs, pl["rows"][:, sl] if mol_tabs else None,
-                  pl["wts"][:, sl] if mol_tabs else None, mol_fac[:, sl] if mol_tabs else None, cont_tabs,
-                  cont_rows, cont_fac[:, sl] if cont_tabs else None, ray_tabs, ray_fac[:, sl] if ray_tabs else None,
-                  tg3.row_block(f0), tr3.row_block(f0), mol_mode=mol_mode, ngauss=1)
+
+def _gas_raman_facet_form(atm_f, opa, nfac, tg3, tr3, raman, exclude_mol):
+    """Front end of ``compute_opacity_facets`` from ONE facet-form atmosphere: the batched gas stage into ``tg3`` /
+    ``tr3`` and the Raman factor ``(d_rf, rf_rows)`` -- on the device, or under PICASO_AMD_RAMAN_PLANES from the
+    host function, one plane per facet."""
+    nlayer = atm_f.c.nlayer
+    gas_stage_facets(atm_f, opa, nfac, tg3, tr3, exclude_mol=exclude_mol)
+    if raman in (0, 1) and _options().raman_planes:
+        tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float), (nlayer, nfac))
+        rf3 = [raman_plane_host(types_namespace_layer(atm_f, tl[:, f]), opa, raman) for f in range(nfac)]
+        return DeviceArray.from_host(np.stack(rf3), opa.ctx), nlayer
+    return _raman_factor_tall(atm_f, opa, raman, nfac)
+
+
+def _gas_raman_facet_loop(atms, opa, numg, numt, tg3, tr3, raman, exclude_mol):
+    """The same from one atmosphere per facet (``atms[g][t]``, PICASO_AMD_FACET_LOOP): the reference's loop, one table
+    search, gas launch and Raman plane per facet."""
+    nlayer = atms[0][0].c.nlayer
+    on_dev = not _options().raman_planes
+    rf3 = []                                                  # host planes, one per facet
+    d_rf3 = DeviceArray((numg * numt, nlayer, opa.nwno), opa.ctx) if raman == 0 and on_dev else None
+    for g in range(numg):
+        for t in range(numt):
+            f, atm = g * numt + t, atms[g][t]
+            opa.get_opacities(atm, exclude_mol=exclude_mol)
+            gas_stage(atm, opa, tg3.row_block(f), tr3.row_block(f))
+            if raman in (0, 1) and not on_dev:
+                rf3.append(raman_plane_host(atm, opa, raman))
+            if d_rf3 is not None:                             # Oklopcic: this facet's layer temperatures
+                raman_oklopcic_device(opa, atm.layer["temperature"], d_rf3.row_block(f))
+    if raman == 1 and on_dev:                                 # Pollack: one row for every layer and facet
+        return raman_device(atms[0][0], opa, raman)
+    return (DeviceArray.from_host(np.stack(rf3), opa.ctx) if rf3 else d_rf3), nlayer
 
 
 def compute_opacity_facets(atms, opacityclass, numg, numt, stream=2, delta_eddington=True, test_mode=None,
                            raman=0, clouds_3d=None, exclude_mol=1, want=None):
     """3-D path: the 13 ``(nlayer|nlevel, nwno, numg, numt)`` planes ``get_reflected_3d`` /
-    ``get_thermal_3d`` take, from one atmosphere per facet (``atms[g][t]``; reference
-    justdoit.py:444-471).  Gas + Rayleigh optical depths are gathered facet by facet into a
-    facet-major stack; one launch then mixes all facets (cloud inputs ``(nlayer, nwno, numg, numt)``
-    arrays ``opd``/``w0``/``g0`` or None) and writes the planes with the facet index fastest."""
+    ``get_thermal_3d`` take, from ONE facet-form atmosphere or one atmosphere per facet (``atms[g][t]``; reference
+    justdoit.py:444-471).  Gas + Rayleigh optical depths are gathered into a facet-major stack; one launch then
+    mixes all facets (cloud inputs ``(nlayer, nwno, numg, numt)`` arrays ``opd``/``w0``/``g0``, tables on a grid of
+    their own, or None) and writes the planes with the facet index fastest."""
     opa = opacityclass
     ctx = opa.ctx
     nfac = numg * numt
@@ -1005,96 +1101,11 @@ def compute_opacity_facets(atms, opacityclass, numg, numt, stream=2, delta_eddin
     if opa.ngauss != 1:
         raise Exception("compute_opacity_facets takes monochromatic opacities")
     tg3, tr3 = DeviceArray((nfac, nlayer, nwno), ctx), DeviceArray((nfac, nlayer, nwno), ctx)
-    on_dev = not _options().raman_planes
-    row_mode = raman == 1 and on_dev
-    rf3 = [] if raman in (0, 1) and not on_dev else None      # host planes, one per facet
-    d_rf3 = DeviceArray((nfac, nlayer, nwno), ctx) if raman == 0 and on_dev else None   # Oklopcic: layer temperatures
-    if not isinstance(atms, list):                            # one facet-form atmosphere: batched gas stage
-        atm_f = atms
-        gas_stage_facets(atm_f, opa, nfac, tg3, tr3, exclude_mol=exclude_mol)
-        if rf3 is not None:
-            tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float), (nlayer, nfac))
-            for f in range(nfac):
-                one = types_namespace_layer(atm_f, tl[:, f])
-                rf3.append(raman_plane_host(one, opa, raman))
-        if d_rf3 is not None:
-            tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float), (nlayer, nfac))
-            # all facets in one launch: the tall atmosphere's nfac * nlayer layer temperatures, facet-major
-            raman_oklopcic_device(opa, np.ascontiguousarray(tl.T).ravel(), d_rf3)
-        atms = None
-    for g in range(numg if atms is not None else 0):
-        for t in range(numt):
-            f = g * numt + t
-            opa.get_opacities(atms[g][t], exclude_mol=exclude_mol)
-            gas_stage(atms[g][t], opa, tg3.row_block(f), tr3.row_block(f))
-            if rf3 is not None:
-                rf3.append(raman_plane_host(atms[g][t], opa, raman))
-            if d_rf3 is not None:
-                raman_oklopcic_device(opa, atms[g][t].layer["temperature"], d_rf3.row_block(f))
-    d_rf, rf_rows = (DeviceArray.from_host(np.stack(rf3), ctx) if rf3 else d_rf3), nlayer
-    if row_mode:                                              # Pollack: one row for every layer and facet
-        d_rf, rf_rows = raman_device(atms[0][0] if isinstance(atms, list) else atm_f, opa, raman)
-    d_c = [None, None, None]
-    if clouds_3d is not None:
-        from .device import broadcast_facets, regrid_facets, regrid_rows
-        d_c = []
-        in_wno = clouds_3d.get("wavenumber") if isinstance(clouds_3d, dict) else None
-        if in_wno is not None and len(in_wno) == nwno and np.array_equal(in_wno, opa.wno):
-            in_wno = None
-        if in_wno is not None:
-            # tables on a wavenumber grid of their own (virga's 196 points): regridded on the device with numpy.interp's
-            # bits -- the reference's per-facet get_clouds -> wavelength.regrid (atmsetup.py:609-622) -- instead of
-            # (nlayer, nwno, nfacets) host arrays: 3 x 576 MB and seconds of numpy at 1e5 wavelengths x 64 facets
-            in_wno = np.asarray(in_wno, dtype=np.float64)
-            nin = in_wno.size
-            order = np.argsort(in_wno, kind="stable") if np.any(np.diff(in_wno) < 0) else None
-            d_x = _wno_device(opa, opa.wno)
-        if in_wno is not None and nin >= 2:
-            # the three tables in ONE upload and ONE launch: (3 nlayer[, nfacets], nin) rows, kept on the cloud dictionary
-            # while its arrays are the same objects (a spectrum() called again, the phases of a curve that share a map)
-            arrs = [clouds_3d[k] for k in ("opd", "w0", "g0")]
-            memo = _cloud_memo_get("rows", clouds_3d)
-            stamp = _table_fingerprint(arrs, clouds_3d["wavenumber"])
-            if memo is None or memo[1] != stamp:
-                tabs = [np.asarray(x, dtype=float) for x in arrs]
-                shared = all(t.size == nlayer * nin for t in tabs)
-                if shared:
-                    rows = np.concatenate([t.reshape(nlayer, nin) for t in tabs])
-                    rows = rows if order is None else rows[:, order]
-                else:
-                    rows = np.concatenate([np.moveaxis(np.broadcast_to(t.reshape(nlayer, nin, -1), (nlayer, nin, nfac)), 1, 2)
-                                           for t in tabs])
-                    rows = np.ascontiguousarray(rows if order is None else rows[:, :, order])
-                memo = (arrs, stamp, shared, np.ascontiguousarray(rows),
-                        np.ascontiguousarray(in_wno if order is None else in_wno[order]), {})
-                _cloud_memo_put("rows", clouds_3d, memo)
-            _, _, shared, rows, xp, resident_tabs = memo
-            key = (os.getpid(), getattr(ctx, "value", ctx))
-            if key not in resident_tabs:         # the compact tables stay in HBM with the dictionary (27 MB at 64 facets)
-                resident_tabs[key] = (DeviceArray.from_host(xp, ctx), DeviceArray.from_host(rows, ctx))
-            xp, rows = resident_tabs[key]
-            if shared:
-                d_all = regrid_rows(xp, rows, d_x, ctx)                                  # (3 nlayer, nwno)
-                d_c = [broadcast_facets(d_all.row_range(j * nlayer, (j + 1) * nlayer), nfac) for j in range(3)]
-            else:
-                d_all = regrid_facets(xp, rows, d_x, ctx)                                # (3 nlayer, nwno, nfacets)
-                d_c = [d_all.row_range(j * nlayer, (j + 1) * nlayer) for j in range(3)]
-            for d in d_c:
-                d._inputs = d_all
-        else:
-            for k in ("opd", "w0", "g0"):
-                a = np.asarray(clouds_3d[k], dtype=float)
-                if in_wno is not None:               # a single wavenumber: the value everywhere
-                    a = np.repeat(a.reshape(nlayer, 1, -1), nwno, axis=1)
-                    d_c.append(broadcast_facets(DeviceArray.from_host(np.ascontiguousarray(a[:, :, 0]), ctx), nfac)
-                               if a.shape[2] == 1 else DeviceArray.from_host(np.ascontiguousarray(a), ctx))
-                elif a.size == nlayer * nwno:        # one table for the whole disk: tiled over the facets on the device
-                    d_c.append(broadcast_facets(DeviceArray.from_host(a.reshape(nlayer, nwno), ctx), nfac))
-                else:
-                    d_c.append(DeviceArray.from_host(a.reshape(nlayer, nwno, nfac), ctx))
-    tm = 0
-    if test_mode is not None:
-        tm = 1 if test_mode == "rayleigh" else 2
+    if isinstance(atms, list):
+        d_rf, rf_rows = _gas_raman_facet_loop(atms, opa, numg, numt, tg3, tr3, raman, exclude_mol)
+    else:
+        d_rf, rf_rows = _gas_raman_facet_form(atms, opa, nfac, tg3, tr3, raman, exclude_mol)
+    d_c = [None, None, None] if clouds_3d is None else _cloud_planes_facet_fastest(clouds_3d, opa, nlayer, nfac)
     # only the planes the requested legs read are allocated and written (each is nfacets x 72 MB at
     # 1e5 wavelengths x 90 layers): 11 for reflected light, 3 for thermal emission
     out = {k: (DeviceArray(((nlayer + 1 if k in ("tau", "tau_og") else nlayer), nwno, numg, numt), ctx)
@@ -1102,7 +1113,7 @@ def compute_opacity_facets(atms, opacityclass, numg, numt, stream=2, delta_eddin
     check(load().picaso_compute_opacity_facets_dev(
         ctx, nlayer, nwno, nfac, ptr(tg3.addr), ptr(tr3.addr),
         *[ptr(d.addr) if d is not None else None for d in d_c], ptr(d_rf.addr) if d_rf is not None else None,
-        rf_rows, 0.99999, tm, 1 if delta_eddington else 0, stream,
+        rf_rows, 0.99999, _test_mode_code(test_mode), 1 if delta_eddington else 0, stream,
         *[ptr(out[k].addr) if out[k] is not None else None for k in OUT_NAMES]), ctx)
     return {k: v for k, v in out.items() if v is not None}
 
@@ -1194,29 +1205,6 @@ def _facet_major_cloud_tables(clouds_3d, nlayer, nfac, ctx, stamp=None):
     return memo[4][key] + (memo[2], nin)
 
 
-def tall_plan(atm_f, opa, nfac, exclude_mol=1):
-    """Table rows / weights (``opa._plan``) and per-layer coefficients (``_layer_factors``) of the TALL atmosphere of a
-    3-D spectrum: the ``nfac * nlayer`` layers of all facets, facet-major.  From ``picaso_host_setup_facets`` when the
-    facet-form set-up went through it (``atm_f._fast_tall``), else with the mirror's table search on the flattened
-    layer temperatures and pressures."""
-    nlayer = atm_f.c.nlayer
-    fast = getattr(atm_f, "_fast_tall", None)
-    if fast is not None and fast[2] is opa and exclude_mol == 1:
-        opa._plan = fast[0]
-        opa.molecular_opa, opa.continuum_opa = _LazyPlanes(opa, "mol"), _LazyPlanes(opa, "cia")
-        return fast[0], fast[1]
-    import types
-
-    def flat(a):
-        return np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=float), (nlayer, nfac)).T).ravel()
-    tall = types.SimpleNamespace(
-        c=types.SimpleNamespace(nlayer=nfac * nlayer, pconv=atm_f.c.pconv),
-        layer={"temperature": flat(atm_f.layer["temperature"]), "pressure": flat(atm_f.layer["pressure"])},
-        molecules=atm_f.molecules, continuum_molecules=atm_f.continuum_molecules)
-    opa.get_opacities(tall, exclude_mol=exclude_mol)
-    return opa._plan, _layer_factors(atm_f, opa)
-
-
 def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta_eddington=True, raman=2, exclude_mol=1,
                                 want=("dtau", "w0"), cloud_tables=None):
     """The planes of a 3-D spectrum WITHOUT cloud in facet-major layout ``(nfacets, nlayer, nwno)``, from one fused
@@ -1231,29 +1219,10 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
     ctx = opa.ctx
     nfac = numg * numt
     nlayer, nwno = atm_f.c.nlayer, opa.nwno
-    ntot = nfac * nlayer
-    pl, (mol_fac, cont_fac, ray_names, ray_fac) = tall_plan(atm_f, opa, nfac, exclude_mol)
-    mol_tabs = [(opa._mol_log if opa.query_method == "linear" else opa._mol_raw)[m] for m in pl["molecules"]]
-    mol_mode = 1 if opa.query_method == "linear" else 0
-    cont_tabs = [opa._cia[p] for p in pl["cia_pairs"]]
-    ray_tabs = [opa._ray[m] for m in ray_names]
-    # the Raman factor: none (the constant), Pollack's row for every layer and facet, or Oklopcic's plane per facet.
-    # rf_rows = nlayer: a facet-major plane, of which every chunk of facets reads its own rows.  Pollack's factor is read
-    # as one row (rf_rows = 0) also when raman_device hands over a host-made (nlayer, nwno) plane (PICASO_AMD_RAMAN_PLANES):
-    # all its rows are that row, and the plane has no rows for the facets of a second chunk
-    d_rf, rf_rows = None, 0
-    if raman == 1:
-        d_rf = raman_device(atm_f, opa, 1)[0]
-    elif raman == 0:
-        d_rf, rf_rows = DeviceArray((nfac, nlayer, nwno), ctx), nlayer
-        tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float), (nlayer, nfac))
-        raman_oklopcic_device(opa, np.ascontiguousarray(tl.T).ravel(), d_rf)      # all facets in one launch
+    _, factors = tall_plan(atm_f, opa, nfac, exclude_mol)
+    d_rf, rf_rows = _raman_factor_tall(atm_f, opa, raman, nfac)
     out = {k: DeviceArray((nfac, nlayer, nwno), ctx) for k in OUT_NAMES if k in want}
-    per_layer = len(mol_tabs) * (16 + 32 + 8) + len(cont_tabs) * (4 + 8) + len(ray_tabs) * 8 + 8
-    fchunk = max(1, int((3600 * 1024) // (per_layer * nlayer)))         # per-layer tables of a launch: one 4 MB slot
-    for f0 in range(0, nfac, fchunk):
-        f1 = min(nfac, f0 + fchunk)
-        sl = slice(f0 * nlayer, f1 * nlayer)
+    for f0, f1, sl, tables in _tall_gas_launches(opa, factors, nlayer, nfac):
         nl_c = (f1 - f0) * nlayer
         off = f0 * nlayer * nwno * 8
         cld_tab, keep = (0, None, None, None), None
@@ -1270,10 +1239,7 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
                *[ptr(out[k].addr + off) if k in out else None for k in OUT_NAMES], 0, *cld_tab)
         if keep is not None:
             out.setdefault("_cloud_chunks", []).append(keep)
-        cont_rows = np.repeat(pl["cia_rows"][None, sl], len(cont_tabs), axis=0) if cont_tabs else None
-        _gas_call(opa, nl_c, mol_tabs, pl["rows"][:, sl] if mol_tabs else None, pl["wts"][:, sl] if mol_tabs else None,
-                  mol_fac[:, sl] if mol_tabs else None, cont_tabs, cont_rows, cont_fac[:, sl] if cont_tabs else None,
-                  ray_tabs, ray_fac[:, sl] if ray_tabs else None, None, None, mol_mode=mol_mode, ngauss=1, mix=mix)
+        _gas_call(opa, nl_c, taugas=None, tauray=None, ngauss=1, mix=mix, **tables)
     out["_fm"] = True
     if d_rf is not None:
         out["_raman"] = d_rf              # the launch is asynchronous: its inputs live as long as its outputs
@@ -1282,17 +1248,82 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
     return out
 
 
+def _cloud_own_grid(clouds_3d, wno):
+    """The wavenumber grid the 3-D cloud tables ``clouds_3d`` come on, as ``(grid, order)``.  ``grid`` is None for tables
+    on the opacity grid ``wno`` (no ``wavenumber`` entry, or that very grid), else float64 as given: one wavenumber stands
+    for the value everywhere, two or more are regridded with numpy.interp's bits -- the reference's per-facet
+    get_clouds -> wavelength.regrid (atmsetup.py:609-622).  ``order``: the stable sort of a grid that decreases
+    somewhere, else None."""
+    in_wno = clouds_3d.get("wavenumber") if isinstance(clouds_3d, dict) else None
+    if in_wno is None or (np.size(in_wno) == len(wno) and np.array_equal(in_wno, wno)):
+        return None, None
+    in_wno = np.asarray(in_wno, dtype=np.float64).reshape(-1)
+    return in_wno, (np.argsort(in_wno, kind="stable") if np.any(np.diff(in_wno) < 0) else None)
+
+
+def _cloud_planes_facet_fastest(clouds_3d, opa, nlayer, nfac):
+    """The cloud inputs of ``compute_opacity_facets`` as three resident planes ``(nlayer, nwno, nfacets)``, the facet
+    index fastest.  Tables on a wavenumber grid of their own (virga's 196 points) are regridded on the device instead
+    of as (nlayer, nwno, nfacets) host arrays: 3 x 576 MB and seconds of numpy at 1e5 wavelengths x 64 facets."""
+    ctx, nwno = opa.ctx, opa.nwno
+    in_wno, order = _cloud_own_grid(clouds_3d, opa.wno)
+    if in_wno is not None and in_wno.size >= 2:
+        # the three tables in ONE upload and ONE launch: (3 nlayer[, nfacets], nin) rows, kept on the cloud dictionary
+        # while its arrays are the same objects (a spectrum() called again, the phases of a curve that share a map)
+        nin = in_wno.size
+        arrs = [clouds_3d[k] for k in ("opd", "w0", "g0")]
+        memo = _cloud_memo_get("rows", clouds_3d)
+        stamp = _table_fingerprint(arrs, clouds_3d["wavenumber"])
+        if memo is None or memo[1] != stamp:
+            tabs = [np.asarray(x, dtype=float) for x in arrs]
+            shared = all(t.size == nlayer * nin for t in tabs)
+            if shared:
+                rows = np.concatenate([t.reshape(nlayer, nin) for t in tabs])
+                rows = rows if order is None else rows[:, order]
+            else:
+                rows = np.concatenate([np.moveaxis(np.broadcast_to(t.reshape(nlayer, nin, -1), (nlayer, nin, nfac)), 1, 2)
+                                       for t in tabs])
+                rows = np.ascontiguousarray(rows if order is None else rows[:, :, order])
+            memo = (arrs, stamp, shared, np.ascontiguousarray(rows),
+                    np.ascontiguousarray(in_wno if order is None else in_wno[order]), {})
+            _cloud_memo_put("rows", clouds_3d, memo)
+        _, _, shared, rows, xp, resident_tabs = memo
+        key = (os.getpid(), getattr(ctx, "value", ctx))
+        if key not in resident_tabs:         # the compact tables stay in HBM with the dictionary (27 MB at 64 facets)
+            resident_tabs[key] = (DeviceArray.from_host(xp, ctx), DeviceArray.from_host(rows, ctx))
+        xp, rows = resident_tabs[key]
+        d_x = _wno_device(opa, opa.wno)
+        if shared:
+            d_all = regrid_rows(xp, rows, d_x, ctx)                                  # (3 nlayer, nwno)
+            d_c = [broadcast_facets(d_all.row_range(j * nlayer, (j + 1) * nlayer), nfac) for j in range(3)]
+        else:
+            d_all = regrid_facets(xp, rows, d_x, ctx)                                # (3 nlayer, nwno, nfacets)
+            d_c = [d_all.row_range(j * nlayer, (j + 1) * nlayer) for j in range(3)]
+        for d in d_c:
+            d._inputs = d_all
+        return d_c
+    d_c = []
+    for k in ("opd", "w0", "g0"):
+        a = np.asarray(clouds_3d[k], dtype=float)
+        if in_wno is not None:               # a single wavenumber: the value everywhere
+            a = np.repeat(a.reshape(nlayer, 1, -1), nwno, axis=1)
+            d_c.append(broadcast_facets(DeviceArray.from_host(np.ascontiguousarray(a[:, :, 0]), ctx), nfac)
+                       if a.shape[2] == 1 else DeviceArray.from_host(np.ascontiguousarray(a), ctx))
+        elif a.size == nlayer * nwno:        # one table for the whole disk: tiled over the facets on the device
+            d_c.append(broadcast_facets(DeviceArray.from_host(a.reshape(nlayer, nwno), ctx), nfac))
+        else:
+            d_c.append(DeviceArray.from_host(a.reshape(nlayer, nwno, nfac), ctx))
+    return d_c
+
+
 def _cloud_planes_facet_major(clouds_3d, opa, nlayer, nfac, ctx):
     """The cloud tables of the 3-D path as resident facet-major planes ``(d_opd, d_w0, d_g0, stride)``, each
     ``(nfacets | 1, nlayer, nwno)``; ``stride`` = elements between two facets (0: one set for the whole disk).  Tables on
-    a wavenumber grid of their own are regridded on the device with numpy.interp's bits -- the reference's per-facet
-    get_clouds -> wavelength.regrid (atmsetup.py:609-622) -- from the compact rows kept with the cloud dictionary
+    a wavenumber grid of their own are regridded on the device from the compact rows kept with the cloud dictionary
     (``_facet_major_cloud_tables``: re-uploaded when any byte of the caller's arrays changes)."""
     nwno = opa.nwno
-    in_wno = clouds_3d.get("wavenumber") if isinstance(clouds_3d, dict) else None
-    if in_wno is not None and np.size(in_wno) == nwno and np.array_equal(in_wno, opa.wno):
-        in_wno = None
-    if in_wno is not None and np.size(in_wno) >= 2:
+    in_wno, _ = _cloud_own_grid(clouds_3d, opa.wno)
+    if in_wno is not None and in_wno.size >= 2:
         tabs = _facet_major_cloud_tables(clouds_3d, nlayer, nfac, ctx)
         if tabs is None:
             raise Exception("clouds_3d: opd / w0 / g0 must hold nlayer x nwavenumber (x nfacets) numbers")
@@ -1327,66 +1358,25 @@ def compute_opacity_facet_major_ck(atm_f, opacityclass, numg, numt, stream=2, de
     them), then ``picaso_compute_opacity_facet_major_ck_dev``.  Each facet's numbers are those of
     ``compute_opacity_resident`` on that facet's atmosphere (tests/test_ck3d_gpu.py).  ``want``: the planes to write
     (default all 13).  The solvers: ``resident.reflected_3d_ck`` / ``thermal_3d_ck``."""
-    import types
     opa = opacityclass
     ctx = opa.ctx
     nfac = numg * numt
     nlayer, nwno, ngauss = atm_f.c.nlayer, opa.nwno, opa.ngauss
-    ntot = nfac * nlayer
-
-    def flat(a):                      # (nlayer, nfacets | 1) -> facet-major (nfacets*nlayer,)
-        a = np.asarray(a, dtype=float)
-        return np.ascontiguousarray(np.broadcast_to(a.reshape(nlayer, -1), (nlayer, nfac)).T).ravel()
-    mix = atm_f.layer["mixingratios"]
-    tall = types.SimpleNamespace(
-        c=types.SimpleNamespace(nlayer=ntot, pconv=atm_f.c.pconv),
-        layer={"temperature": flat(atm_f.layer["temperature"]), "pressure": flat(atm_f.layer["pressure"]),
-               "mixingratios": {m: flat(mix[m].values if hasattr(mix[m], "values") else mix[m]) for m in atm_f.molecules}},
-        molecules=atm_f.molecules, continuum_molecules=atm_f.continuum_molecules)
-    fast = getattr(atm_f, "_fast_tall", None)
-    if fast is not None and fast[2] is opa and fast[0].get("premixed") and exclude_mol == 1:
-        # the tall plan and coefficients came with the facet-form set-up (fastsetup.setup_facets)
-        opa._plan = pl = fast[0]
-        opa.continuum_opa, opa.molecular_opa = _LazyPlanes(opa, "cia"), None
-        mol_fac, cont_fac, ray_names, ray_fac = fast[1]
-    else:
-        opa.get_opacities(tall, exclude_mol=exclude_mol)
-        pl = opa._plan
-        mol_fac, cont_fac, ray_names, ray_fac = _layer_factors(atm_f, opa)
-    cont_tabs = [opa._cia[p] for p in pl["cia_pairs"]]
-    ray_tabs = [opa._ray[m] for m in ray_names]
-    mol_tabs = [pl.get("table", opa._kappa)]
+    pl, factors = tall_plan(atm_f, opa, nfac, exclude_mol, ck=True)
     taugas, tauray = DeviceArray((nfac, nlayer, nwno, ngauss), ctx), DeviceArray((nfac, nlayer, nwno), ctx)
-    per_layer = (16 + 32 + 8) + len(cont_tabs) * (8 + 16 + 8) + len(ray_tabs) * 8 + 8
-    fchunk = max(1, int((3600 * 1024) // (per_layer * nlayer)))         # per-layer tables of a launch: one 4 MB slot
-    for f0 in range(0, nfac, fchunk):
-        f1 = min(nfac, f0 + fchunk)
-        sl = slice(f0 * nlayer, f1 * nlayer)
-        cont_rows = np.repeat(pl["cia_rows"][None, sl], len(cont_tabs), axis=0) if cont_tabs else None
-        cont_wts = np.repeat(pl["cia_wts"][None, sl], len(cont_tabs), axis=0) if cont_tabs else None
-        _gas_call(opa, (f1 - f0) * nlayer, mol_tabs, pl["rows"][:, sl], pl["wts"][:, sl], mol_fac[:, sl], cont_tabs,
-                  cont_rows, cont_fac[:, sl] if cont_tabs else None, ray_tabs, ray_fac[:, sl] if ray_tabs else None,
-                  taugas.row_block(f0), tauray.row_block(f0), mol_mode=2, cont_wts=cont_wts, ngauss=ngauss)
-    # the Raman factor: none (the constant), Pollack's row for every layer and facet, or Oklopcic's plane per facet
-    d_rf, rf_rows = None, 0
-    if raman == 1:                       # one row, also from a host-made plane (see compute_opacity_facet_major)
-        d_rf = raman_device(atm_f, opa, 1)[0]
-    elif raman == 0:
-        d_rf, rf_rows = DeviceArray((nfac, nlayer, nwno), ctx), nlayer
-        tl = np.broadcast_to(np.asarray(atm_f.layer["temperature"], dtype=float).reshape(nlayer, -1), (nlayer, nfac))
-        raman_oklopcic_device(opa, np.ascontiguousarray(tl.T).ravel(), d_rf)      # all facets in one launch
+    for f0, f1, _, tables in _tall_gas_launches(opa, factors, nlayer, nfac):
+        _gas_call(opa, (f1 - f0) * nlayer, taugas=taugas.row_block(f0), tauray=tauray.row_block(f0), ngauss=ngauss,
+                  **tables)
+    d_rf, rf_rows = _raman_factor_tall(atm_f, opa, raman, nfac)
     d_cld = (None, None, None, 0, None)
     if clouds_3d is not None:
         d_cld = _cloud_planes_facet_major(clouds_3d, opa, nlayer, nfac, ctx)
-    tm = 0
-    if test_mode is not None:
-        tm = 1 if test_mode == "rayleigh" else 2
     out = {k: (DeviceArray((nfac, (nlayer + 1 if k in ("tau", "tau_og") else nlayer), nwno, ngauss), ctx)
                if (want is None or k in want) else None) for k in OUT_NAMES}
     check(load().picaso_compute_opacity_facet_major_ck_dev(
         ctx, nfac, nlayer, nwno, ngauss, ptr(taugas.addr), ptr(tauray.addr),
         *[ptr(d.addr) if d is not None else None for d in d_cld[:3]], d_cld[3],
-        ptr(d_rf.addr) if d_rf is not None else None, rf_rows, 0.99999, tm,
+        ptr(d_rf.addr) if d_rf is not None else None, rf_rows, 0.99999, _test_mode_code(test_mode),
         1 if delta_eddington else 0, stream,
         *[ptr(out[k].addr) if out[k] is not None else None for k in OUT_NAMES]), ctx)
     out = {k: v for k, v in out.items() if v is not None}

@@ -12,7 +12,8 @@ profiles, cloud slabs, a premixed ln-kappa table with 8 Gauss points).
 Shapes: layer counts hit every tail of the 6- and 10-layer tiles and of k_level_sums' 8-layer loop;
 wavelength counts sit on both sides of 8 column groups (the XCD-ordered block mapping) up to 1e5.  3-D:
 facet counts whose 1024-column blocks straddle wavelengths, 64 facets, and the chunked facet-major
-launches (12 molecules: chunks of 56 + 8 facets).
+launches (12 molecules: chunks of 56 + 8 facets; the correlated-k route and the facet-fastest route with cloud
+tables, which no affordable shape chunks, under a table budget cut down to five facets' worth).
 
 Tolerances, elementwise with the NaN pattern exact: TAUGAS / TAURAY / species planes 1e-13, the 13
 planes 1e-12; ``tau`` is np.cumsum of ``dtau`` and regridded cloud tables are numpy.interp's, bit for
@@ -382,13 +383,15 @@ def chunked():
     return T, atm_f, ones, _facet_refs(T, ones)
 
 
-def _count_gas_calls(monkeypatch):
+def _count_gas_calls(monkeypatch, tables=None):
     from picaso_amd import optics as px
     calls = []
     real = px._gas_call
 
     def spy(*a, **k):
         calls.append(a[1])                 # nlayer of the launch
+        if tables is not None:
+            tables.append(k)               # ... and its tables
         return real(*a, **k)
     monkeypatch.setattr(px, "_gas_call", spy)
     return calls
@@ -451,3 +454,58 @@ def test_chunked_facet_major_raman(chunked, raman, monkeypatch, pollack_table): 
         wrong = np.stack([reference_planes(*refs[56 + f], rf=rfs[f])["w0"] for f in range(8)])
         _far(got["w0"][56:], wrong, "chunked/raman")
     _far(got["dtau"][56:], np.stack([reference_planes(*r)["dtau"] for r in refs[:8]]), "chunked/facet-major")
+
+
+def _budget_of_facets(monkeypatch, nfacets, nlayer, tables):
+    """the table budget of one gas launch cut down to ``nfacets`` facets' worth of a recorded launch's tables"""
+    from picaso_amd import optics as px
+    counts = [len(tables[k]) for k in ("mol_tabs", "cont_tabs", "ray_tabs")]
+    monkeypatch.setattr(px, "GAS_TABLE_BUDGET", nfacets * px.gas_table_bytes(*counts, nlayer, tables["cont_wts"]))
+
+
+def test_chunked_facet_major_ck(monkeypatch):
+    """compute_opacity_facet_major_ck in three launches (5 + 5 + 2 of 12 facets; no affordable shape overflows the real
+    budget): the 13 planes are those of the single launch bit for bit and every facet's are its 1-D correlated-k
+    reference's; the last chunk's facets are far from the first facets' references."""
+    from picaso_amd import optics as px
+    ng, nt, nlayer = 4, 3, 23
+    T, ck = _ck_tables(257)
+    atm_f, ones = _facets(T, nlayer, ng, nt)
+    cld = _cloud_planes(nlayer, 257)
+    tables = []
+    calls = _count_gas_calls(monkeypatch, tables)
+    whole = _host(px.compute_opacity_facet_major_ck(atm_f, T.opa, ng, nt, raman=2, clouds_3d=cld))
+    assert calls == [12 * 23]
+    _budget_of_facets(monkeypatch, 5, nlayer, tables[0])
+    del calls[:]
+    got = _host(px.compute_opacity_facet_major_ck(atm_f, T.opa, ng, nt, raman=2, clouds_3d=cld))
+    assert calls == [5 * 23, 5 * 23, 2 * 23]
+    assert sorted(got) == sorted(NAMES)
+    for k in NAMES:
+        assert np.array_equal(got[k], whole[k]), k
+    want = [reference_planes(tg, tr, cld) for tg, tr in _facet_refs(T, ones, ck=ck)]
+    for f in range(ng * nt):
+        _check_planes({k: got[k][f] for k in NAMES}, want[f], "chunked/facet-major-ck")
+    _far(got["dtau"][10:], np.stack([w["dtau"] for w in want[:2]]), "chunked/facet-major-ck")
+
+
+def test_chunked_facets_cloud_tables(monkeypatch):
+    """compute_opacity_facets with cloud tables on their own grid, its gas stage in two launches (5 + 1 of 6 facets):
+    the planes of the single launch bit for bit."""
+    from picaso_amd import optics as px
+    ng, nt, nlayer = 3, 2, 23
+    T = Tables(3001, "linear")
+    atm_f, _ = _facets(T, nlayer, ng, nt)
+    xp, compact = _cloud_tables(nlayer)
+    cld3 = dict(compact, wavenumber=xp)
+    tables = []
+    calls = _count_gas_calls(monkeypatch, tables)
+    whole = _host(px.compute_opacity_facets(atm_f, T.opa, ng, nt, raman=2, clouds_3d=cld3))
+    assert calls == [6 * 23]
+    _budget_of_facets(monkeypatch, 5, nlayer, tables[0])
+    del calls[:]
+    got = _host(px.compute_opacity_facets(atm_f, T.opa, ng, nt, raman=2, clouds_3d=cld3))
+    assert calls == [5 * 23, 1 * 23]
+    assert sorted(got) == sorted(NAMES)
+    for k in NAMES:
+        assert np.array_equal(got[k], whole[k]), k
