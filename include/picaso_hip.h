@@ -212,7 +212,20 @@ int picaso_reflected_1d_can_derive(int nlevel, long plane_pitch, int numg, int n
  * byte of any plane of the set.  Unsealing what is not sealed is not an error.
  *
  * picaso_reflected_seal_stat: *seals = sets of the context's device that are sealed with all three flags right now,
- * *hits = launches on that device that used one, since the process started (either may be NULL). */
+ * *hits = launches on that device that used one, since the process started (either may be NULL).
+ *
+ * CLEAR LAYERS.  The same pass records, for a set of at most 128 layers, which layers carry no cloud in ANY column:
+ *     ftau_cld[i] == 0.0 and dtau_og[i] == dtau[i]     (the kernels' own two tests; a NaN fails them)
+ *     ftau_ray[i] has the bit pattern of 1.0, w0_og[i] that of w0[i]
+ * in all nwno columns.  The fused five-angle launch of a sealed set (not its one-wave-per-SIMD form, not the cooperative
+ * kernel) then reads dtau and w0 alone in such a layer and puts the other values in -- they ARE the stored ones, so the
+ * bits do not change; every other layer is read and tested as before.  A batch takes the masks when every member's seal
+ * has one.  The mask is no flag (*flags_out stays PICASO_SEAL_LEVELS & ~failed) and lives and dies with its seal.
+ * PICASO_AMD_REFL_NO_LAYER_MASK=1 in the environment switches its use off (the launch is then the sealed one above).
+ * picaso_reflected_seal_layers: clear_out[i] = 1 / 0 for the first min(cap, nlayer) layers of the sealed set that owns
+ * the byte at any_plane_ptr, *nlayer_out = its layer count -- 0 when there is no such set or it recorded no mask.
+ * picaso_reflected_seal_layers_stat: *mask_launches = launches on the context's device that used a mask (each is also
+ * one of the *hits above). */
 #define PICASO_SEAL_TAU 1
 #define PICASO_SEAL_TAU_OG 2
 #define PICASO_SEAL_GCOS2 4
@@ -223,6 +236,8 @@ int picaso_reflected_planes_seal_dev(picaso_ctx *ctx, int nlevel, int nwno, long
                                      const double *tau_og, const double *w0_og, const double *cosb_og, int *flags_out);
 int picaso_reflected_planes_unseal(picaso_ctx *ctx, const void *any_plane_ptr);
 int picaso_reflected_seal_stat(picaso_ctx *ctx, long *seals, long *hits);
+int picaso_reflected_seal_layers(picaso_ctx *ctx, const void *any_plane_ptr, int cap, int *clear_out, int *nlayer_out);
+int picaso_reflected_seal_layers_stat(picaso_ctx *ctx, long *mask_launches);
 /* `nspec` spectra of one shape and one option set in ONE launch (the reference runs the
  * spectra of a retrieval or the phases of a curve as separate processes -- driver.py:405-426,
  * justdoit.py:4741-4777 -- each calling get_reflected_1d, fluxes.py:1009-1413).  Every pointer argument of

@@ -592,8 +592,9 @@ struct ReflBatchHost {
 static bool reflected_seal_applies(picaso_ctx *ctx, int nlevel, int nwno, long plane_pitch, int numg, int numt,
                                    const double *const one[11], const double *ubar0, const double *ubar1, double cos_theta,
                                    int single_phase, int multi_phase, double frac_c, int toon_coefficients,
-                                   const ReflBatchHost *bt)
+                                   const ReflBatchHost *bt, std::vector<unsigned long long> &masks, bool &use_masks)
 {
+    use_masks = false;
     const int nang = numg * numt, nspec = bt ? bt->nspec : 1, ngeom = bt ? bt->ngeom : 1;
     if (nang != 5) return false;
     for (int s = 0; s < ngeom; ++s) {
@@ -616,11 +617,19 @@ static bool reflected_seal_applies(picaso_ctx *ctx, int nlevel, int nwno, long p
         if (angle_chunks(nang).size() != 1) return false;
         if ((long)nspec * ((nwno + 255L) / 256) * 4 <= 1024 && !getenv("PICASO_AMD_REFL_NO_BIG")) return false;   // BIG
     }
+    // The clear-layer masks of the seals (DRV = 4, "LAYERS"): the fused launch only -- the cooperative kernel has no such
+    // variant -- when every member's seal recorded one and at least one layer of one member is clear; else LEVELS as before
+    masks.assign(2 * (size_t)nspec, 0ull);
+    bool all_valid = true, any_clear = false;
     for (int s = 0; s < nspec; ++s) {
         const double *pl[11];
         for (int j = 0; j < 11; ++j) pl[j] = bt ? bt->plane[j][s] : one[j];
-        if (!seal_derivable(ctx->device, pl, nlevel, nwno, plane_pitch)) return false;
+        bool valid = false;
+        if (!seal_derivable(ctx->device, pl, nlevel, nwno, plane_pitch, &masks[2 * (size_t)s], &valid)) return false;
+        all_valid = all_valid && valid;
+        any_clear = any_clear || masks[2 * (size_t)s] || masks[2 * (size_t)s + 1];
     }
+    use_masks = !coop && all_valid && any_clear && !getenv("PICASO_AMD_REFL_NO_LAYER_MASK");
     return true;
 }
 
@@ -667,10 +676,12 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
     // a sealed set: its level planes were verified when they entered the device, the launch forms them itself
     ReflBatchHost bt_sealed;
     std::vector<const double *> absent;
+    std::vector<unsigned long long> lmasks;      // two words per spectrum, see ReflectedArgs::lmask
+    bool use_lmask = false;
     if (!derived && ncolper == 1 && get_toa_intensity && !get_lvl_flux) {
         const double *const pl[11] = {dtau, tau, w0, cosb, gcos2, ftau_cld, ftau_ray, dtau_og, tau_og, w0_og, cosb_og};
         if (reflected_seal_applies(ctx, nlevel, nwno, plane_pitch, numg, numt, pl, ubar0, ubar1, cos_theta, single_phase,
-                                   multi_phase, frac_c, toon_coefficients, bt)) {
+                                   multi_phase, frac_c, toon_coefficients, bt, lmasks, use_lmask)) {
             tau = tau_og = gcos2 = nullptr;
             if (bt) {
                 absent.assign((size_t)nspec, nullptr);
@@ -678,7 +689,7 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
                 bt_sealed.plane[1] = bt_sealed.plane[4] = bt_sealed.plane[8] = absent.data();
                 bt = &bt_sealed;
             }
-            seal_count_hit(ctx->device);
+            seal_count_hit(ctx->device, use_lmask);
         }
     }
     if (get_lvl_flux) {
@@ -703,6 +714,8 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
     a.single_phase = single_phase; a.multi_phase = multi_phase; a.toon_coefficients = toon_coefficients;
     a.frac_a = frac_a; a.frac_b = frac_b; a.frac_c = frac_c; a.constant_back = constant_back;
     a.constant_forward = constant_forward; a.b_top = b_top;
+    a.use_lmask = use_lmask ? 1 : 0;
+    if (use_lmask) { a.lmask[0] = lmasks[0]; a.lmask[1] = lmasks[1]; }
     const bool fuse = albedo && gweight && tweight;
     a.albedo = fuse ? albedo : nullptr;
     a.albedo_scale = ((numt == 1) ? 2.0 * 3.14159265358979323846 : 1.0) * 0.5;   // disco.py:140-141
@@ -725,6 +738,8 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
             it.albedo = (fuse && weights) ? bt->albedo[s] : nullptr;
             it.cos_theta = bt->cos_theta[bt->ngeom > 1 ? s : 0];
             it.u0_tab = it.u1_tab = nullptr;
+            it.lmask[0] = use_lmask ? lmasks[2 * (size_t)s] : 0ull;
+            it.lmask[1] = use_lmask ? lmasks[2 * (size_t)s + 1] : 0ull;
             ct1 = ct1 && it.cos_theta == 1.0;
             const double *u0 = ubar0 + (bt->ngeom > 1 ? (size_t)s * nang : 0), *u1 = ubar1 + (bt->ngeom > 1 ? (size_t)s * nang : 0);
             for (int k = 0; k < count; ++k) {

@@ -189,6 +189,10 @@ struct ReflectedArgs {
     int batch_zp;                           // every angle of every spectrum has ubar0 == ubar1 (the table is on the device)
     int batch_interleave;                   // all spectra read the SAME planes (geometries differ): the workgroups
                                             // of one column group go to one XCD, like angle groups (ny)
+    // DRV = 4 ("LAYERS") only: bit i set = layer i of the sealed set is cloud-free in EVERY column (planeseal.hip), the
+    // kernel then reads dtau and w0 of that layer alone.  0 everywhere else.  A batched launch: the entry's own mask.
+    unsigned long long lmask[2];
+    int use_lmask;                          // the launcher's request for that variant (every member's mask is valid)
 };
 struct ReflBatchItem {
     const double *dtau, *tau, *w0, *cosb, *gcos2, *ftau_cld, *ftau_ray, *dtau_og, *tau_og, *w0_og, *cosb_og;
@@ -197,6 +201,7 @@ struct ReflBatchItem {
     double cos_theta;
     const double *u0_tab, *u1_tab;          // 3-D: this spectrum's (nfac) tables of ubar0, ubar1
     ReflectedArgs::Angle ang[MAX_ANGLES];   // 1-D: this launch chunk's angles of this spectrum
+    unsigned long long lmask[2];            // this spectrum's clear-layer mask (ReflectedArgs::lmask)
 };
 int launch_reflected_toa(picaso_ctx *ctx, const ReflectedArgs &a, bool is3d);
 // cooperative kernel for small 1-D launches (toon_reflected_coop.hip): one workgroup per 64 columns, a wave for the

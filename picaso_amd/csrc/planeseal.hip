@@ -15,137 +15,80 @@
 // dies when the library sees its bytes change or go away: picaso_dev_free, the picaso_memcpy_h2d* / _d2d / picaso_memset
 // calls whose destination overlaps a plane, picaso_pool_trim, picaso_ctx_destroy.  Writes the library cannot see
 // (a kernel's output, another process) are the caller's to announce with picaso_reflected_planes_unseal.
+//
+// The same pass records WHICH LAYERS are cloud-free in every column (sets of up to 128 layers): ftau_cld == 0, dtau_og ==
+// dtau, and ftau_ray / w0_og carrying the bit patterns of 1.0 / w0.  A cloud deck in a few of the layers is the usual
+// atmosphere; in all the others six of the eight rows the LEVELS kernel reads hold constants and copies.  The fused five-
+// angle launch takes the mask (DRV = 4, "LAYERS", toon_reflected.hip) and reads dtau and w0 alone there: 240 plane rows
+// instead of 720 at 90 layers with a ten-layer cloud.  The mask lives and dies with its seal.  The bookkeeping itself is
+// host-only code in planeseal_registry.hpp.
 #include "common.hpp"
 #include "planeseal.hpp"
-
-#include <atomic>
-#include <cstdint>
-#include <map>
-#include <mutex>
+#include "planeseal_registry.hpp"
 
 namespace pz {
 
 namespace {
 
-struct Seal {
-    const double *plane[11];
-    int nlevel, nwno;
-    long pitch;
-    int flags;
-
-    // bytes of plane j the solver may read: rows of `pitch` elements, the last one `nwno` long
-    size_t extent(int j) const
-    {
-        const long rows = (j == 1 || j == 8) ? nlevel : nlevel - 1;      // tau and tau_og are level planes
-        return sizeof(double) * (size_t)((rows - 1) * pitch + nwno);
-    }
-    bool overlaps(const void *p, size_t bytes) const
-    {
-        const uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
-        for (int j = 0; j < 11; ++j) {
-            const uintptr_t q = (uintptr_t)plane[j];
-            if (lo < q + extent(j) && q < hi) return true;
-        }
-        return false;
-    }
-    bool same_set(const double *const p[11]) const
-    {
-        for (int j = 0; j < 11; ++j)
-            if (plane[j] != p[j]) return false;
-        return true;
-    }
-};
-
-struct DeviceSeals {
-    std::vector<Seal> seals;
-    long hits = 0;
-};
-
-struct Registry {
-    std::mutex mu;
-    std::map<int, DeviceSeals> dev;
-};
+using sealreg::Seal;
+static_assert(sealreg::LEVELS_FLAGS == PICASO_SEAL_LEVELS, "planeseal_registry.hpp restates PICASO_SEAL_LEVELS");
 
 // never destroyed: a buffer may be freed while the process shuts down, after the static destructors have run
-Registry &registry()
+sealreg::Registry &registry()
 {
-    static Registry *r = new Registry();
+    static sealreg::Registry *r = new sealreg::Registry();
     return *r;
-}
-std::atomic<long> g_records{0};      // seals of all devices: the copies and frees of a process without seals skip the mutex
-
-long drop_where(DeviceSeals &d, bool (*pred)(const Seal &, const void *, size_t), const void *p, size_t bytes)
-{
-    long n = 0;
-    for (size_t k = d.seals.size(); k-- > 0;)
-        if (pred(d.seals[k], p, bytes)) {
-            d.seals.erase(d.seals.begin() + (long)k);
-            ++n;
-        }
-    g_records -= n;
-    return n;
 }
 
 }  // namespace
 
-bool seal_derivable(int device, const double *const planes[11], int nlevel, int nwno, long pitch)
+bool seal_derivable(int device, const double *const planes[11], int nlevel, int nwno, long pitch,
+                    unsigned long long *layer_mask, bool *mask_valid)
 {
-    if (g_records.load(std::memory_order_relaxed) == 0) return false;
-    Registry &r = registry();
-    std::lock_guard<std::mutex> lock(r.mu);
-    auto it = r.dev.find(device);
-    if (it == r.dev.end()) return false;
-    for (const Seal &s : it->second.seals)
-        if (s.same_set(planes))
-            return s.nlevel == nlevel && s.nwno == nwno && s.pitch == pitch &&
-                   (s.flags & PICASO_SEAL_LEVELS) == PICASO_SEAL_LEVELS;
-    return false;
+    uint64_t m[2];
+    const bool ok = registry().derivable(device, planes, nlevel, nwno, pitch, m, mask_valid);
+    if (layer_mask) {
+        layer_mask[0] = m[0];
+        layer_mask[1] = m[1];
+    }
+    return ok;
 }
 
-void seal_count_hit(int device)
-{
-    Registry &r = registry();
-    std::lock_guard<std::mutex> lock(r.mu);
-    ++r.dev[device].hits;
-}
+void seal_count_hit(int device, bool with_layer_mask) { registry().count_hit(device, with_layer_mask); }
 
-void seal_invalidate(int device, const void *p, size_t bytes)
-{
-    if (!p || !bytes || g_records.load(std::memory_order_relaxed) == 0) return;
-    Registry &r = registry();
-    std::lock_guard<std::mutex> lock(r.mu);
-    auto it = r.dev.find(device);
-    if (it == r.dev.end()) return;
-    drop_where(it->second, [](const Seal &s, const void *q, size_t n) { return s.overlaps(q, n); }, p, bytes);
-}
+void seal_invalidate(int device, const void *p, size_t bytes) { registry().invalidate(device, p, bytes); }
 
-void seal_drop_device(int device)
-{
-    if (g_records.load(std::memory_order_relaxed) == 0) return;
-    Registry &r = registry();
-    std::lock_guard<std::mutex> lock(r.mu);
-    auto it = r.dev.find(device);
-    if (it == r.dev.end()) return;
-    drop_where(it->second, [](const Seal &, const void *, size_t) { return true; }, nullptr, 0);
-}
+void seal_drop_device(int device) { registry().drop_device(device); }
 
 // One lane per column, blockIdx.y = a run of SEAL_ROWS layers; every comparison needs only values of the planes
 // themselves (tau[i + 1] against tau[i] + dtau[i] with the STORED tau[i]), so the runs are independent.  The rows read are
 // the rows the solver reads: dtau, dtau_og, ftau_ray, gcos2 [0, nlayer), tau [0, nlayer], tau_og [0, nlayer) -- the
 // solver never looks at tau_og[nlayer].  A NaN fails its comparison.  Lanes that found something OR their bits into
 // one word (a vector atomic; none is issued for a set that passes).
+//
+// The clear-layer mask (notclear_out != nullptr: nlayer <= 128): a layer is NOT clear when some column has ftau_cld != 0
+// or dtau_og != dtau (the solver's own two tests; a NaN fails them), or carries another bit pattern than 1.0 in ftau_ray
+// or than w0's in w0_og -- those two values the LAYERS kernel puts in without loading them.  The lanes of a wave vote
+// per layer; a wave that found a layer not clear ORs its eight bits (a run of SEAL_ROWS layers lies inside one 32-bit
+// word) into the array with one vector atomic from its first lane.  A cloud-free set issues none.
 constexpr int SEAL_BLOCK = 256, SEAL_ROWS = 8;
+static_assert(32 % SEAL_ROWS == 0, "the layers of one block lie inside one word of the mask");
+constexpr int SEAL_WORDS = 1 + sealreg::MASK_LAYERS / 32;      // the device buffer: flags found bad, then the mask words
 
 __global__ __launch_bounds__(SEAL_BLOCK) void k_planes_seal(int nlayer, int nwno, long pitch, const double *dtau,
                                                              const double *tau, const double *gcos2,
                                                              const double *ftau_ray, const double *dtau_og,
-                                                             const double *tau_og, int *bad_out)
+                                                             const double *tau_og, const double *w0,
+                                                             const double *ftau_cld, const double *w0_og, int *bad_out,
+                                                             unsigned *notclear_out)
 {
 #pragma clang fp contract(off)      // the solver's own unfused operations
     const long col = (long)blockIdx.x * SEAL_BLOCK + threadIdx.x;
     if (col >= nwno) return;
     const int i0 = (int)blockIdx.y * SEAL_ROWS, i1 = (i0 + SEAL_ROWS < nlayer) ? i0 + SEAL_ROWS : nlayer;
     int bad = 0;
+    unsigned notclear = 0;                           // wave-uniform: bit (i & 31) = some lane of this wave saw cloud in layer i
+    unsigned lane_cloudy = 0;                        // this lane's own findings, bit (i - i0)
     double t = tau[(long)i0 * pitch + col], to = tau_og[(long)i0 * pitch + col];
     if (i0 == 0) {                                   // the sums start from +0.0 (the bit pattern: -0.0 is another start)
         if (__double_as_longlong(t) != 0) bad |= PICASO_SEAL_TAU;
@@ -155,16 +98,28 @@ __global__ __launch_bounds__(SEAL_BLOCK) void k_planes_seal(int nlayer, int nwno
     for (int i = i0; i < i1; ++i) {
         const long o = (long)i * pitch + col;
         const double tn = tau[o + pitch];
-        if (!(tn == t + dtau[o])) bad |= PICASO_SEAL_TAU;
+        const double dt = dtau[o], dto = dtau_og[o], fr = ftau_ray[o];
+        if (!(tn == t + dt)) bad |= PICASO_SEAL_TAU;
         t = tn;
         if (i + 1 < nlayer) {
             const double ton = tau_og[o + pitch];
-            if (!(ton == to + dtau_og[o])) bad |= PICASO_SEAL_TAU_OG;
+            if (!(ton == to + dto)) bad |= PICASO_SEAL_TAU_OG;
             to = ton;
         }
-        if (!(gcos2[o] == 0.5 * ftau_ray[o])) bad |= PICASO_SEAL_GCOS2;
+        if (!(gcos2[o] == 0.5 * fr)) bad |= PICASO_SEAL_GCOS2;
+        if (notclear_out) {
+            const bool cloudy = !(ftau_cld[o] == 0.0) || !(dto == dt) ||
+                                __double_as_longlong(fr) != __double_as_longlong(1.0) ||
+                                __double_as_longlong(w0_og[o]) != __double_as_longlong(w0[o]);
+            if (cloudy) lane_cloudy |= 1u << (i - i0);
+        }
     }
+    // (the votes after the loop: a vote inside it would keep the loop from being unrolled)
+#pragma unroll
+    for (int b = 0; b < SEAL_ROWS; ++b)
+        if (__any((lane_cloudy >> b) & 1u)) notclear |= 1u << ((i0 & 31) + b);
     if (bad) atomicOr(bad_out, bad);
+    if (notclear && (threadIdx.x & 63) == 0) atomicOr(notclear_out + (i0 >> 5), notclear);   // lane 0 is active if any is
 }
 
 }  // namespace pz
@@ -185,16 +140,18 @@ int picaso_reflected_planes_seal_dev(picaso_ctx *ctx, int nlevel, int nwno, long
     PZ_NEED(ctx, "reflected_planes_seal", dtau, tau, w0, cosb, gcos2, ftau_cld, ftau_ray, dtau_og, tau_og, w0_og, cosb_og);
     PZ_HIP(ctx, hipSetDevice(ctx->device));
     void *word = nullptr;
-    PZ_TRY(picaso_dev_malloc(ctx, sizeof(int), &word));
-    int bad = 0;
+    PZ_TRY(picaso_dev_malloc(ctx, sizeof(int) * SEAL_WORDS, &word));
+    int found[SEAL_WORDS] = {0};
+    const int nlayer = nlevel - 1;
+    const bool with_mask = nlayer <= sealreg::MASK_LAYERS;
     auto run = [&]() -> int {
-        const int nlayer = nlevel - 1;
-        PZ_HIP(ctx, hipMemsetAsync(word, 0, sizeof(int), ctx->stream));
+        PZ_HIP(ctx, hipMemsetAsync(word, 0, sizeof(int) * SEAL_WORDS, ctx->stream));
         const dim3 grid((unsigned)((nwno + SEAL_BLOCK - 1) / SEAL_BLOCK), (unsigned)((nlayer + SEAL_ROWS - 1) / SEAL_ROWS));
         hipLaunchKernelGGL(k_planes_seal, grid, dim3(SEAL_BLOCK), 0, ctx->stream, nlayer, nwno, plane_pitch, dtau, tau,
-                           gcos2, ftau_ray, dtau_og, tau_og, (int *)word);
+                           gcos2, ftau_ray, dtau_og, tau_og, w0, ftau_cld, w0_og, (int *)word,
+                           with_mask ? (unsigned *)word + 1 : nullptr);
         PZ_HIP(ctx, hipGetLastError());
-        PZ_HIP(ctx, hipMemcpyAsync(&bad, word, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        PZ_HIP(ctx, hipMemcpyAsync(found, word, sizeof(int) * SEAL_WORDS, hipMemcpyDeviceToHost, ctx->stream));
         PZ_HIP(ctx, hipStreamSynchronize(ctx->stream));
         return 0;
     };
@@ -207,16 +164,9 @@ int picaso_reflected_planes_seal_dev(picaso_ctx *ctx, int nlevel, int nwno, long
     s.nlevel = nlevel;
     s.nwno = nwno;
     s.pitch = plane_pitch;
-    s.flags = PICASO_SEAL_LEVELS & ~bad;
-    {
-        Registry &r = registry();
-        std::lock_guard<std::mutex> lock(r.mu);
-        DeviceSeals &d = r.dev[ctx->device];
-        // a second seal of the same eleven addresses replaces the first
-        drop_where(d, [](const Seal &x, const void *q, size_t) { return x.same_set((const double *const *)q); }, pl, 0);
-        d.seals.push_back(s);
-        ++g_records;
-    }
+    s.flags = PICASO_SEAL_LEVELS & ~found[0];
+    sealreg::mask_from_device_words(s, with_mask ? (const unsigned *)found + 1 : nullptr);
+    registry().record(ctx->device, s);
     if (flags_out) *flags_out = s.flags;
     return 0;
 }
@@ -231,14 +181,22 @@ int picaso_reflected_planes_unseal(picaso_ctx *ctx, const void *any_plane_ptr)
 int picaso_reflected_seal_stat(picaso_ctx *ctx, long *seals, long *hits)
 {
     if (!ctx) return fail(nullptr, "null context");
-    Registry &r = registry();
-    std::lock_guard<std::mutex> lock(r.mu);
-    auto it = r.dev.find(ctx->device);
-    long n = 0;
-    if (it != r.dev.end())
-        for (const Seal &s : it->second.seals) n += (s.flags & PICASO_SEAL_LEVELS) == PICASO_SEAL_LEVELS;
-    if (seals) *seals = n;
-    if (hits) *hits = it != r.dev.end() ? it->second.hits : 0;
+    registry().stat(ctx->device, seals, hits, nullptr);
+    return 0;
+}
+
+int picaso_reflected_seal_layers(picaso_ctx *ctx, const void *any_plane_ptr, int cap, int *clear_out, int *nlayer_out)
+{
+    if (!ctx) return fail(nullptr, "null context");
+    if (!nlayer_out || cap < 0 || (cap > 0 && !clear_out)) return fail(ctx, "reflected_seal_layers: bad arguments");
+    *nlayer_out = registry().layers(ctx->device, any_plane_ptr, cap, clear_out);
+    return 0;
+}
+
+int picaso_reflected_seal_layers_stat(picaso_ctx *ctx, long *mask_launches)
+{
+    if (!ctx) return fail(nullptr, "null context");
+    registry().stat(ctx->device, nullptr, nullptr, mask_launches);
     return 0;
 }
 

@@ -80,6 +80,9 @@ enum { S_T = 0, S_XU, S_EO, S_KAPPA, S_ZETA, S_D1, S_D2 };   // late-use variabl
 #ifndef PZ_REFL_LEVELS_VARIANT
 #define PZ_REFL_LEVELS_VARIANT 1
 #endif
+#ifndef PZ_REFL_LAYERS_VARIANT
+#define PZ_REFL_LAYERS_VARIANT 1
+#endif
 #ifndef PZ_REFL_CLEAR_VARIANT
 #define PZ_REFL_CLEAR_VARIANT 1
 #endif
@@ -464,7 +467,16 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     // present -- known at compile time, so the two tests of "the level depths are the running sums" (they are: they are
     // formed here), the exec-mask tests and the branches behind them disappear from every layer (timing build of the
     // eleven-plane kernel with those two tests compiled out: 0.223 -> 0.207 ms)
-    constexpr bool CLEAR = (DRV == 2), LEVELS = (DRV == 3);
+    // DRV = 4 ("LAYERS"): DRV = 3 plus what a seal knows about the layers (planeseal.hip): bit i of a.lmask says that
+    // layer i carries no cloud in ANY column of the set -- ftau_cld = 0, ftau_ray = 1, dtau_og = dtau, w0_og = w0, bit for
+    // bit.  Such a layer is read and prepared as DRV = 2 does it (dtau and w0 alone, the constants put in, no vote, straight
+    // to the cloud-free copy of the body); every other layer is DRV = 3 unchanged.  The values put in ARE the stored ones
+    // and the votes would have passed, so the same copy of the body runs on the same numbers.
+    constexpr bool CLEAR = (DRV == 2), LAYERS = (DRV == 4), LEVELS = (DRV == 3) || LAYERS;
+    auto layer_clear = [&](int i) -> bool {          // wave-uniform: the mask is a kernel argument / a table entry
+        if constexpr (LAYERS) return (((i & 64) ? a.lmask[1] : a.lmask[0]) >> (i & 63)) & 1ull;
+        return false;
+    };
     const bool derive_tau = CLEAR || LEVELS || (DRV && a.tau == nullptr);
     const bool derive_tauo = CLEAR || LEVELS || (DRV && a.tau_og == nullptr);
     const bool derive_g2 = CLEAR || LEVELS || (DRV && a.gcos2 == nullptr);
@@ -494,12 +506,22 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     auto ld = [&](const double *base, unsigned off) {
         return *(const double *)((const char *)base + off);
     };
-    auto load = [&](LayerIn &L, int i) {
+    auto load = [&](LayerIn &L, int i, bool in_loop = false) {
         if constexpr (FAST && PZ_REFL_SADDR && DRV) {      // 1-D with planes left out: only what exists is loaded
             const unsigned o = voff0 + (unsigned)i * pitch8;
+            if constexpr (LAYERS) {
+                // The number of loads now differs from layer to layer, and a wait for the OTHER register set counted in
+                // instructions issued since would have to assume the smaller number: it would wait for part of this
+                // prefetch.  So the other set (issued a whole layer ago) is waited for here, by name, before this one
+                // is issued: s_waitcnt vmcnt(0), the other counters left alone.
+                if (in_loop) __builtin_amdgcn_s_waitcnt(0x0F70);
+            }
             L.dt = ld(a.dtau, o);
             L.w0 = ld(a.w0, o);
             if constexpr (CLEAR) return;
+            if constexpr (LAYERS) {
+                if (layer_clear(i)) return;
+            }
             if constexpr (LEVELS) {
                 L.g = ld(a.cosb, o);
                 L.fc = ld(a.ftau_cld, o);
@@ -568,8 +590,8 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         L.w0o = p_w0o[o];
         L.cbo = p_cbo[o];
     };
-    auto prep = [&](LayerIn &L) {
-        if constexpr (CLEAR) {
+    auto prep = [&](LayerIn &L, bool lclear) {
+        if (CLEAR || (LAYERS && lclear)) {
             L.g = 0.0; L.fc = 0.0; L.fr = 1.0; L.gcos2 = 0.5; L.cbo = 0.0;
             L.dto = L.dt; L.w0o = L.w0;
             L.tau_n = tau_i + L.dt;
@@ -609,9 +631,10 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         tau_i = L.tau_n;
         tauo_pred = L.tauo + L.dto;
     };
-#define PZ_LAYER(FIRST_, LAST_, L_)                                                                      \
+#define PZ_LAYER(FIRST_, LAST_, L_, I_)                                                                  \
     do {                                                                                                 \
-        prep(L_);                                                                                        \
+        const bool lclear_ = layer_clear(I_);                                                            \
+        prep(L_, lclear_);                                                                               \
         if (PZ_REFL_NOCLD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf)                  \
             reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, true, true>(a, L_, S, g, K, F, clip, tc, b_top); \
         else if (PZ_REFL_CLOUD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.af_cloud)                      \
@@ -636,34 +659,34 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     LayerIn A, B;
     load(A, 0);
     if (n == 1) {
-        PZ_LAYER(true, true, A);
+        PZ_LAYER(true, true, A, 0);
     } else if constexpr (TWO_SETS) {
         load(B, 1);
-        PZ_LAYER(true, false, A);
+        PZ_LAYER(true, false, A, 0);
         int i = 1;                               // B holds layer i
         for (; i + 2 <= n - 1; i += 2) {         // layers i and i+1 are interior, layer i+2 exists
-            load(A, i + 1);
-            PZ_LAYER(false, false, B);
-            load(B, i + 2);
-            PZ_LAYER(false, false, A);
+            load(A, i + 1, true);
+            PZ_LAYER(false, false, B, i);
+            load(B, i + 2, true);
+            PZ_LAYER(false, false, A, i + 1);
         }
         if (i == n - 1) {
-            PZ_LAYER(false, true, B);
+            PZ_LAYER(false, true, B, i);
         } else {                                 // i == n - 2
-            load(A, i + 1);
-            PZ_LAYER(false, false, B);
-            PZ_LAYER(false, true, A);
+            load(A, i + 1, true);
+            PZ_LAYER(false, false, B, i);
+            PZ_LAYER(false, true, A, i + 1);
         }
     } else {
         load(B, 1);                              // B: prefetch set, A: the layer being computed
-        PZ_LAYER(true, false, A);
+        PZ_LAYER(true, false, A, 0);
         for (int i = 1; i < n - 1; ++i) {
             A = B;
             load(B, i + 1);
-            PZ_LAYER(false, false, A);
+            PZ_LAYER(false, false, A, i);
         }
         A = B;
-        PZ_LAYER(false, true, A);
+        PZ_LAYER(false, true, A, n - 1);
     }
 #undef PZ_LAYER
 
@@ -762,6 +785,7 @@ __global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : NA <= 2 ? PZ_REFL_MINWAVE
     b.surf_reflect = it.surf_reflect; b.F0PI = it.F0PI; b.xint = it.xint; b.albedo = it.albedo;
     b.cos_theta = it.cos_theta;
     b.u0_tab = it.u0_tab; b.u1_tab = it.u1_tab;
+    if constexpr (DRV == 4) { b.lmask[0] = it.lmask[0]; b.lmask[1] = it.lmask[1]; }
     reflected_toa_body<NA, IS3D, ZP, FAST, BIG, DRV>(b, bx, by, it.ang);
 }
 
@@ -810,13 +834,17 @@ static int launch1d(picaso_ctx *ctx, const ReflectedArgs &a_in)
         // only dtau and w0: the compile-time form (five angles, symmetric geometry: the shape of a spectrum() call)
         const bool only2 = !a.tau && !a.tau_og && !a.gcos2 && !a.ftau_cld && !a.dtau_og && PZ_REFL_CLEAR_VARIANT;
         const bool levels3 = !a.tau && !a.tau_og && !a.gcos2 && a.ftau_cld && a.dtau_og && PZ_REFL_LEVELS_VARIANT;
+        // the seal's clear-layer mask (api.hip asks for it): the fused five-angle shape only, never the BIG form
+        const bool layers4 = levels3 && a.use_lmask && PZ_REFL_LAYERS_VARIANT;
         if (a.batch) {
             if (zp && big) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, true, 1>)); }
+            else if (zp && layers4 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 4>)); }
             else if (zp && only2 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 2>)); }
             else if (zp && levels3 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 3>)); }
             else if (zp) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 1>));
             else PZ_GO((k_reflected_toa_batch<NA, false, false, true, false, 1>));
         } else if (zp && big) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, true, 1>)); }
+        else if (zp && layers4 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, false, 4>)); }
         else if (zp && only2 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, false, 2>)); }
         else if (zp && levels3 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, false, 3>)); }
         else if (zp) PZ_GO((k_reflected_toa<NA, false, true, true, false, 1>));

@@ -57,6 +57,24 @@ def reflected_seal_stat(ctx):
     return n.value, h.value
 
 
+def reflected_seal_layers(ctx, plane, cap=128):
+    """The clear-layer mask of the sealed set that ``plane`` (a DeviceArray or an address inside one) belongs to: a bool
+    array with one entry per layer, True where no column of the layer carries cloud -- or ``None`` when there is no such
+    set or it recorded no mask (``picaso_reflected_seal_layers``)."""
+    out, n = (ctypes.c_int * cap)(), ctypes.c_int(0)
+    check(load().picaso_reflected_seal_layers(ctx, addr(plane), cap, out, ctypes.byref(n)), ctx)
+    if n.value == 0:
+        return None
+    return np.array(out[:min(cap, n.value)], dtype=bool)
+
+
+def reflected_seal_layers_stat(ctx):
+    """Launches on the context's device that used a clear-layer mask (each is also one of ``reflected_seal_stat``'s hits)."""
+    m = ctypes.c_long(0)
+    check(load().picaso_reflected_seal_layers_stat(ctx, ctypes.byref(m)), ctx)
+    return m.value
+
+
 def reflected_can_derive(nlevel, nwno, numg, numt, ubar0, ubar1, cos_theta, single_phase, multi_phase, frac_c,
                          toon_coefficients=0, get_lvl_flux=False):
     """True when ``reflected_1d`` / ``reflected_1d_batch`` with these arguments may be handed ``None`` for the planes the

@@ -5,9 +5,10 @@ launch saves: after how many solves has a seal paid for itself?
     python tools/seal_time.py [--nwno 100000] [--nlayer 90] [--reps 5]
 
 Prints one JSON line: upload_ms (host -> HBM of the eleven planes, once), seal_ms (picaso_reflected_planes_seal_dev:
-the kernel, the wait for its flags, the registry; wall clock of the call), seal_kernel_ms (HIP events around the call),
-solve_sealed_ms / solve_all_planes_ms (steady state, the same process, PICASO_AMD_REFL_ALL_PLANES toggled) and
-break_even_solves = seal_ms / (solve_all_planes_ms - solve_sealed_ms)."""
+the kernel -- nine planes read: the level checks and the clear-layer mask --, the wait for its flags, the registry; wall
+clock of the call), seal_kernel_ms (HIP events around the call), solve_sealed_ms / solve_no_layer_mask_ms /
+solve_all_planes_ms (steady state, the same process, PICASO_AMD_REFL_NO_LAYER_MASK / PICASO_AMD_REFL_ALL_PLANES toggled),
+clear_layers (of nlayer, from the seal's mask) and break_even_solves = seal_ms / (solve_all_planes_ms - solve_sealed_ms)."""
 import argparse
 import json
 import os
@@ -56,11 +57,11 @@ def main():
         ev.append(device.timer_stop(ctx))
     xint, alb = device.DeviceArray((ng, 1, nwno), ctx), device.DeviceArray((nwno,), ctx)
 
-    def steady(all_planes):
-        if all_planes:
-            os.environ["PICASO_AMD_REFL_ALL_PLANES"] = "1"
-        else:
-            os.environ.pop("PICASO_AMD_REFL_ALL_PLANES", None)
+    def steady(knob):
+        for k in ("PICASO_AMD_REFL_ALL_PLANES", "PICASO_AMD_REFL_NO_LAYER_MASK"):
+            os.environ.pop(k, None)
+        if knob:
+            os.environ[knob] = "1"
 
         def step():
             resident.reflected_1d(ctx, nlayer + 1, nwno, ng, 1, d, d["surf_reflect"], ubar0, ubar1, 1.0, d["F0PI"], 3, 0,
@@ -75,14 +76,19 @@ def main():
             step()
         return device.timer_stop(ctx) / args.steps
 
-    h0 = resident.reflected_seal_stat(ctx)[1]
-    pairs = [(steady(False), steady(True)) for _ in range(args.reps)]
-    hits = resident.reflected_seal_stat(ctx)[1] - h0
+    h0, m0 = resident.reflected_seal_stat(ctx)[1], resident.reflected_seal_layers_stat(ctx)
+    pairs = [(steady(None), steady("PICASO_AMD_REFL_ALL_PLANES"), steady("PICASO_AMD_REFL_NO_LAYER_MASK"))
+             for _ in range(args.reps)]
+    hits, masked = resident.reflected_seal_stat(ctx)[1] - h0, resident.reflected_seal_layers_stat(ctx) - m0
     sealed, allp = min(p[0] for p in pairs), min(p[1] for p in pairs)
+    mask = resident.reflected_seal_layers(ctx, d["dtau"])
     print(json.dumps({"nwno": nwno, "nlayer": nlayer, "flags": flags, "upload_ms": [round(x, 2) for x in upload],
                       "seal_ms": [round(x, 4) for x in wall], "seal_kernel_ms": [round(x, 4) for x in ev],
-                      "solve_sealed_ms": [round(p[0], 5) for p in pairs], "solve_all_planes_ms": [round(p[1], 5) for p in pairs],
-                      "sealed_launches_counted": hits,
+                      "solve_sealed_ms": [round(p[0], 5) for p in pairs],
+                      "solve_no_layer_mask_ms": [round(p[2], 5) for p in pairs],
+                      "solve_all_planes_ms": [round(p[1], 5) for p in pairs],
+                      "clear_layers": None if mask is None else int(mask.sum()),
+                      "sealed_launches_counted": hits, "layer_mask_launches_counted": masked,
                       "break_even_solves": round(min(wall) / (allp - sealed), 1) if allp > sealed else None}), flush=True)
 
 
