@@ -45,8 +45,8 @@ def _param_type(decl, func):
     return _BY_VALUE[ctype]
 
 
-def declared_prototypes():
-    """``{name: (restype, [argtypes])}`` for every function include/picaso_hip.h declares."""
+def _declarations():
+    """``[(return type, name, [parameter declarations])]`` for every function include/picaso_hip.h declares."""
     with open(HEADER) as fh:
         text = fh.read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                        # comments
@@ -54,19 +54,31 @@ def declared_prototypes():
     text = re.sub(r"extern\s+\"C\"\s*\{", "", text)
     text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)      # struct bodies
     text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", "", text)             # opaque handles
-    protos = {}
+    decls = []
     for stmt in text.split(";"):
         stmt = " ".join(stmt.split())
         m = re.fullmatch(r"(.+?)\b(picaso_\w+) ?\((.*)\)", stmt)
         if not m:
             continue
         ret, name, params = m.group(1).replace(" *", "*").replace("*", " *").strip(), m.group(2), m.group(3).strip()
+        decls.append((ret, name, [] if params in ("", "void") else [p.strip() for p in params.split(",")]))
+    return decls
+
+
+def declared_prototypes():
+    """``{name: (restype, [argtypes])}`` for every function include/picaso_hip.h declares."""
+    protos = {}
+    for ret, name, params in _declarations():
         if ret not in _RETURNS:
             raise PicasoHipError("picaso_amd: %s declares %s with a return type %r this binding does not know"
                                  % (os.path.basename(HEADER), name, ret))
-        args = [] if params in ("", "void") else [_param_type(p.strip(), name) for p in params.split(",")]
-        protos[name] = (_RETURNS[ret], args)
+        protos[name] = (_RETURNS[ret], [_param_type(p, name) for p in params])
     return protos
+
+
+def declared_parameters():
+    """``{name: [parameter names]}`` for every function include/picaso_hip.h declares (it names every parameter)."""
+    return {name: [re.split(r"[\s*]+", p)[-1] for p in params] for _, name, params in _declarations()}
 
 
 def declared_symbols():

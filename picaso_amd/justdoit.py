@@ -23,7 +23,7 @@ import warnings
 
 import numpy as np
 
-from . import _lib, disco, optics, resident
+from . import _lib, disco, optics
 from . import convolve as _convolve
 from . import regrid as _regrid
 from . import options as _options
@@ -31,13 +31,14 @@ from .device import DeviceArray
 from .options import Options                                                        # noqa: F401  (jdi.Options)
 from .planes import cloud_free_top as _cloud_free_top                               # noqa: F401  (jdi._cloud_free_top)
 from .convolve import ConvolvePlan, conv_non_uniform_R, convolve_plan               # noqa: F401  (jdi.convolve_plan)
+from .solvebatch import SolveBatch
 from .regrid import RegridPlan, regrid_plan                                         # noqa: F401  (jdi.regrid_plan)
 from .contribution import thermal_contribution, transmission_contribution           # noqa: F401  (jdi.thermal_contribution)
 from .attenuation import cloud_optics_1d, heatmap_taus, photon_attenuation, taumap   # noqa: F401  (jdi.photon_attenuation)
 from .opacity_factory import compute_ck, compute_ck_molecular                        # noqa: F401  (jdi.compute_ck)
 from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
                        _fetch, _interp_axis, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
-                       _reflected, _resident_vector, _setup_atmosphere, _trapz_resident)
+                       _resident_vector, _setup_atmosphere, _trapz_resident)
 
 # option tables (reference justdoit.py:5512-5534, 5647-5658)
 def single_phase_options(printout=True):
@@ -953,14 +954,14 @@ class inputs:
         # ordered on the stream); at most `in_flight` phases keep their small result buffers pending.
         opt = _options.current(options)
         in_flight = opt.phases_in_flight
-        # One solver launch per leg for a CHUNK of phases (picaso_get_reflected_3d_batch_dev / _thermal_3d_batch_dev;
+        # One solver launch per leg for a CHUNK of phases (resident.reflected_3d_batch / thermal_3d_batch;
         # "all phases as one batched launch instead of joblib processes"): the phases' planes
         # stay resident until the chunk's launch, so the chunk is sized to ~48 GB of planes (PICASO_AMD_PHASE_CHUNK
         # overrides; 1 = one launch per phase, the round-3 form).  One batch per replica with devices=N.
         nfac_pc = all_geom[phases[0]]["num_gangle"] * all_geom[phases[0]]["num_tangle"]
         per_phase = 11 * 8.0 * max(self.nlevel - 1, 1) * opacityclass.nwno * nfac_pc
         chunk = opt.phase_chunk or max(1, min(in_flight, int(48e9 // max(per_phase, 1.0))))
-        batches = [_SolveBatch() if chunk > 1 else None for _ in replicas]
+        batches = [SolveBatch() if chunk > 1 else None for _ in replicas]
         results, pending = {}, []
         try:
             for i, ph in enumerate(phases):
@@ -1741,88 +1742,6 @@ def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", 
 # several spectra in one launch: the retrieval / grid callers of the reference run
 # spectrum() once per sample in separate processes (driver.py:405-426, justdoit.py:4741-4777)
 # ------------------------------------------------------------------------------------------------
-class _SolveBatch:
-    """The Toon solver launches of several ``picaso(defer=True, _batch=...)`` calls, issued by ``flush()`` as ONE
-    batched launch per group of spectra that share shape and options (``picaso_get_reflected_1d_batch_dev`` /
-    ``picaso_get_thermal_1d_batch_dev``): every spectrum is bit-identical to its own launch, the GPU sees one grid
-    that fills it instead of B that each leave its SIMDs half empty (DESIGN.md sections 5 and 6)."""
-
-    def __init__(self):
-        self.refl, self.therm, self.refl3, self.therm3 = {}, {}, {}, {}
-
-    def add_reflected(self, key, item):
-        self.refl.setdefault(key, []).append(item)
-
-    def add_thermal(self, key, item):
-        self.therm.setdefault(key, []).append(item)
-
-    def add_reflected_3d(self, key, item):
-        self.refl3.setdefault(key, []).append(item)
-
-    def add_thermal_3d(self, key, item):
-        self.therm3.setdefault(key, []).append(item)
-
-    def pending(self):
-        return sum(len(v) for d in (self.refl, self.therm, self.refl3, self.therm3) for v in d.values())
-
-    def flush(self):
-        for key, items in self.refl3.items():
-            nlevel, nwno, ng, nt, tt, present, gw, tw = key
-            fn = resident.reflected_3d_fm_batch if "facet-major" in present else resident.reflected_3d_batch
-            fn(items[0]["ctx"], nlevel, nwno, ng, nt, [it["planes"] for it in items],
-                                        [it["rs"] for it in items],
-                                        np.stack([np.asarray(it["ubar0"], dtype=float).reshape(ng, nt) for it in items]),
-                                        np.stack([np.asarray(it["ubar1"], dtype=float).reshape(ng, nt) for it in items]),
-                                        np.array([it["cos_theta"] for it in items], dtype=float),
-                                        [it["F0PI"] for it in items], *tt, [it["xint"] for it in items], gweight=gw,
-                                        tweight=tw, albedo=[it["albedo"] for it in items])
-        for key, items in self.therm3.items():
-            nlevel, nwno, ng, nt, hard, _, (has_g, fm), gw, tw = key
-            fn = resident.thermal_3d_fm_batch if fm else resident.thermal_3d_batch
-            fn(items[0]["ctx"], nlevel, items[0]["wno"], nwno, ng, nt,
-                                      np.stack([it["tlevel"] for it in items]), [it["dtau"] for it in items],
-                                      [it["w0"] for it in items], [it["cosb"] for it in items] if has_g else None,
-                                      np.stack([it["plevel"] for it in items]),
-                                      np.stack([np.asarray(it["ubar1"], dtype=float).reshape(ng, nt) for it in items]),
-                                      [it["rs"] for it in items], hard, [it["flux"] for it in items], gweight=gw,
-                                      tweight=tw, flux_disk=[it["disk"] for it in items])
-        self.refl3, self.therm3 = {}, {}
-        for key, items in self.refl.items():
-            nlevel, nwno, ng, nt, tt, tcoef, b_top, gw, tw, _ = key
-            ctx = items[0]["ctx"]
-            if len(items) == 1 or ng * nt > 8:       # the batched launch carries at most 8 disk angles: a 6 x 6 disk goes alone
-                for it in items:
-                    _reflected(ctx, nlevel, nwno, ng, nt, it["planes"], it["rs"], it["ubar0"], it["ubar1"],
-                               it["cos_theta"], it["F0PI"], *tt, tcoef, b_top, it["xint"], None, gw, tw, it["albedo"])
-                continue
-            same = all(np.array_equal(it["ubar0"], items[0]["ubar0"]) and np.array_equal(it["ubar1"], items[0]["ubar1"])
-                       and it["cos_theta"] == items[0]["cos_theta"] for it in items)
-            u0 = items[0]["ubar0"] if same else np.stack([np.asarray(it["ubar0"], dtype=float).reshape(ng, nt) for it in items])
-            u1 = items[0]["ubar1"] if same else np.stack([np.asarray(it["ubar1"], dtype=float).reshape(ng, nt) for it in items])
-            ct = items[0]["cos_theta"] if same else np.array([it["cos_theta"] for it in items], dtype=float)
-            resident.reflected_1d_batch(ctx, nlevel, nwno, ng, nt, [it["planes"] for it in items],
-                                        [it["rs"] for it in items], u0, u1, ct, [it["F0PI"] for it in items], *tt,
-                                        [it["xint"] for it in items], toon_coefficients=tcoef, b_top=b_top,
-                                        gweight=gw, tweight=tw, albedo=[it["albedo"] for it in items])
-        for key, items in self.therm.items():
-            nlevel, nwno, ng, nt, hard, _, gw, tw = key
-            ctx = items[0]["ctx"]
-            if len(items) == 1 or ng * nt > 8:
-                for it in items:
-                    resident.thermal_1d(ctx, nlevel, it["wno"], nwno, ng, nt, it["tlevel"], it["dtau"], it["w0"], it["cosb"],
-                                        it["plevel"], it["ubar1"], it["rs"], hard, it["flux"], gweight=gw, tweight=tw,
-                                        flux_disk=it["disk"])
-                continue
-            same = all(np.array_equal(it["ubar1"], items[0]["ubar1"]) for it in items)
-            u1 = items[0]["ubar1"] if same else np.stack([np.asarray(it["ubar1"], dtype=float).reshape(ng, nt) for it in items])
-            resident.thermal_1d_batch(ctx, nlevel, items[0]["wno"], nwno, ng, nt, np.stack([it["tlevel"] for it in items]),
-                                      [it["dtau"] for it in items], [it["w0"] for it in items],
-                                      [it["cosb"] for it in items], np.stack([it["plevel"] for it in items]), u1,
-                                      [it["rs"] for it in items], hard, [it["flux"] for it in items], gweight=gw,
-                                      tweight=tw, flux_disk=[it["disk"] for it in items])
-        self.refl, self.therm = {}, {}
-
-
 @_lib.serialized
 def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=False, as_dict=True, batch_size=4,
                    options=None, regrid=None, convolve=None):
@@ -1849,7 +1768,7 @@ def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=Fal
                 raise Exception("Need to set atmosphere profile with the atmosphere() function")
             if case.inputs["planet"]["gravity"] is None:
                 raise Exception("Need to set gravity with the gravity() function")
-        batch = _SolveBatch()
+        batch = SolveBatch()
         fins = []
         for case in chunk:
             fins.append(picaso(case, opacityclass, dimension="1d", calculation=calculation, full_output=full_output,

@@ -12,6 +12,79 @@ from ._lib import addr, check, f64, load, ptr, ptr_array
 from .device import DeviceArray
 from .planes import REFLECTED_PLANES, SH_PLANES
 
+
+# ------------------------------------------------------------------------------------------------
+# the pieces every launch wrapper below is made of.  A pointer made by ``ptr`` keeps its host array alive.
+# ------------------------------------------------------------------------------------------------
+def _opt(x):
+    return ptr(x) if x is not None else None
+
+
+def _disk(numg, numt, *ubars):
+    """Pointers to the ``(numg, numt)`` disk geometry arrays."""
+    return [ptr(f64(u, (numg, numt))) for u in ubars]
+
+
+def _disk_per_spectrum(nspec, numg, numt, ubar0, ubar1, cos_theta):
+    """``ngeom, ubar0, ubar1, cos_theta`` of a batched launch: ``(numg, numt)`` arrays and a scalar ``cos_theta`` for all
+    spectra (``ngeom = 1``) or ``(nspec, numg, numt)`` and ``nspec`` values.  ``ubar0=None``: a thermal launch."""
+    u1 = np.asarray(ubar1, dtype=np.float64)
+    u0 = u1 if ubar0 is None else np.asarray(ubar0, dtype=np.float64)
+    ngeom = nspec if u0.ndim == 3 else 1
+    shape = (nspec, numg, numt) if ngeom > 1 else (numg, numt)
+    ct = ptr(f64(np.zeros(ngeom) + np.asarray(cos_theta, dtype=np.float64), (ngeom,)))
+    return ngeom, (None if ubar0 is None else ptr(f64(u0, shape))), ptr(f64(u1, shape)), ct
+
+
+def _weights(gweight, tweight):
+    """Pointers to the disk-integration weights, each NULL when not given."""
+    return _opt(f64(gweight) if gweight is not None else None), _opt(f64(tweight) if tweight is not None else None)
+
+
+def _pitch(nwno, plane_pitch):
+    return nwno if plane_pitch is None else plane_pitch
+
+
+def _levels(lvl_fluxes):
+    """``get_lvl_flux`` and the four level-flux addresses (flux_minus, flux_plus, flux_minus_mdpt, flux_plus_mdpt)."""
+    if lvl_fluxes is None:
+        return 0, [None] * 4
+    return 1, [addr(x) for x in lvl_fluxes]
+
+
+def _per_spectrum(x, nspec):
+    """One entry for all spectra or a list of ``nspec``."""
+    if isinstance(x, (list, tuple)):
+        if len(x) != nspec:
+            raise Exception("batched call: expected %d per-spectrum entries, got %d" % (nspec, len(x)))
+        return list(x)
+    return [x] * nspec
+
+
+def _table(x, nspec):
+    """Pointer table of a per-spectrum argument (one entry for all spectra or a list of ``nspec``)."""
+    return ptr_array(_per_spectrum(x, nspec))
+
+
+def _columns(names, planes, strict=False, family=False):
+    """One pointer table per plane name over a list of plane dictionaries; a plane a dictionary lacks is a NULL entry
+    (``strict``: an error).  ``family``: a name the first dictionary lacks is left out as a whole -- NULL, not a table."""
+    cols = []
+    for k in names:
+        if family and planes[0].get(k) is None:
+            cols.append(None)
+        else:
+            cols.append(ptr_array([pl[k] if strict or family else pl.get(k) for pl in planes]))
+    return cols
+
+
+def _fused(nspec, out, gweight, tweight):
+    """The batch forms' fused disk sum ``(gweight, tweight, out table)``: handed over only when all three are given."""
+    if out is None or gweight is None or tweight is None:
+        return None, None, None
+    return (*_weights(gweight, tweight), _table(out, nspec))
+
+
 def upload_scene(scene, keys, w_lo=None, w_hi=None, ctx=None, seal=True):
     """Upload the named (rows, nwno) planes / (nwno) vectors of a host scene dict, optionally only
     the wavelength shard [w_lo, w_hi).  ``seal``: a set that holds all of ``REFLECTED_PLANES`` as ``(nlayer | nlevel,
@@ -80,31 +153,26 @@ def reflected_can_derive(nlevel, nwno, numg, numt, ubar0, ubar1, cos_theta, sing
     """True when ``reflected_1d`` / ``reflected_1d_batch`` with these arguments may be handed ``None`` for the planes the
     kernels re-derive (``tau``, ``tau_og``, ``gcos2``; for an atmosphere without cloud everything but ``dtau`` and
     ``w0``): ``picaso_reflected_1d_can_derive``."""
-    u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
     return bool(load().picaso_reflected_1d_can_derive(
-        nlevel, nwno, numg, numt, ptr(u0), ptr(u1), cos_theta, single_phase,
+        nlevel, nwno, numg, numt, *_disk(numg, numt, ubar0, ubar1), cos_theta, single_phase,
         multi_phase, frac_c, toon_coefficients, 1 if get_lvl_flux else 0))
 
 
 def reflected_1d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta,
                  F0PI, single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back,
                  constant_forward, xint_at_top, toon_coefficients=0, b_top=0.0, gweight=None,
-                 tweight=None, albedo=None, plane_pitch=None):
+                 tweight=None, albedo=None, plane_pitch=None, lvl_fluxes=None):
     """Asynchronous ``get_reflected_1d`` on resident planes (+ optional fused ``compress_disco``).
     ``planes`` maps the 11 reference plane names to DeviceArrays; outputs are DeviceArrays (or raw
-    device addresses)."""
-    u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    pitch = nwno if plane_pitch is None else plane_pitch
+    device addresses).  ``lvl_fluxes`` = four ``(numg,numt,nlevel,nwno)`` DeviceArrays (flux_minus, flux_plus,
+    flux_minus_mdpt, flux_plus_mdpt) turns ``get_lvl_flux`` on."""
+    get_lvl_flux, lv = _levels(lvl_fluxes)
     check(load().picaso_get_reflected_1d_dev(
-        ctx, nlevel, nwno, pitch, numg, numt,
-        *[addr(planes.get(k)) for k in REFLECTED_PLANES], addr(surf_reflect), ptr(u0), ptr(u1),
+        ctx, nlevel, nwno, _pitch(nwno, plane_pitch), numg, numt,
+        *[addr(planes.get(k)) for k in REFLECTED_PLANES], addr(surf_reflect), *_disk(numg, numt, ubar0, ubar1),
         cos_theta, addr(F0PI), single_phase, multi_phase, frac_a, frac_b,
-        frac_c, constant_back, constant_forward, 1, 0,
-        toon_coefficients, b_top, addr(xint_at_top), None, None, None, None,
-        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None, addr(albedo)),
-        ctx)
+        frac_c, constant_back, constant_forward, 1, get_lvl_flux,
+        toon_coefficients, b_top, addr(xint_at_top), *lv, *_weights(gweight, tweight), addr(albedo)), ctx)
 
 
 def thermal_1d(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb, plevel, ubar1,
@@ -112,27 +180,11 @@ def thermal_1d(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb, pleve
                tweight=None, flux_disk=None, plane_pitch=None, lvl_fluxes=None):
     """Asynchronous ``get_thermal_1d`` on resident planes (+ optional fused ``compress_thermal``).
     ``wno``/``dwno``/``surf_reflect`` and the planes are device-resident; tlevel/plevel host."""
-    u1 = f64(ubar1, (numg, numt))
-    tl, pl = f64(tlevel), f64(plevel)
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    pitch = nwno if plane_pitch is None else plane_pitch
     check(load().picaso_get_thermal_1d_dev(
-        ctx, nlevel, addr(wno), nwno, pitch, numg, numt,
-        ptr(tl), addr(dtau), addr(w0), addr(cosb), ptr(pl), ptr(u1), addr(surf_reflect),
-        int(hard_surface), addr(dwno), calc_type, addr(flux_at_top),
-        *[addr(x) for x in (lvl_fluxes if lvl_fluxes is not None else [None] * 4)],
-        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None,
-        addr(flux_disk)), ctx)
-
-
-def _per_spectrum(x, nspec):
-    """One entry for all spectra or a list of ``nspec``."""
-    if isinstance(x, (list, tuple)):
-        if len(x) != nspec:
-            raise Exception("batched call: expected %d per-spectrum entries, got %d" % (nspec, len(x)))
-        return list(x)
-    return [x] * nspec
+        ctx, nlevel, addr(wno), nwno, _pitch(nwno, plane_pitch), numg, numt,
+        ptr(f64(tlevel)), addr(dtau), addr(w0), addr(cosb), ptr(f64(plevel)), *_disk(numg, numt, ubar1),
+        addr(surf_reflect), int(hard_surface), addr(dwno), calc_type, addr(flux_at_top), *_levels(lvl_fluxes)[1],
+        *_weights(gweight, tweight), addr(flux_disk)), ctx)
 
 
 def reflected_1d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -146,27 +198,11 @@ def reflected_1d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar
     and a scalar ``cos_theta`` for all spectra, or ``(nspec, numg, numt)`` and ``nspec`` values.  Spectrum ``s``
     of the result is bit-identical to ``reflected_1d`` on its own arguments."""
     nspec = len(planes)
-    u0, u1 = np.asarray(ubar0, dtype=np.float64), np.asarray(ubar1, dtype=np.float64)
-    ngeom = nspec if u0.ndim == 3 else 1
-    shape = (nspec, numg, numt) if ngeom > 1 else (numg, numt)
-    u0, u1 = f64(u0, shape), f64(u1, shape)
-    ct = f64(np.zeros(ngeom) + np.asarray(cos_theta, dtype=np.float64), (ngeom,))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    pitch = nwno if plane_pitch is None else plane_pitch
-    cols = []
-    for k in REFLECTED_PLANES:
-        cols.append(ptr_array([pl.get(k) for pl in planes]))
-    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
-    p_f0 = ptr_array(_per_spectrum(F0PI, nspec))
-    p_x = ptr_array(_per_spectrum(xint_at_top, nspec))
-    fuse = albedo is not None and gw is not None and tw is not None
-    p_al = ptr_array(_per_spectrum(albedo, nspec)) if fuse else None
     check(load().picaso_get_reflected_1d_batch_dev(
-        ctx, nspec, nlevel, nwno, pitch, numg, numt, *cols, p_rs,
-        ngeom, ptr(u0), ptr(u1), ptr(ct), p_f0, single_phase, multi_phase, frac_a, frac_b,
-        frac_c, constant_back, constant_forward, toon_coefficients, b_top, p_x,
-        ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
+        ctx, nspec, nlevel, nwno, _pitch(nwno, plane_pitch), numg, numt, *_columns(REFLECTED_PLANES, planes),
+        _table(surf_reflect, nspec), *_disk_per_spectrum(nspec, numg, numt, ubar0, ubar1, cos_theta), _table(F0PI, nspec),
+        single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back, constant_forward, toon_coefficients, b_top,
+        _table(xint_at_top, nspec), *_fused(nspec, albedo, gweight, tweight)), ctx)
 
 
 def thermal_1d_batch(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb, plevel, ubar1, surf_reflect,
@@ -177,24 +213,12 @@ def thermal_1d_batch(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb,
     ``flux_disk`` lists of DeviceArrays, ``surf_reflect`` one DeviceArray or a list, ``wno`` / ``dwno`` shared;
     ``ubar1`` ``(numg, numt)`` or ``(nspec, numg, numt)``.  Bit-identical per spectrum to ``thermal_1d``."""
     nspec = len(dtau)
-    u1 = np.asarray(ubar1, dtype=np.float64)
-    ngeom = nspec if u1.ndim == 3 else 1
-    u1 = f64(u1, (nspec, numg, numt) if ngeom > 1 else (numg, numt))
-    tl, pl = f64(tlevel, (nspec, nlevel)), f64(plevel, (nspec, nlevel))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    pitch = nwno if plane_pitch is None else plane_pitch
-    p_dt = ptr_array(list(dtau))
-    p_w0 = ptr_array(_per_spectrum(w0, nspec))
-    p_cb = ptr_array(_per_spectrum(cosb, nspec))
-    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
-    p_fx = ptr_array(_per_spectrum(flux_at_top, nspec))
-    fuse = flux_disk is not None and gw is not None and tw is not None
-    p_fd = ptr_array(_per_spectrum(flux_disk, nspec)) if fuse else None
+    ngeom, _, u1, _ = _disk_per_spectrum(nspec, numg, numt, None, ubar1, 0.0)
     check(load().picaso_get_thermal_1d_batch_dev(
-        ctx, nspec, nlevel, addr(wno), nwno, pitch, numg, numt, ptr(tl),
-        p_dt, p_w0, p_cb, ptr(pl), ngeom, ptr(u1), p_rs, int(hard_surface), addr(dwno), calc_type,
-        p_fx, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_fd), ctx)
+        ctx, nspec, nlevel, addr(wno), nwno, _pitch(nwno, plane_pitch), numg, numt, ptr(f64(tlevel, (nspec, nlevel))),
+        ptr_array(list(dtau)), _table(w0, nspec), _table(cosb, nspec), ptr(f64(plevel, (nspec, nlevel))), ngeom, u1,
+        _table(surf_reflect, nspec), int(hard_surface), addr(dwno), calc_type, _table(flux_at_top, nspec),
+        *_fused(nspec, flux_disk, gweight, tweight)), ctx)
 
 
 def reflected_1d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect, ubar0, ubar1,
@@ -207,19 +231,13 @@ def reflected_1d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect,
     exactly as ``compute_opacity`` lays them out, ``xint_at_top`` is the Gauss-weighted
     ``(numg,numt,nwno)`` result; ``lvl_fluxes`` = four ``(numg,numt,nlevel,nwno)`` DeviceArrays
     (flux_minus, flux_plus, flux_minus_mdpt, flux_plus_mdpt) turns ``get_lvl_flux`` on."""
-    u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    wts = f64(gauss_wts, (ngauss,))
-    lv = list(lvl_fluxes) if lvl_fluxes is not None else [None] * 4
+    get_lvl_flux, lv = _levels(lvl_fluxes)
     check(load().picaso_get_reflected_1d_ck_dev(
         ctx, nlevel, nwno, ngauss, numg, numt,
-        *[addr(planes[k]) for k in REFLECTED_PLANES], addr(surf_reflect), ptr(u0), ptr(u1),
+        *[addr(planes[k]) for k in REFLECTED_PLANES], addr(surf_reflect), *_disk(numg, numt, ubar0, ubar1),
         cos_theta, addr(F0PI), single_phase, multi_phase, frac_a, frac_b,
-        frac_c, constant_back, constant_forward, int(get_toa_intensity),
-        1 if lvl_fluxes is not None else 0, toon_coefficients, b_top, ptr(wts),
-        addr(xint_at_top), *[addr(x) for x in lv], ptr(gw) if gw is not None else None,
-        ptr(tw) if tw is not None else None, addr(albedo)), ctx)
+        frac_c, constant_back, constant_forward, int(get_toa_intensity), get_lvl_flux, toon_coefficients, b_top,
+        ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), *lv, *_weights(gweight, tweight), addr(albedo)), ctx)
 
 
 def thermal_1d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, cosb, plevel, ubar1,
@@ -228,18 +246,11 @@ def thermal_1d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, 
     """The ``ngauss`` loop around ``get_thermal_1d`` (justdoit.py:328-380) as one launch; planes
     ``(nlayer, nwno, ngauss)``, result Gauss-weighted ``(numg,numt,nwno)``; optional Gauss-weighted
     level fluxes as in ``reflected_1d_ck``."""
-    u1 = f64(ubar1, (numg, numt))
-    tl, pl = f64(tlevel), f64(plevel)
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    wts = f64(gauss_wts, (ngauss,))
-    lv = list(lvl_fluxes) if lvl_fluxes is not None else [None] * 4
     check(load().picaso_get_thermal_1d_ck_dev(
-        ctx, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(tl),
-        addr(dtau), addr(w0), addr(cosb), ptr(pl), ptr(u1), addr(surf_reflect),
-        int(hard_surface), addr(dwno), calc_type, ptr(wts), addr(flux_at_top),
-        *[addr(x) for x in lv], ptr(gw) if gw is not None else None,
-        ptr(tw) if tw is not None else None, addr(flux_disk)), ctx)
+        ctx, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(f64(tlevel)),
+        addr(dtau), addr(w0), addr(cosb), ptr(f64(plevel)), *_disk(numg, numt, ubar1), addr(surf_reflect),
+        int(hard_surface), addr(dwno), calc_type, ptr(f64(gauss_wts, (ngauss,))), addr(flux_at_top),
+        *_levels(lvl_fluxes)[1], *_weights(gweight, tweight), addr(flux_disk)), ctx)
 
 
 def thermal_1d_ck_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dtau, w0, cosb, plevel, ubar1, surf_reflect,
@@ -253,9 +264,9 @@ def thermal_1d_ck_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dt
     tl = f64(tl, (nitem, nlevel))
     check(load().picaso_get_thermal_1d_ck_tbatch_dev(
         ctx, nitem, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(tl), addr(dtau),
-        addr(w0), addr(cosb), ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), addr(surf_reflect),
-        int(hard_surface), addr(dwno), calc_type, ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight)),
-        ptr(f64(tweight)), addr(disk4)), ctx)
+        addr(w0), addr(cosb), ptr(f64(plevel, (nlevel,))), *_disk(numg, numt, ubar1), addr(surf_reflect),
+        int(hard_surface), addr(dwno), calc_type, ptr(f64(gauss_wts, (ngauss,))), *_weights(gweight, tweight),
+        addr(disk4)), ctx)
 
 
 def thermal_nets_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dtau, w0, cosb, plevel, ubar1, surf_reflect,
@@ -269,7 +280,7 @@ def thermal_nets_tbatch(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevels, dta
     tl = f64(tl, (nitem, nlevel))
     check(load().picaso_thermal_nets_tbatch_dev(
         ctx, nitem, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(tl), addr(dtau), addr(w0), addr(cosb),
-        ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))), addr(surf_reflect), int(hard_surface), addr(dwno),
+        ptr(f64(plevel, (nlevel,))), *_disk(numg, numt, ubar1), addr(surf_reflect), int(hard_surface), addr(dwno),
         ptr(f64(gauss_wts, (ngauss,))), ptr(f64(gweight, (numg,))), ptr(f64(tweight, (numt,))), addr(net_layer),
         addr(net)), ctx)
 
@@ -363,25 +374,21 @@ def reflected_SH(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, uba
                  w_single_form, w_multi_form, psingle_form, w_single_rayleigh, w_multi_rayleigh,
                  psingle_rayleigh, frac_a, frac_b, frac_c, constant_back, constant_forward, stream,
                  xint_at_top, b_top=0.0, single_form=0, compound_f_deltaM=True, gweight=None, tweight=None,
-                 albedo=None, plane_pitch=None, cloud_free_above=0):
-    """Asynchronous ``get_reflected_SH`` (``flx=0``) on resident planes (+ optional fused
+                 albedo=None, plane_pitch=None, cloud_free_above=0, flux=None):
+    """Asynchronous ``get_reflected_SH`` on resident planes (+ optional fused
     ``compress_disco``); ``planes`` maps ``SH_PLANES`` to DeviceArrays.  A cloud-free atmosphere may give ``dtau``
     and ``w0`` only (``reflected_SH_can_derive``): the other planes are constants, copies and running sums.
     ``cloud_free_above``: the caller's statement that the first that many layers carry no cloud in any column
-    (``picaso_get_reflected_SH_top_dev``)."""
-    u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    pitch = nwno if plane_pitch is None else plane_pitch
+    (``picaso_get_reflected_SH_top_dev``).  ``flux``: a ``(numg, numt, stream*nlevel, nwno)`` DeviceArray for the layer
+    moment fluxes turns ``flx`` on."""
     check(load().picaso_get_reflected_SH_top_dev(
-        ctx, nlevel, nwno, pitch, numg, numt,
-        *[addr(planes.get(k)) for k in SH_PLANES], addr(surf_reflect), ptr(u0), ptr(u1), cos_theta,
+        ctx, nlevel, nwno, _pitch(nwno, plane_pitch), numg, numt,
+        *[addr(planes.get(k)) for k in SH_PLANES], addr(surf_reflect), *_disk(numg, numt, ubar0, ubar1), cos_theta,
         addr(F0PI), int(w_single_form), int(w_multi_form), int(psingle_form),
         int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh), frac_a,
         frac_b, frac_c, constant_back, constant_forward, int(stream), b_top,
-        0, int(single_form), 1 if compound_f_deltaM else 0, int(cloud_free_above),
-        addr(xint_at_top), None,
-        ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None, addr(albedo)), ctx)
+        1 if flux is not None else 0, int(single_form), 1 if compound_f_deltaM else 0, int(cloud_free_above),
+        addr(xint_at_top), addr(flux), *_weights(gweight, tweight), addr(albedo)), ctx)
 
 
 def reflected_SH_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -393,28 +400,13 @@ def reflected_SH_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar
     ``reflected_1d_batch`` with ``planes`` a list of ``SH_PLANES`` dictionaries.  Bit-identical per spectrum to
     ``reflected_SH``."""
     nspec = len(planes)
-    u0, u1 = np.asarray(ubar0, dtype=np.float64), np.asarray(ubar1, dtype=np.float64)
-    ngeom = nspec if u0.ndim == 3 else 1
-    shape = (nspec, numg, numt) if ngeom > 1 else (numg, numt)
-    u0, u1 = f64(u0, shape), f64(u1, shape)
-    ct = f64(np.zeros(ngeom) + np.asarray(cos_theta, dtype=np.float64), (ngeom,))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    pitch = nwno if plane_pitch is None else plane_pitch
-    cols = []
-    for k in SH_PLANES:
-        cols.append(ptr_array([pl[k] for pl in planes]))
-    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
-    p_f0 = ptr_array(_per_spectrum(F0PI, nspec))
-    p_x = ptr_array(_per_spectrum(xint_at_top, nspec))
-    fuse = albedo is not None and gw is not None and tw is not None
-    p_al = ptr_array(_per_spectrum(albedo, nspec)) if fuse else None
     check(load().picaso_get_reflected_SH_batch_dev(
-        ctx, nspec, nlevel, nwno, pitch, numg, numt, *cols, p_rs, ngeom,
-        ptr(u0), ptr(u1), ptr(ct), p_f0, int(w_single_form), int(w_multi_form), int(psingle_form),
-        int(w_single_rayleigh), int(w_multi_rayleigh), int(psingle_rayleigh), frac_a, frac_b,
-        frac_c, constant_back, constant_forward, int(stream), b_top, int(single_form),
-        1 if compound_f_deltaM else 0, p_x, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
+        ctx, nspec, nlevel, nwno, _pitch(nwno, plane_pitch), numg, numt, *_columns(SH_PLANES, planes, strict=True),
+        _table(surf_reflect, nspec), *_disk_per_spectrum(nspec, numg, numt, ubar0, ubar1, cos_theta), _table(F0PI, nspec),
+        int(w_single_form), int(w_multi_form), int(psingle_form), int(w_single_rayleigh), int(w_multi_rayleigh),
+        int(psingle_rayleigh), frac_a, frac_b, frac_c, constant_back, constant_forward, int(stream), b_top,
+        int(single_form), 1 if compound_f_deltaM else 0, _table(xint_at_top, nspec),
+        *_fused(nspec, albedo, gweight, tweight)), ctx)
 
 
 def reflected_3d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -423,30 +415,21 @@ def reflected_3d(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, uba
     """``get_reflected_3d`` on resident ``(nlayer|nlevel, nwno, numg, numt)`` planes (+ optional fused
     ``compress_disco``).  Planes missing from ``planes`` are passed as NULL: the kernel re-derives them
     (picaso_hip.h: tau / tau_og / gcos2; no-cloud constants; no delta-scaling)."""
-    u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_reflected_3d_dev(
         ctx, nlevel, nwno, numg, numt, *[addr(planes.get(k)) for k in REFLECTED_PLANES],
-        addr(surf_reflect), ptr(u0), ptr(u1), cos_theta, addr(F0PI), single_phase,
+        addr(surf_reflect), *_disk(numg, numt, ubar0, ubar1), cos_theta, addr(F0PI), single_phase,
         multi_phase, frac_a, frac_b, frac_c, constant_back,
-        constant_forward, addr(xint_at_top), ptr(gw) if gw is not None else None,
-        ptr(tw) if tw is not None else None, addr(albedo)), ctx)
+        constant_forward, addr(xint_at_top), *_weights(gweight, tweight), addr(albedo)), ctx)
 
 
 def thermal_3d(ctx, nlevel, wno, nwno, numg, numt, tlevel_3d, dtau_3d, w0_3d, cosb_3d, plevel_3d, ubar1,
                surf_reflect, hard_surface, int_at_top, gweight=None, tweight=None, flux_disk=None):
     """``get_thermal_3d`` on resident ``(nlayer, nwno, numg, numt)`` planes; ``tlevel_3d`` /
     ``plevel_3d`` host ``(nlevel, numg, numt)``."""
-    u1 = f64(ubar1, (numg, numt))
-    tl, pl = f64(tlevel_3d, (nlevel, numg, numt)), f64(plevel_3d, (nlevel, numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_thermal_3d_dev(
-        ctx, nlevel, addr(wno), nwno, numg, numt, ptr(tl), addr(dtau_3d),
-        addr(w0_3d), addr(cosb_3d), ptr(pl), ptr(u1), addr(surf_reflect), int(hard_surface),
-        addr(int_at_top), ptr(gw) if gw is not None else None, ptr(tw) if tw is not None else None,
-        addr(flux_disk)), ctx)
+        ctx, nlevel, addr(wno), nwno, numg, numt, ptr(f64(tlevel_3d, (nlevel, numg, numt))), addr(dtau_3d),
+        addr(w0_3d), addr(cosb_3d), ptr(f64(plevel_3d, (nlevel, numg, numt))), *_disk(numg, numt, ubar1),
+        addr(surf_reflect), int(hard_surface), addr(int_at_top), *_weights(gweight, tweight), addr(flux_disk)), ctx)
 
 
 def reflected_3d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -460,25 +443,12 @@ def reflected_3d_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar
     keys = set(planes[0].keys())
     if any(set(pl.keys()) != keys for pl in planes):
         raise Exception("reflected_3d_batch: every spectrum must hand over the same set of planes")
-    u0, u1 = f64(ubar0, (nspec, numg, numt)), f64(ubar1, (nspec, numg, numt))
     ct = f64(np.zeros(nspec) + np.asarray(cos_theta, dtype=np.float64), (nspec,))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    cols = []
-    for k in REFLECTED_PLANES:
-        if planes[0].get(k) is None:
-            cols.append(None)
-            continue
-        cols.append(ptr_array([pl[k] for pl in planes]))
-    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
-    p_f0 = ptr_array(_per_spectrum(F0PI, nspec))
-    p_x = ptr_array(_per_spectrum(xint_at_top, nspec))
-    fuse = albedo is not None and gw is not None and tw is not None
-    p_al = ptr_array(_per_spectrum(albedo, nspec)) if fuse else None
     check(load().picaso_get_reflected_3d_batch_dev(
-        ctx, nspec, nlevel, nwno, numg, numt, *cols, p_rs, ptr(u0), ptr(u1), ptr(ct), p_f0,
-        single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back,
-        constant_forward, p_x, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_al), ctx)
+        ctx, nspec, nlevel, nwno, numg, numt, *_columns(REFLECTED_PLANES, planes, family=True),
+        _table(surf_reflect, nspec), ptr(f64(ubar0, (nspec, numg, numt))), ptr(f64(ubar1, (nspec, numg, numt))), ptr(ct),
+        _table(F0PI, nspec), single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back, constant_forward,
+        _table(xint_at_top, nspec), *_fused(nspec, albedo, gweight, tweight)), ctx)
 
 
 def reflected_3d_fm_batch(ctx, nlevel, nwno, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -536,27 +506,29 @@ def thermal_3d_batch(ctx, nlevel, wno, nwno, numg, numt, tlevel_3d, dtau_3d, w0_
     planes lists of DeviceArrays (``cosb_3d=None``: no cloud in any spectrum).  Bit-identical per spectrum to
     ``thermal_3d``."""
     nspec = len(dtau_3d)
-    u1 = f64(ubar1, (nspec, numg, numt))
-    tl, pl = f64(tlevel_3d, (nspec, nlevel, numg, numt)), f64(plevel_3d, (nspec, nlevel, numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
-    p_dt = ptr_array(list(dtau_3d))
-    p_w0 = ptr_array(list(w0_3d))
-    p_cb = ptr_array(list(cosb_3d)) if cosb_3d is not None else None
-    p_rs = ptr_array(_per_spectrum(surf_reflect, nspec))
-    p_fx = ptr_array(_per_spectrum(int_at_top, nspec))
-    fuse = flux_disk is not None and gw is not None and tw is not None
-    p_fd = ptr_array(_per_spectrum(flux_disk, nspec)) if fuse else None
+    shape = (nspec, nlevel, numg, numt)
     check(load().picaso_get_thermal_3d_batch_dev(
-        ctx, nspec, nlevel, addr(wno), nwno, numg, numt, ptr(tl), p_dt, p_w0, p_cb, ptr(pl),
-        ptr(u1), p_rs, int(hard_surface), p_fx, ptr(gw) if fuse else None, ptr(tw) if fuse else None, p_fd), ctx)
+        ctx, nspec, nlevel, addr(wno), nwno, numg, numt, ptr(f64(tlevel_3d, shape)), ptr_array(list(dtau_3d)),
+        ptr_array(list(w0_3d)), ptr_array(list(cosb_3d)) if cosb_3d is not None else None, ptr(f64(plevel_3d, shape)),
+        ptr(f64(ubar1, (nspec, numg, numt))), _table(surf_reflect, nspec), int(hard_surface), _table(int_at_top, nspec),
+        *_fused(nspec, flux_disk, gweight, tweight)), ctx)
 
 
 # ------------------------------------------------------------------------------------------------
-# the correlated-k Gauss-point loop around the SH and the 3-D solvers (csrc/ckloop.hip)
+# the spherical-harmonics thermal solver, and the correlated-k Gauss-point loop around the SH and the 3-D solvers
+# (csrc/ckloop.hip)
 # ------------------------------------------------------------------------------------------------
-def _opt(x):
-    return ptr(x) if x is not None else None
+def thermal_SH(ctx, nlevel, wno, nwno, numg, numt, tlevel, dtau, w0, cosb_og, plevel, ubar1, surf_reflect, stream,
+               hard_surface, cosb_differs_from_cosb_og, xint_at_top, tau=None, gweight=None, tweight=None, flux_disk=None,
+               plane_pitch=None):
+    """Asynchronous ``get_thermal_SH`` (``flx=0``) on resident ``(nlayer, nwno)`` planes (+ optional fused
+    ``compress_thermal``; ``picaso_get_thermal_SH_dev``); ``cosb_differs_from_cosb_og`` as in ``thermal_SH_ck``.  ``tau``
+    is never read."""
+    check(load().picaso_get_thermal_SH_dev(
+        ctx, nlevel, addr(wno), nwno, _pitch(nwno, plane_pitch), numg, numt, ptr(f64(tlevel, (nlevel,))), addr(dtau),
+        addr(tau), addr(w0), addr(cosb_og), ptr(f64(plevel, (nlevel,))), *_disk(numg, numt, ubar1), addr(surf_reflect),
+        int(stream), int(hard_surface), 1 if cosb_differs_from_cosb_og else 0, 0, addr(xint_at_top),
+        *_weights(gweight, tweight), addr(flux_disk)), ctx)
 
 
 def reflected_SH_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -566,16 +538,13 @@ def reflected_SH_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect,
     """The reference's ``for ig in range(ngauss)`` loop around ``get_reflected_SH`` (justdoit.py:256-269, :307) as one
     launch: ``planes`` maps ``SH_PLANES`` to ``(nlayer|nlevel, nwno, ngauss)`` DeviceArrays as ``compute_opacity`` lays
     them out; ``xint_at_top`` the Gauss-weighted ``(numg, numt, nwno)`` result (``picaso_get_reflected_SH_ck_dev``)."""
-    u0, u1 = f64(ubar0, (numg, numt)), f64(ubar1, (numg, numt))
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_reflected_SH_ck_dev(
         ctx, nlevel, nwno, ngauss, numg, numt, *[addr(planes.get(k)) for k in SH_PLANES],
-        addr(surf_reflect), ptr(u0), ptr(u1), cos_theta, addr(F0PI), int(w_single_form),
+        addr(surf_reflect), *_disk(numg, numt, ubar0, ubar1), cos_theta, addr(F0PI), int(w_single_form),
         int(w_multi_form), int(psingle_form), int(w_single_rayleigh), int(w_multi_rayleigh),
         int(psingle_rayleigh), frac_a, frac_b, frac_c, constant_back, constant_forward,
         int(stream), b_top, int(single_form), 1 if compound_f_deltaM else 0,
-        int(cloud_free_above), ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), _opt(gw), _opt(tw),
+        int(cloud_free_above), ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), *_weights(gweight, tweight),
         addr(albedo)), ctx)
 
 
@@ -585,13 +554,11 @@ def thermal_SH_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel, dtau, w0, 
     """The ``ngauss`` loop around ``get_thermal_SH`` (justdoit.py:364-370, :380) as one launch
     (``picaso_get_thermal_SH_ck_dev``): planes ``(nlayer, nwno, ngauss)``; ``cosb_differs_from_cosb_og`` is the
     reference's ``np.array_equal(cosb, cosb_og)`` test (fluxes.py:3072-3075), evaluated by the caller."""
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_thermal_SH_ck_dev(
         ctx, nlevel, addr(wno), nwno, ngauss, numg, numt, ptr(f64(tlevel, (nlevel,))),
-        addr(dtau), addr(tau), addr(w0), addr(cosb_og), ptr(f64(plevel, (nlevel,))), ptr(f64(ubar1, (numg, numt))),
+        addr(dtau), addr(tau), addr(w0), addr(cosb_og), ptr(f64(plevel, (nlevel,))), *_disk(numg, numt, ubar1),
         addr(surf_reflect), int(stream), int(hard_surface), 1 if cosb_differs_from_cosb_og else 0,
-        ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), _opt(gw), _opt(tw), addr(flux_disk)), ctx)
+        ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), *_weights(gweight, tweight), addr(flux_disk)), ctx)
 
 
 def reflected_3d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect, ubar0, ubar1, cos_theta, F0PI,
@@ -600,13 +567,11 @@ def reflected_3d_ck(ctx, nlevel, nwno, ngauss, numg, numt, planes, surf_reflect,
     """The ``ngauss`` loop around ``get_reflected_3d`` (justdoit.py:488-500) as one launch on FACET-MAJOR planes
     ``(numg*numt, nlayer|nlevel, nwno, ngauss)`` (``optics.compute_opacity_facet_major_ck``); planes missing from
     ``planes`` are passed as NULL and re-derived (``picaso_get_reflected_3d_ck_dev``)."""
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_reflected_3d_ck_dev(
         ctx, nlevel, nwno, ngauss, numg, numt, *[addr(planes.get(k)) for k in REFLECTED_PLANES],
-        addr(surf_reflect), ptr(f64(ubar0, (numg, numt))), ptr(f64(ubar1, (numg, numt))), cos_theta, addr(F0PI),
+        addr(surf_reflect), *_disk(numg, numt, ubar0, ubar1), cos_theta, addr(F0PI),
         single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back,
-        constant_forward, ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), _opt(gw), _opt(tw), addr(albedo)), ctx)
+        constant_forward, ptr(f64(gauss_wts, (ngauss,))), addr(xint_at_top), *_weights(gweight, tweight), addr(albedo)), ctx)
 
 
 def thermal_3d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel_3d, dtau, w0, cosb, plevel_3d, ubar1, surf_reflect,
@@ -614,11 +579,9 @@ def thermal_3d_ck(ctx, nlevel, wno, nwno, ngauss, numg, numt, tlevel_3d, dtau, w
     """The ``ngauss`` loop around ``get_thermal_3d`` (justdoit.py:502-516) as one launch on facet-major planes
     ``(numg*numt, nlayer, nwno, ngauss)``; ``tlevel_3d`` / ``plevel_3d`` host ``(nlevel, numg, numt)``
     (``picaso_get_thermal_3d_ck_dev``)."""
-    gw = f64(gweight) if gweight is not None else None
-    tw = f64(tweight) if tweight is not None else None
     check(load().picaso_get_thermal_3d_ck_dev(
         ctx, nlevel, addr(wno), nwno, ngauss, numg, numt,
         ptr(f64(tlevel_3d, (nlevel, numg, numt))), addr(dtau), addr(w0), addr(cosb),
-        ptr(f64(plevel_3d, (nlevel, numg, numt))), ptr(f64(ubar1, (numg, numt))), addr(surf_reflect),
-        int(hard_surface), ptr(f64(gauss_wts, (ngauss,))), addr(int_at_top), _opt(gw), _opt(tw),
+        ptr(f64(plevel_3d, (nlevel, numg, numt))), *_disk(numg, numt, ubar1), addr(surf_reflect),
+        int(hard_surface), ptr(f64(gauss_wts, (ngauss,))), addr(int_at_top), *_weights(gweight, tweight),
         addr(flux_disk)), ctx)

@@ -2,15 +2,16 @@
 
 ``justdoit.picaso`` is the entry point and decides between the one-C-call driver (csrc/driver.hip), the multi-GPU split
 (``devices=``) and this module's ``Spectrum``; ``spectrum_batch`` and ``phase_curve`` enqueue several ``Spectrum`` objects
-before they finish the first.  The helpers here are the resident per-wavelength vectors, the ATMSETUP sequence, the
-launch wrappers of the solvers and the spectrum-wide post-processing (Bond albedo, flux ratios, effective temperature).
+before they finish the first.  The helpers here are the resident per-wavelength vectors, the ATMSETUP sequence and the
+spectrum-wide post-processing (Bond albedo, flux ratios, effective temperature); every solver launch is marshalled by
+``resident``, the monochromatic Toon solves as ``solvebatch`` records that go alone or wait for their batch.
 """
 import copy
 import warnings
 
 import numpy as np
 
-from . import _lib, device, fastsetup, optics, planes, resident
+from . import _lib, device, fastsetup, optics, planes, resident, solvebatch
 from . import options as _options
 from .atmsetup import ATMSETUP, CloudTables
 from .device import DeviceArray
@@ -148,15 +149,6 @@ def _atmosphere_block(atm0, lo, hi, wno):
     if np.ndim(sr) > 0 and np.size(sr) == np.size(atm0.wavenumber):
         atm.surf_reflect = np.ascontiguousarray(np.asarray(sr, dtype=float)[lo:hi])
     return atm
-
-
-def _reflected_3d_fm(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta, F0PI, single_phase, multi_phase,
-                     frac_a, frac_b, frac_c, constant_back, constant_forward, xint, gweight, tweight, albedo):
-    """``resident.reflected_3d`` for facet-major planes (one spectrum through ``reflected_3d_fm_batch``)."""
-    resident.reflected_3d_fm_batch(ctx, nlevel, nwno, ng, nt, [planes], [rs], np.asarray(ubar0, dtype=float).reshape(1, ng, nt),
-                                   np.asarray(ubar1, dtype=float).reshape(1, ng, nt), np.array([cos_theta], dtype=float),
-                                   [F0PI], single_phase, multi_phase, frac_a, frac_b, frac_c, constant_back,
-                                   constant_forward, [xint], gweight, tweight, [albedo])
 
 
 def _fetch(prefetched, key, dev, returns=None, integral=None):
@@ -443,8 +435,10 @@ class Spectrum:
             sh_flux = None                                       # layer moment fluxes, flx = calculate_fluxes
             if sh["calculate_fluxes"]:
                 sh_flux = DeviceArray((ng, nt, stream * nlevel, nwno), ctx)
-            _reflected_sh(ctx, nlevel, nwno, ng, nt, pl, *geo, sh, *self.tthg[2:], stream, self.b_top, x, self.gweight,
-                          self.tweight, self.alb, sh_flux, cloud_free_above=self.sh_top)
+            # the disk sum is fused into this launch whatever `fuse` says (no patchy-cloud blend with SH)
+            resident.reflected_SH(ctx, nlevel, nwno, ng, nt, pl, *geo, *forms, *self.tthg[2:], stream, x, b_top=self.b_top,
+                                  single_form=sh["single_form"], gweight=self.gweight, tweight=self.tweight,
+                                  albedo=self.alb, cloud_free_above=self.sh_top, flux=sh_flux)
             if sh_flux is not None:
                 self.atm.flux_layers = sh_flux.to_host()
             return
@@ -453,16 +447,18 @@ class Spectrum:
             resident.reflected_1d_ck(ctx, nlevel, nwno, ngauss, ng, nt, pl, *geo, *self.tthg, self.gauss_wts, x,
                                      toon_coefficients=toon["toon_coefficients"], b_top=self.b_top, gweight=gw, tweight=tw,
                                      albedo=alb, lvl_fluxes=lv)
-        elif self.batch is not None and lv is None and fuse:
-            # spectrum_batch(): the launch is issued later, together with the other spectra's
-            self.batch.add_reflected(
-                (nlevel, nwno, ng, nt, self.tthg, toon["toon_coefficients"], self.b_top, tuple(self.gweight),
-                 tuple(self.tweight), tuple(k_ for k_ in resident.REFLECTED_PLANES if pl.get(k_) is not None)),
-                dict(ctx=ctx, planes=pl, rs=self.rs, ubar0=self.ubar0, ubar1=self.ubar1, cos_theta=self.cos_theta,
-                     F0PI=self.d_f0, xint=x, albedo=self.alb))
+            return
+        solve = solvebatch.Solve(
+            "reflected_1d", ctx,
+            solvebatch.Reflected1D(nlevel, nwno, ng, nt, self.tthg, toon["toon_coefficients"], self.b_top,
+                                   tuple(self.gweight), tuple(self.tweight),
+                                   tuple(k_ for k_ in resident.REFLECTED_PLANES if pl.get(k_) is not None)),
+            dict(planes=pl, rs=self.rs, ubar0=self.ubar0, ubar1=self.ubar1, cos_theta=self.cos_theta, F0PI=self.d_f0,
+                 xint=x, albedo=alb, lvl=lv))
+        if self.batch is not None and lv is None and fuse:
+            self.batch.add(solve)          # spectrum_batch(): the launch is issued later, together with the other spectra's
         else:
-            _reflected(ctx, nlevel, nwno, ng, nt, pl, *geo, *self.tthg, toon["toon_coefficients"], self.b_top, x, lv,
-                       self.gweight, self.tweight, alb)
+            solvebatch.launch(solve)
 
     def _reflected_3d(self):
         """justdoit.py:488-500: all facets, the Gauss loop inside."""
@@ -471,15 +467,18 @@ class Spectrum:
         if self.ngauss > 1:
             resident.reflected_3d_ck(ctx, nlevel, nwno, self.ngauss, ng, nt, p3, *geo, *self.tthg, self.gauss_wts, self.xint,
                                      gweight=self.gweight, tweight=self.tweight, albedo=self.alb)
-        elif self.batch is not None:                             # phase_curve(): one launch for a chunk of phases
-            present = tuple(k for k in resident.REFLECTED_PLANES if p3.get(k) is not None)
-            present += ("facet-major",) if p3.get("_fm") else ()
-            self.batch.add_reflected_3d((nlevel, nwno, ng, nt, self.tthg, present, tuple(self.gweight), tuple(self.tweight)),
-                                        dict(ctx=ctx, planes=p3, rs=self.rs, ubar0=self.ubar0, ubar1=self.ubar1,
-                                             cos_theta=self.cos_theta, F0PI=self.d_f0, xint=self.xint, albedo=self.alb))
+            return
+        solve = solvebatch.Solve(
+            "reflected_3d", ctx,
+            solvebatch.Reflected3D(nlevel, nwno, ng, nt, self.tthg,
+                                   tuple(k for k in resident.REFLECTED_PLANES if p3.get(k) is not None),
+                                   bool(p3.get("_fm")), tuple(self.gweight), tuple(self.tweight)),
+            dict(planes=p3, rs=self.rs, ubar0=self.ubar0, ubar1=self.ubar1, cos_theta=self.cos_theta, F0PI=self.d_f0,
+                 xint=self.xint, albedo=self.alb))
+        if self.batch is not None:                               # phase_curve(): one launch for a chunk of phases
+            self.batch.add(solve)
         else:
-            (resident.reflected_3d if not p3.get("_fm") else _reflected_3d_fm)(
-                ctx, nlevel, nwno, ng, nt, p3, *geo, *self.tthg, self.xint, self.gweight, self.tweight, self.alb)
+            solvebatch.launch(solve)
 
     def _enqueue_reflected(self):
         ctx, nwno, ng, nt, atm = self.ctx, self.nwno, self.ng, self.nt, self.atm
@@ -517,30 +516,38 @@ class Spectrum:
         tl, pv = atm.level["temperature"], atm.level["pressure"]
         if self.is_sh:                                           # justdoit.py:364-370
             stream, de = self.common["stream"], self.common["delta_eddington"]
+            # ff = 0 if np.array_equal(cosb, cosb_og) else cosb_og**stream (fluxes.py:3072-3075).  Without delta-Eddington
+            # scaling the two planes are the same array; with it they are equal only where cosb_og**stream vanishes against
+            # cosb_og, and there `cosb_og**stream` IS the reference's 0 (exactly for a cloud-free atmosphere, to < 1e-21 in
+            # the weights otherwise): the kernel forms it per element, and nothing is copied back to decide (a 72 MB read
+            # of f_deltaM per call used to sit here: 9.5 of the 11.7 ms of an SH4 spectrum at 1e5 wavelengths).
+            differs = 1 if de else 0
             if ngauss > 1:
-                # ff = 0 if np.array_equal(cosb, cosb_og) else cosb_og**stream (fluxes.py:3072-3075): see _thermal_sh
                 resident.thermal_SH_ck(tctx, nlevel, self.d_wno, nwno, ngauss, ng, nt, tl, pl["dtau"], pl["w0"], pl["cosb_og"],
-                                       pv, self.ubar1, self.rs, stream, atm.hard_surface, de, self.gauss_wts, fx,
+                                       pv, self.ubar1, self.rs, stream, atm.hard_surface, differs, self.gauss_wts, fx,
                                        tau=pl.get("tau"), gweight=self.gweight, tweight=self.tweight, flux_disk=self.disk)
             else:
-                _thermal_sh(tctx, nlevel, self.d_wno, nwno, ng, nt, tl, pl, pv, self.ubar1, self.rs, stream,
-                            atm.hard_surface, de, fx, self.gweight, self.tweight, self.disk)
+                resident.thermal_SH(tctx, nlevel, self.d_wno, nwno, ng, nt, tl, pl["dtau"], pl["w0"], pl["cosb_og"], pv,
+                                    self.ubar1, self.rs, stream, atm.hard_surface, differs, fx, tau=pl.get("tau"),
+                                    gweight=self.gweight, tweight=self.tweight, flux_disk=self.disk)
             return
-        kw = dict(gweight=self.gweight, tweight=self.tweight, flux_disk=self.disk) if fuse else {}
-        kw.update(self.tkw)
         if ngauss > 1:
+            kw = dict(gweight=self.gweight, tweight=self.tweight, flux_disk=self.disk) if fuse else {}
             resident.thermal_1d_ck(tctx, nlevel, self.d_wno, nwno, ngauss, ng, nt, tl, pl["dtau_og"], pl["w0_no_raman"],
                                    pl["cosb_og"], pv, self.ubar1, self.rs, atm.hard_surface, self.gauss_wts, fx,
-                                   lvl_fluxes=lv, **kw)
-        elif self.batch is not None and lv is None and fuse and not self.tkw:
-            self.batch.add_thermal(
-                (nlevel, nwno, ng, nt, int(atm.hard_surface), self.d_wno.addr, tuple(self.gweight), tuple(self.tweight)),
-                dict(ctx=tctx, wno=self.d_wno, tlevel=np.array(tl, dtype=float), plevel=np.array(pv, dtype=float),
-                     dtau=pl["dtau_og"], w0=pl["w0_no_raman"], cosb=pl["cosb_og"], ubar1=self.ubar1, rs=self.rs, flux=fx,
-                     disk=self.disk))
+                                   lvl_fluxes=lv, **kw, **self.tkw)
+            return
+        solve = solvebatch.Solve(
+            "thermal_1d", tctx,
+            solvebatch.Thermal1D(nlevel, nwno, ng, nt, int(atm.hard_surface), self.d_wno.addr, tuple(self.gweight),
+                                 tuple(self.tweight)),
+            dict(wno=self.d_wno, tlevel=np.array(tl, dtype=float), plevel=np.array(pv, dtype=float), dtau=pl["dtau_og"],
+                 w0=pl["w0_no_raman"], cosb=pl["cosb_og"], ubar1=self.ubar1, rs=self.rs, flux=fx,
+                 disk=self.disk if fuse else None, lvl=lv, options=self.tkw))
+        if self.batch is not None and lv is None and fuse and not self.tkw:
+            self.batch.add(solve)
         else:
-            resident.thermal_1d(tctx, nlevel, self.d_wno, nwno, ng, nt, tl, pl["dtau_og"], pl["w0_no_raman"], pl["cosb_og"],
-                                pv, self.ubar1, self.rs, atm.hard_surface, fx, lvl_fluxes=lv, **kw)
+            solvebatch.launch(solve)
 
     def _thermal_3d(self, flux):
         """justdoit.py:502-516: all facets, the Gauss loop inside."""
@@ -551,21 +558,18 @@ class Spectrum:
             resident.thermal_3d_ck(tctx, nlevel, self.d_wno, nwno, self.ngauss, ng, nt, self.tlev3, p3[th3[0]], p3[th3[1]],
                                    cosb, self.plev3, self.ubar1, self.rs, atm.hard_surface, self.gauss_wts, flux,
                                    gweight=self.gweight, tweight=self.tweight, flux_disk=self.disk)
-        elif self.batch is not None:
-            self.batch.add_thermal_3d((nlevel, nwno, ng, nt, int(atm.hard_surface), self.d_wno.addr,
-                                       (th3[2] is not None, bool(p3.get("_fm"))), tuple(self.gweight), tuple(self.tweight)),
-                                      dict(ctx=self.ctx, wno=self.d_wno, tlevel=np.array(self.tlev3, dtype=float),
-                                           plevel=np.array(self.plev3, dtype=float), dtau=p3[th3[0]], w0=p3[th3[1]],
-                                           cosb=cosb, ubar1=self.ubar1, rs=self.rs, flux=flux, disk=self.disk, keep=p3))
-        elif p3.get("_fm"):
-            resident.thermal_3d_fm_batch(tctx, nlevel, self.d_wno, nwno, ng, nt, np.asarray(self.tlev3, dtype=float)[None],
-                                         [p3[th3[0]]], [p3[th3[1]]], [cosb] if th3[2] else None,
-                                         np.asarray(self.plev3, dtype=float)[None],
-                                         np.asarray(self.ubar1, dtype=float).reshape(1, ng, nt), [self.rs], atm.hard_surface,
-                                         [flux], self.gweight, self.tweight, [self.disk])
+            return
+        solve = solvebatch.Solve(                                # in a batch tctx is ctx (plan())
+            "thermal_3d", tctx,
+            solvebatch.Thermal3D(nlevel, nwno, ng, nt, int(atm.hard_surface), self.d_wno.addr, bool(th3[2]),
+                                 bool(p3.get("_fm")), tuple(self.gweight), tuple(self.tweight)),
+            dict(wno=self.d_wno, tlevel=np.array(self.tlev3, dtype=float), plevel=np.array(self.plev3, dtype=float),
+                 dtau=p3[th3[0]], w0=p3[th3[1]], cosb=cosb, ubar1=self.ubar1, rs=self.rs, flux=flux, disk=self.disk),
+            keep=p3)
+        if self.batch is not None:
+            self.batch.add(solve)
         else:
-            resident.thermal_3d(tctx, nlevel, self.d_wno, nwno, ng, nt, self.tlev3, p3[th3[0]], p3[th3[1]], cosb, self.plev3,
-                                self.ubar1, self.rs, atm.hard_surface, flux, self.gweight, self.tweight, self.disk)
+            solvebatch.launch(solve)
 
     def _enqueue_thermal(self):
         tctx, nwno, ng, nt, atm, opa = self.tctx, self.nwno, self.ng, self.nt, self.atm, self.opa
@@ -883,58 +887,3 @@ def _postprocess(raw, wno, stellar, sa, radius_star, planet_radius, opa=None):
         _post_thermal(out, raw, wno, stellar, radius_star, planet_radius, opa)
     return _post_final(out, raw)
 
-
-def _reflected(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta, F0PI, single_phase,
-               multi_phase, frac_a, frac_b, frac_c, constant_back, constant_forward,
-               toon_coefficients, b_top, xint, lvl, gweight, tweight, albedo):
-    from ._lib import check, f64, load, ptr
-    u0, u1 = f64(ubar0, (ng, nt)), f64(ubar1, (ng, nt))
-    gw, tw = f64(gweight), f64(tweight)
-    check(load().picaso_get_reflected_1d_dev(
-        ctx, nlevel, nwno, nwno, ng, nt,
-        *[ptr(planes[k].addr) if planes.get(k) is not None else None for k in resident.REFLECTED_PLANES],
-        ptr(rs.addr), ptr(u0), ptr(u1),
-        cos_theta, ptr(F0PI.addr), single_phase, multi_phase, frac_a, frac_b,
-        frac_c, constant_back, constant_forward, 1, 1 if lvl else 0,
-        toon_coefficients, b_top, ptr(xint.addr),
-        *[ptr(l.addr) if lvl else None for l in (lvl or [None] * 4)], ptr(gw), ptr(tw),
-        ptr(albedo.addr) if albedo is not None else None), ctx)
-
-
-def _reflected_sh(ctx, nlevel, nwno, ng, nt, planes, rs, ubar0, ubar1, cos_theta, F0PI, sh, frac_a,
-                  frac_b, frac_c, constant_back, constant_forward, stream, b_top, xint, gweight,
-                  tweight, albedo, flux=None, cloud_free_above=0):
-    from ._lib import check, f64, load, ptr
-    u0, u1 = f64(ubar0, (ng, nt)), f64(ubar1, (ng, nt))
-    gw, tw = f64(gweight), f64(tweight)
-    check(load().picaso_get_reflected_SH_top_dev(
-        ctx, nlevel, nwno, nwno, ng, nt,
-        *[ptr(planes[k].addr) if planes.get(k) is not None else None for k in resident.SH_PLANES], ptr(rs.addr), ptr(u0),
-        ptr(u1), cos_theta,
-        ptr(F0PI.addr), sh["w_single_form"], sh["w_multi_form"], sh["psingle_form"],
-        sh["w_single_rayleigh"], sh["w_multi_rayleigh"], sh["psingle_rayleigh"],
-        frac_a, frac_b, frac_c, constant_back, constant_forward, stream,
-        b_top, 1 if flux is not None else 0, sh["single_form"], 1, int(cloud_free_above),
-        ptr(xint.addr),
-        ptr(flux.addr) if flux is not None else None, ptr(gw), ptr(tw),
-        ptr(albedo.addr)), ctx)
-
-
-def _thermal_sh(ctx, nlevel, d_wno, nwno, ng, nt, tlevel, planes, plevel, ubar1, rs, stream,
-                hard_surface, delta_eddington, flux, gweight, tweight, disk):
-    from ._lib import check, f64, load, ptr
-    u1 = f64(ubar1, (ng, nt))
-    gw, tw = f64(gweight), f64(tweight)
-    tl, pl = f64(tlevel), f64(plevel)
-    # ff = 0 if np.array_equal(cosb, cosb_og) else cosb_og**stream (fluxes.py:3072-3075).  Without delta-Eddington
-    # scaling the two planes are the same array; with it they are equal only where cosb_og**stream vanishes against
-    # cosb_og, and there `cosb_og**stream` IS the reference's 0 (exactly for a cloud-free atmosphere, to < 1e-21 in the
-    # weights otherwise): the kernel forms it per element, and nothing is copied back to decide (a 72 MB read of
-    # f_deltaM per call used to sit here: 9.5 of the 11.7 ms of an SH4 spectrum at 1e5 wavelengths).
-    differs = 1 if delta_eddington else 0
-    check(load().picaso_get_thermal_SH_dev(
-        ctx, nlevel, ptr(d_wno.addr), nwno, nwno, ng, nt, ptr(tl),
-        ptr(planes["dtau"].addr), ptr(planes["tau"].addr) if planes.get("tau") is not None else None,   # tau: never read
-        ptr(planes["w0"].addr),
-        ptr(planes["cosb_og"].addr), ptr(pl), ptr(u1), ptr(rs.addr), stream, int(hard_surface),
-        differs, 0, ptr(flux.addr), ptr(gw), ptr(tw), ptr(disk.addr)), ctx)

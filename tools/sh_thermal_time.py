@@ -5,7 +5,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from picaso_amd import _lib, device, disco, resident
-from picaso_amd.spectrum import _thermal_sh
 from picaso_amd import synthetic as syn
 nwno = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
 nlayer, ng = 90, 5
@@ -17,8 +16,8 @@ sc["surf_reflect"] = np.zeros(nwno)
 d = resident.upload_scene(sc, ("dtau", "w0", "cosb_og", "wno", "surf_reflect"), ctx=ctx)
 f = device.DeviceArray((ng, 1, nwno), ctx); disk = device.DeviceArray((nwno,), ctx)
 def step():
-    _thermal_sh(ctx, nlayer + 1, d["wno"], nwno, ng, 1, sc["tlevel"], d, sc["plevel"], u1, d["surf_reflect"], 4, 0, True, f,
-                gw, tw, disk)
+    resident.thermal_SH(ctx, nlayer + 1, d["wno"], nwno, ng, 1, sc["tlevel"], d["dtau"], d["w0"], d["cosb_og"], sc["plevel"], u1,
+                        d["surf_reflect"], 4, 0, True, f, gweight=gw, tweight=tw, flux_disk=disk)
 t0 = time.perf_counter()
 while time.perf_counter() - t0 < 0.4:
     for _ in range(10): step()
