@@ -92,6 +92,32 @@ enum { S_T = 0, S_XU, S_EO, S_KAPPA, S_ZETA, S_D1, S_D2 };   // late-use variabl
 #ifndef PZ_REFL_NOCLD_BODY
 #define PZ_REFL_NOCLD_BODY 1
 #endif
+// Work the zero-phase default-options kernels that form the level sums themselves (FAST, ZP, DRV 2 / 3 / 4) do not need;
+// each switch removes operations whose result is already held, none changes a bit (=0: the code as it was):
+// PZ_REFL_MERGE_XT: S_T (the running exp(-tau/u1)) and S_XU (exp(-tau/u0)) are one number there -- u0 == u1, both start at
+//   1.0 (fexp2 of 0 * nl1 = -0: rint -0, f = +0, fma(0, p, 1) = 1, ldexp(1, 0)) and every layer multiplies both by et --
+//   so S_XU alone is carried: five multiplies and ten VGPRs per layer in every copy of the body.
+// PZ_REFL_TOPRUN: while no layer above was delta-scaled S_EO is that number too (eo starts at fexp2_cold(-0) = 1.0 and
+//   e0o == e0 in a layer with dtau_og == dtau).  The run of sealed cloud-free layers from the top (all of a DRV = 2
+//   column) is swept by a loop of its own that reads eo from S_XU, keeps no S_EO, loads two planes per layer without
+//   looking at the mask and waits for them by count; S_EO is set from S_XU once where the run ends.
+// PZ_REFL_CLEAR_ENDS: the first and the last layer take straight-line copies of the cloud-free body when they are such
+//   layers (the general body's operations with its flags true, as for the interior copies).  Bit 0: the first, bit 1: the last.
+#ifndef PZ_REFL_MERGE_XT
+#define PZ_REFL_MERGE_XT 1
+#endif
+#ifndef PZ_REFL_TOPRUN
+#define PZ_REFL_TOPRUN 1
+#endif
+#ifndef PZ_REFL_CLEAR_ENDS
+#define PZ_REFL_CLEAR_ENDS 3
+#endif
+// ... and which of them the DRV = 4 kernels take: a third and fourth copy of the last layer beside the general ones gave
+// them a private segment (28 bytes of spills at 254 VGPRs, 44 in the batched form), so only the first layer there
+#ifndef PZ_REFL_CLEAR_ENDS_LAYERS
+#define PZ_REFL_CLEAR_ENDS_LAYERS 1
+#endif
+enum { ZF_XT = 1, ZF_EOX = 2 };    // reflected_layer's ZF: S_T is S_XU / eo is S_XU too
 // One reciprocal for all angles of a layer (Montgomery batch inversion) instead of one per angle:
 // -1.3 % time at five angles, but an angle's result then depends (in its last bits) on which angles
 // share its lane, i.e. on the angle chunking and on whether a small wavelength shard takes the
@@ -154,7 +180,7 @@ struct LayerIn {
 // SDT (with AF): 1 = same_dt holds as well (the cloud-free copy), 2 = it does not (the usual cloud layer: delta-
 // scaled, so dtau_og != dtau and the two extra exponentials are always formed) -- both straight-line.
 template <int NA, bool IS3D, bool ZP, bool FIRST, bool LAST, bool LDS, bool FAST = false, bool NC = false,
-          bool AF = false, int SDT = 1>
+          bool AF = false, int SDT = 1, int ZF = 0>
 __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const LayerIn &L,
                                                 ReflState<NA, LDS> &S,
                                                 const ReflectedArgs::Angle (&g)[NA],
@@ -167,6 +193,9 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     // of fused operations and disagreed in the last bits (5e-12 relative between the one-angle and the
     // five-angle kernel): a column's result depended on how the launch was shaped.  Now it does not.
 #pragma clang fp contract(off)
+    constexpr bool XT = (ZF & ZF_XT) != 0, EOX = (ZF & ZF_EOX) != 0;
+    static_assert(!ZF || (FAST && ZP), "ZF: the zero-phase default-options kernels only");
+    static_assert(!EOX || (NC && AF && SDT == 1), "ZF_EOX: the cloud-free copy only");
     const int tc = FAST ? 0 : tc_;
     const int single_phase = FAST ? 3 : a.single_phase;
     const int multi_phase = FAST ? 0 : a.multi_phase;
@@ -280,8 +309,8 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
         const double am2 = A0 + hz, ap2 = A0 - hz;
         const double et = fexp2(dt * nl1_k, K);              // exp(-dtau/u1)
         const double e0 = ZP ? et : fexp2(dt * nl0_k, K);    // exp(-dtau/u0)
-        const double xu = S.get(S_XU, k), Tk = S.get(S_T, k);
-        const double xd = (AF || L.cum_tau) ? xu * e0 : fexp2_cold(L.tau_n * nl0_k, K);
+        const double xu = S.get(S_XU, k), Tk = XT ? xu : S.get(S_T, k);
+        const double xd = (AF || XT || L.cum_tau) ? xu * e0 : fexp2_cold(L.tau_n * nl0_k, K);
         const double fw = Fw0h * rden;
         const double fx = fw * xu;
         const double cmu = am2 * fx, cpu = ap2 * fx;       // c-/c+ at the top of the layer
@@ -315,7 +344,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
         }
         // exp(-tau_og[i]/u0): the running product of the layers above when tau_og really is the
         // running sum of dtau_og, else formed directly
-        const double eo = (!FIRST && (AF || L.eo_ok)) ? S.get(S_EO, k) : fexp2_cold(L.tauo * nl0_k, K);
+        const double eo = EOX ? xu : (!FIRST && (AF || L.eo_ok)) ? S.get(S_EO, k) : fexp2_cold(L.tauo * nl0_k, K);
         // 1 - exp(-dtau (1/u0 + 1/u1)) and the same for dtau_og (fluxes.py:1395-1406) from the two
         // single-angle exponentials; a layer that is not delta-scaled (dtau_og == dtau) shares them
         const double t2 = fma(-e0, et, 1.0);
@@ -325,7 +354,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
             e0o = ZP ? e1o : fexp2_cold(L.dto * nl0_k, K);
             t1 = fma(-e0o, e1o, 1.0);
         }
-        if (!LAST) S.set(S_EO, k, eo * e0o);
+        if (!LAST && !EOX) S.set(S_EO, k, eo * e0o);
         // S0 = (ssa eo t1 + Aq t2) u0/(u0+u1) with Aq = 2 w2pi fx Aqq; wq2 = 2 u0/(u0+u1) (1 if ZP)
         double S0;
         if (PZ_REFL_DIET && ZP && (NC || L.nocld) && (AF ? (SDT != 2) : L.same_dt)) {
@@ -336,7 +365,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
             S0 = fma((w2pi * wq2_k) * fx, Aqq * t2, s1);
         }
         double kap = fma(Tk, S0, S.get(S_KAPPA, k));
-        const double Tn = Tk * et;
+        const double Tn = XT ? xd : Tk * et;               // XT: xd = xu e0 is Tk et
         if (LAST) {                                        // xint[n] = flux_zero/pi (fluxes.py:1266-1270)
             vp = fma(Tn * EP, 1.0 / PI, vp);
             vn = fma((Tn * gam) * EM, 1.0 / PI, vn);
@@ -357,7 +386,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
             S.set(S_ZETA, k, fma(-vn, rho_n, fma(zeta, sfac, vp)));
         }
         S.set(S_KAPPA, k, kap);
-        S.set(S_T, k, Tn);
+        if (!XT) S.set(S_T, k, Tn);
         S.set(S_D1, k, fma(gEM, delta_n, cpd));
         S.set(S_D2, k, fma(EM, delta_n, cmd));
     }
@@ -473,8 +502,19 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     // to the cloud-free copy of the body); every other layer is DRV = 3 unchanged.  The values put in ARE the stored ones
     // and the votes would have passed, so the same copy of the body runs on the same numbers.
     constexpr bool CLEAR = (DRV == 2), LAYERS = (DRV == 4), LEVELS = (DRV == 3) || LAYERS;
+    // the kernels PZ_REFL_MERGE_XT and its companions apply to (see the macros): cum_tau holds by construction, u0 == u1
+    constexpr bool ZDRV = FAST && ZP && !IS3D && (CLEAR || LEVELS);
+    constexpr int ZX = (ZDRV && PZ_REFL_MERGE_XT) ? ZF_XT : 0;
+    constexpr bool TOPRUN = ZDRV && (CLEAR || LAYERS) && PZ_REFL_TOPRUN;
+    constexpr int CLEAR_ENDS = !ZDRV ? 0 : CLEAR ? PZ_REFL_CLEAR_ENDS : LAYERS ? (PZ_REFL_CLEAR_ENDS & PZ_REFL_CLEAR_ENDS_LAYERS) : 0;
+    // the mask, read once
+    unsigned long long m0 = 0, m1 = 0;
+    if constexpr (LAYERS) {
+        m0 = a.lmask[0];
+        m1 = a.lmask[1];
+    }
     auto layer_clear = [&](int i) -> bool {          // wave-uniform: the mask is a kernel argument / a table entry
-        if constexpr (LAYERS) return (((i & 64) ? a.lmask[1] : a.lmask[0]) >> (i & 63)) & 1ull;
+        if constexpr (LAYERS) return (((i & 64) ? m1 : m0) >> (i & 63)) & 1ull;
         return false;
     };
     const bool derive_tau = CLEAR || LEVELS || (DRV && a.tau == nullptr);
@@ -492,7 +532,8 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         S.set(S_D1, k, 0.0);
         S.set(S_D2, k, 0.0);
         S.set(S_EO, k, 0.0);
-        S.set(S_XU, k, fexp2(mul_unfused(tau_i, ZP ? g[k].nl1 : g[k].nl0), K));
+        // ZX: tau_i is +0.0, the product -0.0 and fexp2 of it exactly 1.0 (see PZ_REFL_MERGE_XT)
+        S.set(S_XU, k, ZX ? 1.0 : fexp2(mul_unfused(tau_i, ZP ? g[k].nl1 : g[k].nl0), K));
     }
 
     // Software prefetch with two register sets used alternately (loop unrolled by two): the eleven
@@ -635,13 +676,26 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     do {                                                                                                 \
         const bool lclear_ = layer_clear(I_);                                                            \
         prep(L_, lclear_);                                                                               \
-        if (PZ_REFL_NOCLD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf)                  \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, true, true>(a, L_, S, g, K, F, clip, tc, b_top); \
+        /* a first / last layer known to be cloud-free (the seal's mask, DRV = 2): the straight-line copy, if PZ_REFL_CLEAR_ENDS says so */ \
+        constexpr bool kcopy_ = PZ_REFL_NOCLD_BODY && ZDRV && ((FIRST_) || (LAST_)) &&                   \
+                                (!(FIRST_) || (CLEAR_ENDS & 1)) && (!(LAST_) || (CLEAR_ENDS & 2));       \
+        constexpr int kzf_ = kcopy_ ? (ZX | ((FIRST_) ? ZF_EOX : 0)) : 0;                                \
+        if (kcopy_ && (CLEAR || lclear_))                                                                \
+            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, kcopy_, kcopy_, 1, kzf_>(a, L_, S, g, K, F, clip, tc, b_top); \
+        else if (PZ_REFL_NOCLD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf)             \
+            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, true, true, 1, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
         else if (PZ_REFL_CLOUD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.af_cloud)                      \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, false, true, 2>(a, L_, S, g, K, F, clip, tc, b_top); \
+            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, false, true, 2, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
         else                                                                                             \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST>(a, L_, S, g, K, F, clip, tc, b_top); \
+            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, false, false, 1, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
         if constexpr (CLEAR) __builtin_amdgcn_sched_barrier(0);   /* straight-line code: keep the layers apart */ \
+    } while (0)
+    // a layer of the clear run from the top: known cloud-free, nothing above it delta-scaled
+#define PZ_RUN_LAYER(L_)                                                                                 \
+    do {                                                                                                 \
+        prep(L_, true);                                                                                  \
+        reflected_layer<NA, IS3D, ZP, false, false, LDS, FAST, TOPRUN, TOPRUN, 1, TOPRUN ? (ZX | ZF_EOX) : 0>(a, L_, S, g, K, F, clip, tc, b_top); \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
     } while (0)
 
     // Two register sets used alternately (no copy) for one or two angles per lane -- the HBM-bound 3-D facet
@@ -664,6 +718,35 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         load(B, 1);
         PZ_LAYER(true, false, A, 0);
         int i = 1;                               // B holds layer i
+        if constexpr (TOPRUN || CLEAR_ENDS) {
+            // r: the number of cloud-free layers from the top (scalar bit operations on the mask; DRV = 2: all of them)
+            int r = n;
+            if constexpr (LAYERS) {
+                r = (~m0) ? __builtin_ctzll(~m0) : 64 + ((~m1) ? __builtin_ctzll(~m1) : 64);
+                r = r < n ? r : n;
+            }
+            if (r >= 1) {
+                if constexpr (TOPRUN) {
+                    // layers i, i+1 and the two prefetched ones (i+1, i+2) all belong to the run: two loads each, so the
+                    // compiler's own counted vmcnt waits do, and no mask is looked at
+                    auto load_clear = [&](LayerIn &L, int l) {
+                        const unsigned o = voff0 + (unsigned)l * pitch8;
+                        L.dt = ld(a.dtau, o);
+                        L.w0 = ld(a.w0, o);
+                    };
+                    for (; i + 2 < r; i += 2) {
+                        load_clear(A, i + 1);
+                        PZ_RUN_LAYER(B);
+                        load_clear(B, i + 2);
+                        PZ_RUN_LAYER(A);
+                    }
+                }
+                // the run ends here (the layers left of it, at most two, take the masked loop): from now on S_EO is kept.
+                // Layer 0 was cloud-free, so whichever copy of the body ran it, S_EO is S_XU at this point, bit for bit.
+#pragma unroll
+                for (int k = 0; k < NA; ++k) S.set(S_EO, k, S.get(S_XU, k));
+            }
+        }
         for (; i + 2 <= n - 1; i += 2) {         // layers i and i+1 are interior, layer i+2 exists
             load(A, i + 1, true);
             PZ_LAYER(false, false, B, i);
@@ -689,6 +772,7 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         PZ_LAYER(false, true, A, n - 1);
     }
 #undef PZ_LAYER
+#undef PZ_RUN_LAYER
 
     // ---- surface row (fluxes.py:178-183) and output ----
     // EP(1 - rs G) pos + EM(G - rs) neg = b_surface - c+dn + rs c-dn with neg = delta - rho pos,
