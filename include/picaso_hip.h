@@ -1230,6 +1230,26 @@ int picaso_chem_interp_dev(picaso_ctx *ctx, int nrow, int nspecies, const double
                            long npoints, const double *temperature, const double *p_log, int nsel, const int *sel,
                            int log10_out, double *out /* (nsel, npoints) */);
 
+/* ---- cloud tables of every phase of a phase curve from one GCM cloud map (reference justdoit.py:3875-4090 clouds_4d) ----
+ * replaces, per phase, the host's bilinear regrid of the map onto the facets, the re-stack into facet-major rows and their
+ * upload.  opd, w0, g0: device, the map's three variables, each (nlon, nlat, npres, nin) with the wavenumber index fastest, in
+ * the caller's own order along every axis.  lon_idx: device, (nphase, ng, 2) = the two source longitude columns (j0, j1) of
+ * every Gauss angle of every phase; lon_t: device, (nphase, ng) = the weight of j1.  lat_idx (nphase, nt, 2), lat_u (nphase,
+ * nt): the same along latitude for every Chebyshev angle.  layer_src: device, (nlayer) = the source pressure index of every
+ * output layer, top to bottom; wno_src: device, (nin) = the source index of every output wavenumber, wavenumber increasing.
+ * The caller does every search (picaso_amd/gcm.py: axis_indices, the index form of spectrum._interp_axis).  Per element
+ *   a = m[j0, i0] * (1.0 - t) + m[j1, i0] * t;   b = m[j0, i1] * (1.0 - t) + m[j1, i1] * t;   out = a * (1.0 - u) + b * u
+ * (1.0 - t) and (1.0 - u) one rounded subtraction each, every product and sum rounded in this order, nothing contracted: the
+ * bits of numpy's longitude-then-latitude interpolation.  out: device, (nphase, 3, ng * nt * nlayer, nin): per phase the opd
+ * rows, then w0, then g0, facet-major with facet = g * nt + t, the wavenumber index fastest -- what the fused opacity launch
+ * reads through cld_tab_fp.  One launch for all phases.  The caller checks every index against its axis; the kernel clamps
+ * them, so a broken table reads no memory outside the map.  nphase == 0: nothing is launched; nphase <= 65535.
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_gcm_facet_tables_dev(picaso_ctx *ctx, int nlon, int nlat, int npres, int nin, const double *opd, const double *w0,
+                                const double *g0, int nphase, int ng, int nt, int nlayer, const int *lon_idx,
+                                const double *lon_t, const int *lat_idx, const double *lat_u, const int *layer_src,
+                                const int *wno_src, double *out /* (nphase, 3, ng * nt * nlayer, nin) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ import warnings
 import numpy as np
 
 from . import _lib, disco, optics
+from . import gcm as _gcm
 from . import convolve as _convolve
 from . import regrid as _regrid
 from . import options as _options
@@ -37,7 +38,7 @@ from .contribution import thermal_contribution, transmission_contribution       
 from .attenuation import cloud_optics_1d, heatmap_taus, photon_attenuation, taumap   # noqa: F401  (jdi.photon_attenuation)
 from .opacity_factory import compute_ck, compute_ck_molecular                        # noqa: F401  (jdi.compute_ck)
 from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
-                       _fetch, _interp_axis, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
+                       _fetch, _interp_axis, _lon_period, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
                        _resident_vector, _setup_atmosphere, _trapz_resident)
 
 # option tables (reference justdoit.py:5512-5534, 5647-5658)
@@ -285,12 +286,9 @@ def _regrid_lonlat(coords, variables, lon_new, lat_new):
     geometry."""
     out = {}
     lon = np.asarray(coords["lon"], dtype=float)
-    # a longitude axis that goes around the planet is periodic: facets beyond its first / last column are interpolated
-    # across the +-180 seam; a regional map (less than a full circle with its own spacing) keeps its end values
-    ulon = np.unique(lon)
-    wraps = ulon.size > 2 and (ulon[-1] - ulon[0]) + 1.5 * np.max(np.diff(ulon)) >= 360.0
+    period = _lon_period(lon)        # a longitude axis that goes around the planet is periodic, a regional map is not
     for k, v in variables.items():
-        out[k] = _interp_axis(lat_new, coords["lat"], _interp_axis(lon_new, lon, v, 0, period=360.0 if wraps else None), 1)
+        out[k] = _interp_axis(lat_new, coords["lat"], _interp_axis(lon_new, lon, v, 0, period=period), 1)
     return out
 
 
@@ -474,7 +472,10 @@ class inputs:
                                    radius_unit="nostar", flux="nostar", wno="nostar", relative_flux=None)
 
     def clouds_reset(self):
-        """Cloud tables back to zeros (reference justdoit.py:4115-4124)."""
+        """Cloud tables back to zeros (reference justdoit.py:4115-4124); the per-phase tables of ``clouds_4d`` are dropped,
+        with the phase they last handed to ``phase_curve``."""
+        if self.inputs["clouds"].pop("profile_4d", None) is not None:
+            self.inputs["clouds"].pop("profile_3d", None)
         prof = self.inputs["clouds"]["profile"]
         if prof is not None:
             self.inputs["clouds"]["profile"] = {k: (np.zeros_like(np.asarray(v, dtype=float)) if k in ("g0", "w0", "opd") else v)
@@ -922,7 +923,9 @@ class inputs:
         GPU).  ``devices=N`` (or a list of device indices) deals the phases out to N GPUs round-robin -- the
         reference's fan-out of whole phases, with a replica of the opacity tables resident on every device
         (``optics.shard_opacity`` over the full grid, uploaded once) and every phase enqueued before the first
-        result is read.  Returns ``{phase: spectrum output}``.  ``regrid`` and ``convolve`` are not supported here."""
+        result is read.  Clouds: ``clouds_by_phase`` (one ``clouds_3d``-style dictionary per phase), else the tables
+        ``clouds_4d`` left in ``inputs['clouds']['profile_4d']``, else whatever ``profile_3d`` holds for all phases.
+        Returns ``{phase: spectrum output}``.  ``regrid`` and ``convolve`` are not supported here."""
         if convolve is not None:
             raise NotImplementedError("phase_curve(convolve=...) is not supported: convolve each phase's spectrum with "
                                       "conv_non_uniform_R, or call spectrum(convolve=...) per phase")
@@ -937,6 +940,12 @@ class inputs:
         if profs is None or len(profs) != len(phases):
             raise Exception("atmosphere_4d() needs one profile per phase (%d)" % len(phases))
         calculation = all_geom["calculation"]
+        if clouds_by_phase is None:            # the tables of clouds_4d, one per phase (an explicit clouds_by_phase wins)
+            clouds_by_phase = self.inputs["clouds"].get("profile_4d")
+            if clouds_by_phase is not None and len(clouds_by_phase) != len(phases):
+                raise Exception("clouds_4d() made cloud tables for %d phases, but there are %d now: the number of phases has "
+                                "changed since -- run clouds_4d() again (or clouds_reset())"
+                                % (len(clouds_by_phase), len(phases)))
         replicas = [opacityclass]
         if devices is not None:
             devs = _device_list(devices)
@@ -1028,6 +1037,69 @@ class inputs:
         out["wavenumber"] = wno_c[worder]
         out["pressure"] = coords["pressure"][order]
         self.inputs["clouds"]["profile_3d"] = out
+
+    @_lib.serialized
+    def clouds_4d(self, ds=None, plot=True, iz_plot=0, iw_plot=0, verbose=True, calculation='reflected'):
+        """The cloud tables of every phase of ``phase_curve_geometry`` from ONE GCM cloud map (reference
+        justdoit.py:3875-4090): ``ds`` = ``opd`` / ``w0`` / ``g0`` on ``(lon, lat, pressure, wno)`` (layer pressures;
+        xarray-like or dictionary, see ``_dataset_like``).  Run after ``atmosphere_4d(gcm)``: per phase the map is rotated
+        by that call's ``phase + shift`` degrees of longitude and interpolated bilinearly onto the same facets, so cloud
+        and profile stay co-located.  The map goes to HBM once (``gcm.GcmCloudMap``, kept by content: the same arrays
+        again upload nothing) and one launch writes the tables of all phases where the opacity stage of ``phase_curve``
+        reads them (``gcm.facet_tables``); no interpolation in pressure -- the map holds ``nlevel - 1`` layer pressures,
+        sorted ascending here, as ``clouds_3d`` does.  Result: ``inputs['clouds']['profile_4d']``, one
+        ``gcm.FacetCloudTables`` per phase, taken by ``phase_curve`` unless it is given ``clouds_by_phase``; and
+        ``inputs['clouds']['wavenumber']``.
+
+        ``calculation`` must name ``reflected`` or ``thermal`` as in the reference; the facets are those of
+        ``phase_curve_geometry`` either way.  ``plot`` / ``iz_plot`` / ``iw_plot`` are accepted and ignored (no plotting
+        here).  The reference additionally re-centres the illuminated crescent of a reflected-light curve with corrections
+        written for its 6- and 10-angle grids (justdoit.py:3959-4008); as in ``atmosphere_4d`` those are not reproduced:
+        hand per-phase tables to ``phase_curve(clouds_by_phase=...)`` for such a curve."""
+        phases = self.inputs["phase_angle"]
+        if ds is None:
+            raise Exception("Need to submit an xarray.DataArray because there is no input attached to "
+                            "self.inputs['clouds']['profile']")
+        if not (isinstance(ds, dict) or hasattr(ds, "coords")):
+            raise Exception("PICASO has moved to only accept xarray input. Please see GCM 3D input tutorials to learn how "
+                            "to reformat your input. (picaso_amd takes an xarray-like object or a dictionary with "
+                            "lon / lat / pressure / wno entries.)")
+        if "shift" not in self.inputs:
+            raise Exception("Oops! It looks like cloud_4d is being run before atmosphere_4d. Please run atmosphere_4d first "
+                            "so that you can speficy a shift, relative to the phase. This shift will then be used in "
+                            "cloud_4d.")
+        for need in ("opd", "g0", "w0"):
+            if need not in ds:
+                raise Exception("Must include %s as data component" % need)
+        have = ds.coords if hasattr(ds, "coords") else ds
+        if "pressure" not in have:
+            raise Exception("Must include pressure in coords and units")
+        if "wno" not in have:
+            raise Exception("Must include 'wno' (wavenumber) in coords and units")
+        if "lat" not in have or "lon" not in have:
+            raise Exception('Must include "lat" and "lon" as coordinates. Please see GCM 3D input tutorials to learn how '
+                            'to reformat your input.')
+        if "reflected" not in calculation and "thermal" not in calculation:
+            raise Exception("Must include 'reflected' or 'thermal' in calculation")
+        all_geom = self.inputs["disco"]
+        if not isinstance(all_geom, dict) or "calculation" not in all_geom:
+            raise Exception("run phase_curve_geometry() first")
+        shift = np.asarray(self.inputs["shift"], dtype=float)
+        if len(shift) != len(phases):
+            raise Exception("shift has %d entries but there are %d phases: run atmosphere_4d() again" % (len(shift), len(phases)))
+        coords, variables = _dataset_like(ds, extra_coords=("wno",))
+        if verbose and str(coords["pressure_unit_in"]).lower() not in ("bar", "bars"):
+            print("verbose=True; Converting pressure grid from %s to required unit of bar." % coords["pressure_unit_in"])
+        if len(coords["pressure"]) != self.nlevel - 1:
+            raise Exception("clouds_4d: the cloud map holds %d pressures; the profiles of atmosphere_4d have %d levels, so it "
+                            "must hold %d layer pressures" % (len(coords["pressure"]), self.nlevel, self.nlevel - 1))
+        cmap = _gcm.GcmCloudMap.resident(coords, variables)
+        tables = _gcm.facet_tables(cmap, [all_geom[ph]["longitude"] * 180 / np.pi for ph in phases],
+                                   [all_geom[ph]["latitude"] * 180 / np.pi for ph in phases],
+                                   [(ph * 180 / np.pi, shift[i]) for i, ph in enumerate(phases)])
+        self.inputs["clouds"]["dims"] = "3d"
+        self.inputs["clouds"]["profile_4d"] = tables
+        self.inputs["clouds"]["wavenumber"] = cmap.wno_sorted
 
     def surface_reflect(self, albedo, wavenumber=None, old_wavenumber=None):
         """Surface reflectivity, scalar or per wavelength (reference justdoit.py:4092)."""

@@ -382,8 +382,11 @@ def prepare_3d(bundle, opa, subs, calculation, opt, slot=None, regrid=None):
     if cld3 is not None:
         if not isinstance(cld3, dict) or cld3.get("wavenumber") is None:
             return None             # cloud arrays on the opacity grid: the facet-fastest mixing launch (Spectrum)
-        # ONE digest of the tables per call (0.5 ms for 64 facets x 90 x 196 x 3), whatever the number of blocks
-        stamp3 = optics._table_fingerprint([cld3[k] for k in ("opd", "w0", "g0")], cld3["wavenumber"])
+        # ONE digest of the tables per call (0.5 ms for 64 facets x 90 x 196 x 3), whatever the number of blocks; tables made
+        # in HBM (gcm.FacetCloudTables) bring their stamp: there are no host arrays to digest
+        stamp3 = getattr(cld3, "stamp", None)
+        if stamp3 is None:
+            stamp3 = optics._table_fingerprint([cld3[k] for k in ("opd", "w0", "g0")], cld3["wavenumber"])
         first = optics._facet_major_cloud_tables(cld3, nlayer, nfac, subs[0][2].ctx, stamp=stamp3)
         if first is None:
             return None

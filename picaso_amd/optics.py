@@ -1181,7 +1181,14 @@ def _table_fingerprint(arrs, wavenumber):
 def _facet_major_cloud_tables(clouds_3d, nlayer, nfac, ctx, stamp=None):
     """Cloud tables on their own increasing wavenumber grid as resident ``(3, nfacets * nlayer, nin)`` rows in
     facet-major order (opd, w0, g0) with their grid, kept on the cloud dictionary while its arrays are the same
-    objects.  None when the tables are not of that kind."""
+    objects.  None when the tables are not of that kind.  Tables a regrid launch wrote in HBM (``gcm.FacetCloudTables``)
+    are handed on where they lie, with None for the host rows: nothing is stacked, digested or uploaded; on a device other
+    than theirs they are taken as the dictionary they also are."""
+    res = getattr(clouds_3d, "resident_tables", None)
+    if res is not None:
+        tabs = res(nlayer, nfac, ctx)
+        if tabs is not None:
+            return tabs
     in_wno = clouds_3d.get("wavenumber") if isinstance(clouds_3d, dict) else None
     if in_wno is None or np.size(in_wno) < 2:
         return None
@@ -1230,6 +1237,11 @@ def compute_opacity_facet_major(atm_f, opacityclass, numg, numt, stream=2, delta
             d_xp, d_tall, h_tall, nin = cloud_tables
             if f0 == 0 and f1 == nfac:           # one launch: the resident (3 ntot, nin) rows as they are
                 d_fp = d_tall
+            elif h_tall is None:                 # rows made on the device (gcm.FacetCloudTables): this chunk's, device to device
+                d_fp = keep = DeviceArray((3 * nl_c, nin), ctx)
+                for j in range(3):
+                    check(load().picaso_memcpy_d2d(ctx, d_fp.addr + j * nl_c * nin * 8,
+                                                   d_tall.addr + (j * nfac * nlayer + sl.start) * nin * 8, nl_c * nin * 8), ctx)
             else:                                # this chunk's opd / w0 / g0 rows, contiguous
                 d_fp = keep = DeviceArray.from_host(np.ascontiguousarray(h_tall[:, sl].reshape(3 * nl_c, nin)), ctx)
             cld_tab = (nin, ptr(d_xp.addr), ptr(d_fp.addr), ptr(_wno_device(opa, opa.wno).addr))

@@ -17,32 +17,53 @@ from .atmsetup import ATMSETUP, CloudTables
 from .device import DeviceArray
 
 
-def _interp_axis(x_new, x_old, arr, axis, period=None):
-    """Linear interpolation of ``arr`` along ``axis`` from the grid ``x_old`` to ``x_new`` (end values held outside the
-    grid).  ``x_old`` is sorted here if need be; repeated abscissae (a longitude axis holding both -180 and 180) keep
-    their first entry.  ``period``: the axis is periodic (longitude, 360): points beyond either end are interpolated
-    across the seam instead of being clamped to the end value."""
+def _axis_indices(x_new, x_old, period=None):
+    """The searches of ``_interp_axis`` without the values: ``(j0, j1, t)``, one entry per point of ``x_new``, such that the
+    interpolated value is ``arr[j0] * (1.0 - t) + arr[j1] * t`` with ``j0`` / ``j1`` indices into ``x_old`` AS GIVEN.
+    ``x_old`` is sorted here if need be; repeated abscissae (a longitude axis holding both -180 and 180) keep their
+    first entry.  ``period``: the axis is periodic (longitude, 360): points beyond either end are interpolated across
+    the seam (between the last and the first kept column) instead of being clamped to the end value.  An axis of one
+    point gives ``j0 = j1 = 0`` (its place in ``x_old``) and ``t = 0``, ``j0`` and ``j1`` being the same array."""
     x_old = np.asarray(x_old, dtype=float)
-    arr = np.asarray(arr)
+    src = np.arange(x_old.size)
     if np.any(np.diff(x_old) <= 0):
-        x_old, first = np.unique(x_old, return_index=True)          # sorted, duplicates dropped
-        arr = np.take(arr, first, axis=axis)
+        x_old, src = np.unique(x_old, return_index=True)            # sorted, duplicates dropped
     if period is not None and x_old.size > 1:
         if x_old[-1] - x_old[0] >= period:                          # both ends of the seam present: one of them is the other
             keep = x_old < x_old[0] + period
-            x_old, arr = x_old[keep], np.compress(keep, arr, axis=axis)
+            x_old, src = x_old[keep], src[keep]
         x_old = np.concatenate([[x_old[-1] - period], x_old, [x_old[0] + period]])
-        arr = np.concatenate([np.take(arr, [-1], axis=axis), arr, np.take(arr, [0], axis=axis)], axis=axis)
+        src = np.concatenate([src[-1:], src, src[:1]])
         x_new = x_old[1] + np.mod(np.asarray(x_new, dtype=float) - x_old[1], period)
     if x_old.size == 1:
-        return np.repeat(arr, len(x_new), axis=axis)
+        j = np.repeat(src, len(x_new))
+        return j, j, np.zeros(len(x_new))
     x = np.clip(np.asarray(x_new, dtype=float), x_old[0], x_old[-1])
     j = np.clip(np.searchsorted(x_old, x, side="right") - 1, 0, x_old.size - 2)
     t = (x - x_old[j]) / (x_old[j + 1] - x_old[j])
+    return src[j], src[j + 1], t
+
+
+def _lon_period(lon):
+    """360.0 for a longitude axis (degrees) that goes around the planet, else None: such an axis is periodic, facets
+    beyond its first / last column are interpolated across the +-180 seam; a regional map (less than a full circle with
+    its own spacing) keeps its end values."""
+    ulon = np.unique(np.asarray(lon, dtype=float))
+    wraps = ulon.size > 2 and (ulon[-1] - ulon[0]) + 1.5 * np.max(np.diff(ulon)) >= 360.0
+    return 360.0 if wraps else None
+
+
+def _interp_axis(x_new, x_old, arr, axis, period=None):
+    """Linear interpolation of ``arr`` along ``axis`` from the grid ``x_old`` to ``x_new`` (end values held outside the
+    grid): ``_axis_indices`` applied to the values."""
+    arr = np.asarray(arr)
+    j0, j1, t = _axis_indices(x_new, x_old, period)
+    if j0 is j1:                                                    # an axis of one point: its value, untouched
+        return np.take(arr, j0, axis=axis)
     shape = [1] * arr.ndim
     shape[axis] = -1
     t = t.reshape(shape)
-    return np.take(arr, j, axis=axis) * (1.0 - t) + np.take(arr, j + 1, axis=axis) * t
+    return np.take(arr, j0, axis=axis) * (1.0 - t) + np.take(arr, j1, axis=axis) * t
 
 
 def _resident_vector(opa, name, value, nwno):

@@ -77,7 +77,7 @@ def main(argv=None):
     opk = px.RetrieveCKs(wck, gwts, np.tile(pk, tk.size), np.repeat(tk, pk.size), np.full(tk.size, pk.size), lnk,
                          continuum=cont, cia_temps=cia_t, rayleigh_opa={m: 1e-27 * (wck / 1e4) ** 4 for m in ("H2", "He")},
                          gauss_pts=gpts, ctx=ctx)
-    NKIND = 14
+    NKIND = 15
     kinds = {}
 
     def one(i):
@@ -131,6 +131,27 @@ def main(argv=None):
                               for k in range(2)])
             pc.approx(raman="none")
             curve = pc.phase_curve(opk)
+            kinds[kind] = kinds.get(kind, 0) + 1
+            return all(np.all(np.isfinite(v["thermal"])) for v in curve.values())
+        if kind == 14:               # clouds_4d: a new GCM cloud map every call (resident by content: the old one goes), 2 phases
+            nlon, nlat = 8, 4
+            lon, lat = np.linspace(-180.0, 135.0, nlon), np.linspace(-67.5, 67.5, nlat)
+            day = 1.0 + 0.1 * np.cos(np.radians(lon) + rng.random())[:, None, None] * np.ones((1, nlat, 1))
+            gcm = {"lon": lon, "lat": lat, "pressure": plev, "temperature": day * prof["temperature"][None, None, :]}
+            for m in ("H2", "He", "H2O", "CH4", "CO", "NH3"):
+                gcm[m] = np.broadcast_to(prof[m], (nlon, nlat, nlevel)).copy()
+            shp = (nlon, nlat, nlevel - 1, 12)
+            opd = np.zeros(shp)
+            opd[:, :, 30:40] = rng.uniform(0.1, 0.5, (nlon, nlat, 1, 1))
+            pc = jdi.inputs()
+            pc.phase_curve_geometry("thermal", [0.4, 2.0], num_gangle=4, num_tangle=4)
+            pc.gravity(gravity=2500.0)
+            pc.atmosphere_4d(gcm, verbose=False)
+            pc.clouds_4d({"lon": lon, "lat": lat, "pressure": np.sqrt(plev[1:] * plev[:-1]), "wno": np.linspace(wno[0], wno[-1], 12),
+                          "opd": opd, "w0": np.where(opd > 0, 0.95, 0.0), "g0": np.where(opd > 0, 0.6, 0.0)},
+                         verbose=False, calculation="thermal")
+            pc.approx(raman="none")
+            curve = pc.phase_curve(opa)
             kinds[kind] = kinds.get(kind, 0) + 1
             return all(np.all(np.isfinite(v["thermal"])) for v in curve.values())
         if kind == 7:                # 3-D: 4 x 4 facets, per-facet temperatures, a cloud map on its own grid every other call
