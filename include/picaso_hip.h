@@ -1250,6 +1250,25 @@ int picaso_gcm_facet_tables_dev(picaso_ctx *ctx, int nlon, int nlat, int npres, 
                                 const double *lon_t, const int *lat_idx, const double *lat_u, const int *layer_src,
                                 const int *wno_src, double *out /* (nphase, 3, ng * nt * nlayer, nin) */);
 
+/* ---- cloud tables of a batch of parametrized grey clouds (reference parameterizations.py:200-253 cloud_brewster_grey /
+ * cloud_hard_grey, :753-792 cloud_averaging) ----
+ * replaces, per sample of a retrieval, the host build of the (3 * nlayer, nin) table, its digest and its upload.  S samples of
+ * K decks each, 1 <= K <= 4.  layers: device, (S, K, 3, nlayer) = per deck the layer vectors opd_l, w0_l, g0_l, formed on the
+ * host (Parameterize.deck_decay / slab_decay, the box test of inputs.clouds: their argmin, caps and comparisons stay there).
+ * params: device, (S, K, 2) = per deck alpha and reference_wave.  wavelength: device, (nin) = 1e4 / wavenumber with the
+ * wavenumber increasing, formed by the caller so that the device raises the numbers the reference raises.  Per element
+ *   opd_k = opd_l[k][l] * (wavelength[w] / reference_wave_k) ** (-alpha_k)
+ * an IEEE division, the library's pow (< 1 ulp; alpha == 0 gives exactly 1) and one rounded product.  average == 0 (K must be
+ * 1): opd_0, w0_l[0][l] and g0_l[0][l] as they are.  average == 1: cloud_averaging in deck order -- opd the left-to-right sum
+ * of opd_k from 0, w0 and g0 the left-to-right sums of opd_k * w0_k and opd_k * g0_k from 0, opd replaced by 1e-33 where the sum
+ * is 0, then the two IEEE quotients, nothing contracted: with every alpha = 0 the reference's bits.
+ * out: device, (S, 3, nlayer, nin): per sample the opd rows, then w0, then g0, the wavenumber index fastest -- the stack
+ * onecall._cloud_inputs hands to the fused opacity launch through cld_tab_fp.  One launch for all samples; how the layers are
+ * dealt to workgroups depends on S and moves no bit.  S < 1, K outside [1, 4], nlayer < 1, nin < 2, average outside {0, 1},
+ * average == 0 with K != 1, a NULL array: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_param_cloud_tables_dev(picaso_ctx *ctx, int S, int K, int nlayer, int nin, int average, const double *layers,
+                                  const double *params, const double *wavelength, double *out /* (S, 3, nlayer, nin) */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -57,6 +57,49 @@ class CloudTables(dict):
         return CloudTables(self.compact, self.in_wno, self.wno[lo:hi])
 
 
+class ResidentCloudTables(CloudTables):
+    """``CloudTables`` of a table that was made in HBM (``parameterizations.ParamCloudTable``, kept in ``resident``):
+    ``compact`` is formed from the table's dictionary face -- one copy back -- only when somebody reads it; the one-call
+    spectrum path takes ``resident.resident_tables`` instead and never does.  The wavelength blocks cut by ``columns`` read
+    the arrays of the object they were cut from: one reshape for all of them."""
+    _NAMES = ("opd", "g0", "w0")
+
+    def __init__(self, resident, nlayer, wno):
+        dict.__init__(self)
+        self.resident, self.nlayer = resident, nlayer
+        self.in_wno = np.ascontiguousarray(resident.grid, dtype=np.float64)
+        self.wno = wno
+
+    @property
+    def compact(self):
+        whole = self.__dict__.get("_whole")
+        if whole is not None:
+            return whole.compact
+        made = self.__dict__.get("_compact")
+        if made is None:
+            made = self.__dict__["_compact"] = {
+                k: np.ascontiguousarray(np.asarray(self.resident[k], dtype=np.float64).reshape(self.nlayer, self.in_wno.size))
+                for k in self._NAMES}
+        return made
+
+    def __iter__(self):
+        return iter(self._NAMES)
+
+    def __len__(self):
+        return len(self._NAMES)
+
+    def __contains__(self, k):
+        return k in self._NAMES
+
+    def keys(self):
+        return list(self._NAMES)
+
+    def columns(self, lo, hi):
+        child = ResidentCloudTables(self.resident, self.nlayer, self.wno[lo:hi])
+        child._whole = self.__dict__.get("_whole", self)       # every block reads the arrays the whole grid's object forms, once
+        return child
+
+
 # Mass (u) of the most abundant isotope of every element: the reference weighs a molecule with these,
 # not with standard atomic weights (``get_weights``, atmsetup.py:285-342: argmax of the isotope
 # abundances), so H2 is 2.01565 rather than 2.01588 -- it enters every opacity through colden/mmw.
@@ -292,6 +335,10 @@ class ATMSETUP:
             self.layer["cloud"] = {"w0": z, "g0": z, "opd": z}
             return
         in_wno = self.input["clouds"]["wavenumber"]
+        if getattr(prof, "resident_tables", None) is not None and prof.nlayer == self.c.nlayer \
+                and not (prof.nin == nwno and np.array_equal(in_wno, wno)):
+            self.layer["cloud"] = ResidentCloudTables(prof, self.c.nlayer, wno)    # rows in HBM: nothing is read here
+            return
         sizes = {np.size(prof[k]) for k in ("opd", "g0", "w0")}
         if in_wno is not None and len(sizes) == 1:          # all three on their own grid: regridded where they are read
             nin = sizes.pop() // self.c.nlayer

@@ -730,7 +730,14 @@ class inputs:
         if not hasattr(self, "nlevel"):
             raise Exception("Please make sure to run `atmosphere` before adding clouds")
         nlayer = self.nlevel - 1
-        if (filename is not None) != (df is not None):
+        if filename is None and getattr(df, "resident_tables", None) is not None:
+            # a table made in HBM (parameterizations.ParamCloudTable) is kept as it is: the one-call path reads its rows
+            # where they lie, everybody else its dictionary face (already sorted by pressure and wavenumber)
+            if df.nlayer != nlayer:
+                raise Exception("There are %d layers in the cloud table, which does not equal %d layers previously "
+                                "specified" % (df.nlayer, nlayer))
+            self.inputs["clouds"].update(profile=df, wavenumber=df.grid)
+        elif (filename is not None) != (df is not None):
             if filename is not None:
                 import pandas as pd
                 df = pd.read_csv(filename, **pd_kwargs)

@@ -92,12 +92,19 @@ def _in_scope(inp, opa, legs, nblocks, opt):
     return not (inp["approx"]["rt_params"]["common"]["raman"] == 0 and nblocks != 1)
 
 
-def _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, hold):
+def _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, hold, subs=()):
     """The cloud tables of the call as ``(device planes | None, device tables on their own grid | None, host planes |
     None)``: tables on their own wavenumber grid (what virga and the box-cloud form of clouds() hand over) are regridded on
     the device as in ``compute_opacity_resident`` -- interpolated inside the opacity launch, no regridded planes in HBM
-    (same bits) -- arrays already on the opacity grid travel as host planes, block by block."""
+    (same bits) -- arrays already on the opacity grid travel as host planes, block by block.  Tables that were made in HBM
+    (``parameterizations.ParamCloudTable``) on the device of every block are handed on where they lie: no host stack, no
+    digest, no upload."""
     cld = atm.layer["cloud"]
+    made = getattr(cld, "resident", None) if tables else None
+    if made is not None and subs and not (opt.unfused_opacity or opt.regrid_planes):
+        faces = [made.resident_tables(nlayer, sub.ctx) for _, _, sub in subs]
+        if all(f is not None for f in faces):
+            return None, faces[0], None
     if tables:
         stack = cld.__dict__.get("_stack")
         if stack is None:
@@ -179,11 +186,15 @@ def _fill_block_opacity(k, sub, lo, hi, c):
     if dtab is not None:
         # kept on the block's opacity object while the tables' content is the same (a digest of every byte): a retrieval
         # that varies the gas keeps its cloud, and eight blocks otherwise pay sixteen uploads per call
-        hit = sub.__dict__.get("_cloud_tables_dev")
-        if hit is None or hit[0] != dtab[3]:
-            hit = sub.__dict__["_cloud_tables_dev"] = (dtab[3], DeviceArray.from_host(dtab[1], sub.ctx),
-                                                       DeviceArray.from_host(dtab[2], sub.ctx))
-        d_xp, d_fp = hit[1], hit[2]
+        if isinstance(dtab[2], DeviceArray):        # made in HBM on this device (a ParamCloudTable): read where they lie
+            d_xp, d_fp = dtab[1], dtab[2]
+        else:
+            hit = sub.__dict__.get("_cloud_tables_dev")
+            if hit is None or hit[0] != dtab[3]:
+                hit = sub.__dict__["_cloud_tables_dev"] = (dtab[3], DeviceArray.from_host(dtab[1], sub.ctx),
+                                                           DeviceArray.from_host(dtab[2], sub.ctx))
+                optics.CLOUD_UPLOADS += 1
+            d_xp, d_fp = hit[1], hit[2]
         hold.append((d_xp, d_fp))
         k.cld_tab_nin, k.cld_tab_xp, k.cld_tab_fp = dtab[0], _lib.ptr(d_xp), _lib.ptr(d_fp)
         k.wno = _lib.ptr(_resident_vector(sub, "wno", sub.wno, nw))
@@ -303,7 +314,7 @@ def prepare(bundle, opa, subs, calculation, opt, slot=None, early=False, regrid=
                                                 linear, choice, host_cloud, do_r, do_t, _constant_planes, sh=is_sh,
                                                 ngauss=opa.ngauss))
     c = _call_state(inp, opa, subs, opt, atm, raman, do_r, do_t, table, ng, nt, regrid)
-    c["clouds"] = _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, c["hold"])
+    c["clouds"] = _cloud_inputs(atm, opa, tables, nlayer, nwno, opt, c["hold"], subs)
     # The opacity stage first (round 6): as soon as the table rows / weights / coefficients are in the job and the cloud
     # inputs in the blocks, the gas kernel goes on the stream (drv.enqueue(phase=1)); geometry, level tables, resident
     # vectors, result buffers -- what the legs read -- are filled while it runs, and ``run`` enqueues the legs (phase 2).

@@ -1397,6 +1397,10 @@ def compute_opacity_facet_major_ck(atm_f, opacityclass, numg, numt, stream=2, de
     return out
 
 
+CLOUD_UPLOADS = 0       # uploads of cloud tables on their own grid for a fused opacity launch, by this process so far: here
+#                         and in onecall._fill_block_opacity (a memo hit there, or a table made in HBM, does not count)
+
+
 def _wno_device(opa, wno):
     """The wavenumber grid as a device vector; the opacity object's own grid is uploaded once."""
     if wno is opa.wno:
@@ -1415,6 +1419,7 @@ def compute_opacity_resident(atmosphere, opacityclass, ngauss=1, stream=2, delta
     for monochromatic opacities, ``(rows, nwno, ngauss)`` (reference layout, optics.py:423-431)
     for correlated-k tables.  (3-D path: ``compute_opacity_facets``.)  ``want``: names of the planes
     the caller will read (default all 13); the others are neither allocated nor written."""
+    global CLOUD_UPLOADS
     atm, opa = atmosphere, opacityclass
     if ngauss != opa.ngauss:
         raise Exception("compute_opacity: ngauss=%d but the opacity tables have %d Gauss points"
@@ -1450,11 +1455,17 @@ def compute_opacity_resident(atmosphere, opacityclass, ngauss=1, stream=2, delta
     elif on_device and fused and not do_holes and not _options().regrid_planes:
         # tables on their own wavenumber grid, interpolated INSIDE the fused opacity launch (numpy.interp's bits, as
         # picaso_regrid_rows_dev): no regridded planes in HBM
-        stack = cld.__dict__.get("_stack")
-        if stack is None:
-            stack = cld.__dict__["_stack"] = np.concatenate([cld.compact[k] for k in ("opd", "w0", "g0")])
-        tab_keep = (DeviceArray.from_host(np.ascontiguousarray(cld.in_wno, dtype=np.float64), ctx),
-                    DeviceArray.from_host(np.ascontiguousarray(stack, dtype=np.float64), ctx), _wno_device(opa, cld.wno))
+        made = getattr(cld, "resident", None)
+        face = made.resident_tables(nlayer, ctx) if made is not None else None
+        if face is not None:        # rows made in HBM on this device (parameterizations.ParamCloudTable): read where they lie
+            tab_keep = (face[1], face[2], _wno_device(opa, cld.wno))
+        else:
+            stack = cld.__dict__.get("_stack")
+            if stack is None:
+                stack = cld.__dict__["_stack"] = np.concatenate([cld.compact[k] for k in ("opd", "w0", "g0")])
+            tab_keep = (DeviceArray.from_host(np.ascontiguousarray(cld.in_wno, dtype=np.float64), ctx),
+                        DeviceArray.from_host(np.ascontiguousarray(stack, dtype=np.float64), ctx), _wno_device(opa, cld.wno))
+            CLOUD_UPLOADS += 1
         cld_tab = (int(np.size(cld.in_wno)), ptr(tab_keep[0].addr), ptr(tab_keep[1].addr), ptr(tab_keep[2].addr))
         d_cld = d_w0 = d_g0 = None
     elif on_device:     # tables on their own wavenumber grid: interpolated where they are used (same bits)
