@@ -10,7 +10,7 @@ import numpy as np
 
 OFFSET = int(os.environ.get("PICASO_FUZZ_OFFSET", "0"))        # shifts every seed, as in test_fuzz_gpu.py
 NBLOCK, NDRAW = 4, 16
-SH_MAX_ANG = 16                                                 # sh.hip: angles of one launch of k_sh_thermal
+SH_MAX_ANG = 16                                                 # sh.hpp: angles of one launch of k_sh_thermal
 
 # Offset 0 is the committed set: every block must hold at least three draws with more than SH_MAX_ANG angles (a second
 # launch of launch_sh_thermal) and one with 17 or 18 (a short second launch).  The recipe gives 5 x 4, 6 x 3 or 6 x 4 to about

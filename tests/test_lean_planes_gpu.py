@@ -103,7 +103,7 @@ def test_lean_planes_not_used_with_clouds_or_test_mode(monkeypatch):
 def test_sh4_cloud_free_writes_two_planes(monkeypatch, calc):
     """rt_method='SH', stream 4, default forms, no cloud: dtau and w0 are written and the cloud-free SH launch
     (k_sh4_clear) solves them; reflected light agrees with the full-plane launch to the oracle's tolerance (not bit for
-    bit: sh.hip), thermal emission -- the same kernel on the same two planes -- is bit-identical.  Other
+    bit: sh_clear.hip), thermal emission -- the same kernel on the same two planes -- is bit-identical.  Other
     forms or layer fluxes keep the thirteen planes; a cloud with the default forms takes eight."""
     from picaso_amd import justdoit as jdi
     from picaso_amd import optics as px

@@ -1,5 +1,5 @@
 """get_reflected_SH (reference fluxes.py:2675-2976, 3336-3607) for cloud-free columns with the angle-independent half of
-each layer shared between the disk angles of a lane (`k_sh4_clear<NA>`, sh.hip): the call with `dtau` and `w0` only
+each layer shared between the disk angles of a lane (`k_sh4_clear<NA>`, sh_clear.hip): the call with `dtau` and `w0` only
 against the oracle on the full plane set, against the full-plane kernel (`k_sh`: to the oracle's tolerance, not bit for bit --
 see the kernel's header), and the same bits however many angles share a lane and however the wavelengths are cut."""
 import numpy as np

@@ -1,5 +1,5 @@
 """get_thermal_SH (reference fluxes.py:2979-3182) with the angle-independent block algebra shared between the disk
-angles of a lane (`k_sh_thermal<NB, NA>`, sh.hip): against the oracle on fresh scenes, against the round-2 kernel
+angles of a lane (`k_sh_thermal<NB, NA>`, sh_thermal.hip): against the oracle on fresh scenes, against the round-2 kernel
 (one wave per angle, `PICASO_AMD_SH_THERMAL_PER_ANGLE=1`), and the same bits however many angles share a lane
 (`PICASO_AMD_SHT_ANGLES=1..5`) and however the wavelengths are cut into blocks."""
 import numpy as np

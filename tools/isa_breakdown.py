@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Instruction breakdown of a kernel's layer loop from the gfx950 disassembly (no GPU needed).
 
-    python tools/isa_breakdown.py picaso_amd/csrc/sh.hip 'k_shILi2ELb0ELb0ELb1E' [-o profiles/r05_isa_k_sh4_fast.json]
+    python tools/isa_breakdown.py picaso_amd/csrc/sh_sweep.hip 'k_sh_reflILi2ELb1ELb0E' [-o profiles/r05_isa_k_sh4_fast.json]
 
 Compiles the file to device assembly (hipcc -S --cuda-device-only, the library's flags), takes the kernel whose mangled
 name contains the pattern, finds its loops (a backward branch to a label) and reports, for the loop with the most

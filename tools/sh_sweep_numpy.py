@@ -12,7 +12,7 @@ carry the relation d_i = delta_i - R_i v_i (R: 2x2) downwards together with the 
 J = kappa + zeta . v_i (reference source-function integrals fluxes.py:2898-2970), so the banded
 matrix is never formed and no pivoting across layers is needed (the 2x2 blocks are the physical
 reflection operators; all exponentials that appear are decaying).  Development / test aid for
-picaso_amd/csrc/sh.hip; checked by tests/test_single_sweep_numpy.py.
+picaso_amd/csrc/sh_sweep.hip; checked by tests/test_single_sweep_numpy.py.
 """
 import numpy as np
 
