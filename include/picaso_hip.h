@@ -222,6 +222,9 @@ int picaso_reflected_1d_can_derive(int nlevel, long plane_pitch, int numg, int n
  * bits do not change; every other layer is read and tested as before.  A batch takes the masks when every member's seal
  * has one.  The mask is no flag (*flags_out stays PICASO_SEAL_LEVELS & ~failed) and lives and dies with its seal.
  * PICASO_AMD_REFL_NO_LAYER_MASK=1 in the environment switches its use off (the launch is then the sealed one above).
+ * In the run of cloud-free layers from the top, that launch (and the cloud-free one that is handed dtau and w0 alone)
+ * forms exp(-dtau/u) without range reduction while |dtau| <= 0.34 min(ubar) holds in every column of a wave: the same
+ * bits with four instructions fewer per exponential.  PICASO_AMD_REFL_NO_SMALL_EXP=1 (read per launch) switches that off.
  * picaso_reflected_seal_layers: clear_out[i] = 1 / 0 for the first min(cap, nlayer) layers of the sealed set that owns
  * the byte at any_plane_ptr, *nlayer_out = its layer count -- 0 when there is no such set or it recorded no mask.
  * picaso_reflected_seal_layers_stat: *mask_launches = launches on the context's device that used a mask (each is also

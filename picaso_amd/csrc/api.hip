@@ -571,6 +571,23 @@ static ReflectedArgs::Angle make_refl_angle(double v0, double v1, double gw, dou
     return g;
 }
 
+// ReflectedArgs::dt_small for a call with these angles (a batch: every member's table).  The kernel forms
+// t = fl(dtau * nl1) with nl1 = fl(-log2(e) / u): for |dtau| <= fl(0.34 min u) that is at most
+// 0.34 * 1.4427 * (1 + eps)^3 = 0.49052 in magnitude for the smallest u and, the rounded product being monotone in
+// |dtau| and in |nl1|, no more for any other (dtau, angle) the test lets through.  PICASO_AMD_REFL_NO_SMALL_EXP=1 (the
+// A/B switch, read per launch) and angle tables the bound says nothing about give a negative bound: no layer passes.
+static double refl_dt_small(const double *ubar0, const double *ubar1, int count)
+{
+    if (getenv("PICASO_AMD_REFL_NO_SMALL_EXP") || !ubar0 || !ubar1 || count < 1) return -1.0;
+    double umin = 1.0;
+    for (int k = 0; k < count; ++k) {
+        const double v0 = fabs(ubar0[k]), v1 = fabs(ubar1[k]);
+        if (!(v0 > 0.0) || !(v1 > 0.0)) return -1.0;
+        umin = fmin(umin, fmin(v0, v1));
+    }
+    return 0.34 * umin;
+}
+
 // A batched call (picaso_get_reflected_1d_batch_dev): host arrays of nspec device pointers and the geometries
 struct ReflBatchHost {
     int nspec;
@@ -716,6 +733,7 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
     a.constant_forward = constant_forward; a.b_top = b_top;
     a.use_lmask = use_lmask ? 1 : 0;
     if (use_lmask) { a.lmask[0] = lmasks[0]; a.lmask[1] = lmasks[1]; }
+    a.dt_small = refl_dt_small(ubar0, ubar1, (bt ? bt->ngeom : 1) * nang);
     const bool fuse = albedo && gweight && tweight;
     a.albedo = fuse ? albedo : nullptr;
     a.albedo_scale = ((numt == 1) ? 2.0 * 3.14159265358979323846 : 1.0) * 0.5;   // disco.py:140-141

@@ -193,6 +193,10 @@ struct ReflectedArgs {
     // kernel then reads dtau and w0 of that layer alone.  0 everywhere else.  A batched launch: the entry's own mask.
     unsigned long long lmask[2];
     int use_lmask;                          // the launcher's request for that variant (every member's mask is valid)
+    // The zero-phase default-options kernels (DRV 2 / 3 / 4): a cloud-free layer whose |dtau| <= dt_small in every lane of
+    // the wave forms exp(-dtau/u) without range reduction (fexp2_small).  0.34 min(u) over every angle of the call (a
+    // batch: of every member): dtau * nl1 as the kernel rounds it then lies within +-0.4906.  Negative: never.
+    double dt_small;
 };
 struct ReflBatchItem {
     const double *dtau, *tau, *w0, *cosb, *gcos2, *ftau_cld, *ftau_ray, *dtau_og, *tau_og, *w0_og, *cosb_og;

@@ -117,6 +117,22 @@ enum { S_T = 0, S_XU, S_EO, S_KAPPA, S_ZETA, S_D1, S_D2 };   // late-use variabl
 #ifndef PZ_REFL_CLEAR_ENDS_LAYERS
 #define PZ_REFL_CLEAR_ENDS_LAYERS 1
 #endif
+// PZ_REFL_SMALL_EXP: a cloud-free layer with |dtau| <= a.dt_small in every lane of the wave (one compare and a vote per
+// layer) takes a copy of the cloud-free body whose five exp(-dtau/u) leave out the range reduction (reflected_layer's SX:
+// a trip of two layers is 758 VALU instructions against 793, same bits).  Bit 0: the top run starts with a loop of such
+// copies and leaves it for the general loop at the first trip with a layer that fails the vote.  Bit 1: the masked loop selects such a copy next to its other three --
+// off: with a fourth copy in its dispatch the DRV = 3 and DRV = 4 kernels get a private segment (20-28 and 60 bytes of
+// spills at 254 VGPRs), and the layers it would serve are few (below a cloud deck the optical depths are mostly large).
+#ifndef PZ_REFL_SMALL_EXP
+#define PZ_REFL_SMALL_EXP 1
+#endif
+// PZ_REFL_RUNS: every maximal run of sealed cloud-free interior layers BELOW the top run (under a cloud deck) gets a loop of
+// its own as well: the top run's loads and waits, the cloud-free copy of the body that keeps S_EO.  The masked loop's mask
+// test, vmcnt(0) and dispatch block around each such layer (15-22 VALU) go; same operations on the same numbers.  =0: the
+// masked loop takes those layers one by one.
+#ifndef PZ_REFL_RUNS
+#define PZ_REFL_RUNS 1
+#endif
 enum { ZF_XT = 1, ZF_EOX = 2 };    // reflected_layer's ZF: S_T is S_XU / eo is S_XU too
 // One reciprocal for all angles of a layer (Montgomery batch inversion) instead of one per angle:
 // -1.3 % time at five angles, but an angle's result then depends (in its last bits) on which angles
@@ -179,8 +195,12 @@ struct LayerIn {
 // the flags are true, so the bits do not change.
 // SDT (with AF): 1 = same_dt holds as well (the cloud-free copy), 2 = it does not (the usual cloud layer: delta-
 // scaled, so dtau_og != dtau and the two extra exponentials are always formed) -- both straight-line.
+// SX (PZ_REFL_SMALL_EXP, with NC, AF, SDT = 1 in the zero-phase kernels): every lane's |dtau| is at most a.dt_small, so
+// dtau * nl1 lies within +-1/2 for every angle of the launch and et is formed by fexp2_small -- fexp2 without its four
+// range-reduction instructions, the same bits (device_math.hpp).  e0 is et there; EP and the cloudy body's dtau_og
+// exponentials take other arguments and keep the general form.
 template <int NA, bool IS3D, bool ZP, bool FIRST, bool LAST, bool LDS, bool FAST = false, bool NC = false,
-          bool AF = false, int SDT = 1, int ZF = 0>
+          bool AF = false, int SDT = 1, int ZF = 0, bool SX = false>
 __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const LayerIn &L,
                                                 ReflState<NA, LDS> &S,
                                                 const ReflectedArgs::Angle (&g)[NA],
@@ -196,6 +216,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     constexpr bool XT = (ZF & ZF_XT) != 0, EOX = (ZF & ZF_EOX) != 0;
     static_assert(!ZF || (FAST && ZP), "ZF: the zero-phase default-options kernels only");
     static_assert(!EOX || (NC && AF && SDT == 1), "ZF_EOX: the cloud-free copy only");
+    static_assert(!SX || (FAST && ZP && NC && AF && SDT == 1), "SX: the cloud-free copy of the zero-phase default-options kernels only");
     const int tc = FAST ? 0 : tc_;
     const int single_phase = FAST ? 3 : a.single_phase;
     const int multi_phase = FAST ? 0 : a.multi_phase;
@@ -307,7 +328,8 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
         const double rd = r3 * den;                        // 1/((lu-1)(lu+1))
         const double hz = NC ? iu0_k : fma(A1, u0_k, iu0_k);
         const double am2 = A0 + hz, ap2 = A0 - hz;
-        const double et = fexp2(dt * nl1_k, K);              // exp(-dtau/u1)
+        // exp(-dtau/u1).  SX: the caller's vote says |dt * nl1_k| <= 1/2 in every lane and for every angle: same bits
+        const double et = SX ? fexp2_small(dt * nl1_k, K) : fexp2(dt * nl1_k, K);
         const double e0 = ZP ? et : fexp2(dt * nl0_k, K);    // exp(-dtau/u0)
         const double xu = S.get(S_XU, k), Tk = XT ? xu : S.get(S_T, k);
         const double xd = (AF || XT || L.cum_tau) ? xu * e0 : fexp2_cold(L.tau_n * nl0_k, K);
@@ -506,6 +528,12 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     constexpr bool ZDRV = FAST && ZP && !IS3D && (CLEAR || LEVELS);
     constexpr int ZX = (ZDRV && PZ_REFL_MERGE_XT) ? ZF_XT : 0;
     constexpr bool TOPRUN = ZDRV && (CLEAR || LAYERS) && PZ_REFL_TOPRUN;
+    constexpr bool DECKRUN = ZDRV && LAYERS && TOPRUN && PZ_REFL_RUNS;                     // run loops below the top run
+    constexpr bool SMALLX = ZDRV && (PZ_REFL_SMALL_EXP & 1) && TOPRUN;                    // the loop of the top run
+    constexpr bool SMALLM = ZDRV && (PZ_REFL_SMALL_EXP & 2) && PZ_REFL_NOCLD_BODY;        // the copy of the masked loop
+    const double dt_small = a.dt_small;
+    // wave-uniform; a NaN fails it
+    auto small_dt = [&](double dt) -> bool { return (SMALLX || SMALLM) && __all(__builtin_fabs(dt) <= dt_small); };
     constexpr int CLEAR_ENDS = !ZDRV ? 0 : CLEAR ? PZ_REFL_CLEAR_ENDS : LAYERS ? (PZ_REFL_CLEAR_ENDS & PZ_REFL_CLEAR_ENDS_LAYERS) : 0;
     // the mask, read once
     unsigned long long m0 = 0, m1 = 0;
@@ -682,6 +710,8 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         constexpr int kzf_ = kcopy_ ? (ZX | ((FIRST_) ? ZF_EOX : 0)) : 0;                                \
         if (kcopy_ && (CLEAR || lclear_))                                                                \
             reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, kcopy_, kcopy_, 1, kzf_>(a, L_, S, g, K, F, clip, tc, b_top); \
+        else if (SMALLM && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf && small_dt(L_.dt))              \
+            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, SMALLM, SMALLM, 1, SMALLM ? ZX : 0, SMALLM>(a, L_, S, g, K, F, clip, tc, b_top); \
         else if (PZ_REFL_NOCLD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf)             \
             reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, true, true, 1, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
         else if (PZ_REFL_CLOUD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.af_cloud)                      \
@@ -691,10 +721,18 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         if constexpr (CLEAR) __builtin_amdgcn_sched_barrier(0);   /* straight-line code: keep the layers apart */ \
     } while (0)
     // a layer of the clear run from the top: known cloud-free, nothing above it delta-scaled
-#define PZ_RUN_LAYER(L_)                                                                                 \
+#define PZ_RUN_LAYER(L_, SX_)                                                                            \
     do {                                                                                                 \
         prep(L_, true);                                                                                  \
-        reflected_layer<NA, IS3D, ZP, false, false, LDS, FAST, TOPRUN, TOPRUN, 1, TOPRUN ? (ZX | ZF_EOX) : 0>(a, L_, S, g, K, F, clip, tc, b_top); \
+        reflected_layer<NA, IS3D, ZP, false, false, LDS, FAST, TOPRUN, TOPRUN, 1, TOPRUN ? (ZX | ZF_EOX) : 0, TOPRUN && (SX_)>(a, L_, S, g, K, F, clip, tc, b_top); \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+    } while (0)
+
+    // a layer of a clear run below the top run: known cloud-free, S_EO kept
+#define PZ_DECK_LAYER(L_)                                                                                \
+    do {                                                                                                 \
+        prep(L_, true);                                                                                  \
+        reflected_layer<NA, IS3D, ZP, false, false, LDS, FAST, DECKRUN, DECKRUN, 1, DECKRUN ? ZX : 0>(a, L_, S, g, K, F, clip, tc, b_top); \
         __builtin_amdgcn_sched_barrier(0);                                                               \
     } while (0)
 
@@ -709,6 +747,12 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
 #ifndef PZ_REFL_TWOSETS_NONZP
 #define PZ_REFL_TWOSETS_NONZP 0
 #endif
+    // a layer of a run: dtau and w0 alone
+    auto load_clear = [&](LayerIn &L, int l) {
+        const unsigned o = voff0 + (unsigned)l * pitch8;
+        L.dt = ld(a.dtau, o);
+        L.w0 = ld(a.w0, o);
+    };
     constexpr bool TWO_SETS = (NA <= 2) || (PZ_REFL_TWOSETS_5 && NA == 5 && FAST && (ZP || PZ_REFL_TWOSETS_NONZP));   // generic five-angle kernel: 30 VGPRs spilled with it
     LayerIn A, B;
     load(A, 0);
@@ -729,16 +773,32 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
                 if constexpr (TOPRUN) {
                     // layers i, i+1 and the two prefetched ones (i+1, i+2) all belong to the run: two loads each, so the
                     // compiler's own counted vmcnt waits do, and no mask is looked at
-                    auto load_clear = [&](LayerIn &L, int l) {
-                        const unsigned o = voff0 + (unsigned)l * pitch8;
-                        L.dt = ld(a.dtau, o);
-                        L.w0 = ld(a.w0, o);
-                    };
+                    if constexpr (SMALLX) {
+                        // The small-argument loop: a trip runs while both of its layers pass the vote, then the sweep
+                        // moves to the general loop below for the rest of the run and never comes back.  Both votes are
+                        // taken before the trip on values loaded a trip ago -- B, and dtau of layer i + 1 read one layer
+                        // further ahead than the rest of A (two more VGPRs) -- so the loop has one exit and each trip is
+                        // one straight-line block of two layers; the row index is clamped to the last layer of the planes.
+                        if (i + 2 < r) {
+                            double dt_a = ld(a.dtau, voff0 + (unsigned)(i + 1) * pitch8);
+                            bool go = small_dt(B.dt) && small_dt(dt_a);
+                            while (go) {
+                                A.dt = dt_a;
+                                A.w0 = ld(a.w0, voff0 + (unsigned)(i + 1) * pitch8);
+                                PZ_RUN_LAYER(B, true);
+                                load_clear(B, i + 2);
+                                dt_a = ld(a.dtau, voff0 + (unsigned)(i + 3 < n ? i + 3 : n - 1) * pitch8);
+                                PZ_RUN_LAYER(A, true);
+                                i += 2;
+                                go = i + 2 < r && small_dt(B.dt) && small_dt(dt_a);
+                            }
+                        }
+                    }
                     for (; i + 2 < r; i += 2) {
                         load_clear(A, i + 1);
-                        PZ_RUN_LAYER(B);
+                        PZ_RUN_LAYER(B, false);
                         load_clear(B, i + 2);
-                        PZ_RUN_LAYER(A);
+                        PZ_RUN_LAYER(A, false);
                     }
                 }
                 // the run ends here (the layers left of it, at most two, take the masked loop): from now on S_EO is kept.
@@ -748,6 +808,25 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
             }
         }
         for (; i + 2 <= n - 1; i += 2) {         // layers i and i+1 are interior, layer i+2 exists
+            if constexpr (DECKRUN) {
+                // A run of sealed cloud-free interior layers below the top run (under a cloud deck, between two): swept
+                // like the top run -- two loads per layer under the compiler's counted waits, no mask test, no dispatch --
+                // by the cloud-free copy of the body that keeps S_EO (a layer above was delta-scaled, so S_EO is not S_XU).
+                // e: one past the run that starts at layer i (scalar bit operations on the mask), the last layer left out.
+                const unsigned long long w = i < 64 ? (m0 >> i) | (i ? m1 << (64 - i) : 0ull) : m1 >> (i - 64);
+                int e = i + ((~w) ? __builtin_ctzll(~w) : 64);
+                e = e < n - 1 ? e : n - 1;
+                if (i + 2 < e) {
+                    // as in the top run: layers i .. i + 2 belong to the run, B holds layer i on the way in and out
+                    for (; i + 2 < e; i += 2) {
+                        load_clear(A, i + 1);
+                        PZ_DECK_LAYER(B);
+                        load_clear(B, i + 2);
+                        PZ_DECK_LAYER(A);
+                    }
+                    if (!(i + 2 <= n - 1)) break;
+                }
+            }
             load(A, i + 1, true);
             PZ_LAYER(false, false, B, i);
             load(B, i + 2, true);
@@ -773,6 +852,7 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     }
 #undef PZ_LAYER
 #undef PZ_RUN_LAYER
+#undef PZ_DECK_LAYER
 
     // ---- surface row (fluxes.py:178-183) and output ----
     // EP(1 - rs G) pos + EM(G - rs) neg = b_surface - c+dn + rs c-dn with neg = delta - rho pos,
