@@ -909,25 +909,25 @@ int launch_sh(picaso_ctx *ctx, SHArgs &a, int nang, bool thermal)
     if (drvt && (!fast || a.tau || a.tau_og))
         return fail(ctx, "get_reflected_SH: tau and tau_og may be left out (both) only with the reference's default "
                          "options, flx = 0 and planes below 4 GB (picaso_reflected_SH_can_derive_levels)");
-#define PZ_GO(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(block), 0, ctx->stream, a)
+#define SH_GO(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(block), 0, ctx->stream, a)
     if (!thermal && !flx) {                         // single spectrum (a.batch = NULL) or a batch: the same kernel
         if (a.stream == 4) {
-            if (drvt) PZ_GO((k_sh_refl<2, true, true>));
-            else if (fast) PZ_GO((k_sh_refl<2, true>));
-            else PZ_GO((k_sh_refl<2, false>));
+            if (drvt) SH_GO((k_sh_refl<2, true, true>));
+            else if (fast) SH_GO((k_sh_refl<2, true>));
+            else SH_GO((k_sh_refl<2, false>));
         } else {
-            if (drvt) PZ_GO((k_sh_refl<1, true, true>));
-            else if (fast) PZ_GO((k_sh_refl<1, true>));
-            else PZ_GO((k_sh_refl<1, false>));
+            if (drvt) SH_GO((k_sh_refl<1, true, true>));
+            else if (fast) SH_GO((k_sh_refl<1, true>));
+            else SH_GO((k_sh_refl<1, false>));
         }
     } else if (a.stream == 4) {
-        if (thermal) PZ_GO((k_sh<2, true, false>));
-        else PZ_GO((k_sh<2, false, true>));
+        if (thermal) SH_GO((k_sh<2, true, false>));
+        else SH_GO((k_sh<2, false, true>));
     } else {
-        if (thermal) PZ_GO((k_sh<1, true, false>));
-        else PZ_GO((k_sh<1, false, true>));
+        if (thermal) SH_GO((k_sh<1, true, false>));
+        else SH_GO((k_sh<1, false, true>));
     }
-#undef PZ_GO
+#undef SH_GO
     PZ_HIP(ctx, hipGetLastError());
     return 0;
 }

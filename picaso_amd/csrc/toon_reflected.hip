@@ -39,27 +39,30 @@
 
 namespace pz {
 
+// The three numeric tuning parameters of the file (-D overridable: PICASO_HIPCC_EXTRA with tools/ab.sh).  None selects a
+// code path.
 // Two waves per SIMD: one fp64 wave alone issues at most every ~5.1 cycles (tools/ubench/
 // f64_rates.hip) while the pipe accepts one per ~3.5-4, and a 1e5-column spectrum is only 1.5 waves
 // per SIMD, so co-residency beats the extra scratch spills (measured 0.405 ms vs 0.481 ms).
 #ifndef PZ_REFL_MINWAVES
 #define PZ_REFL_MINWAVES 2
 #endif
-// threads per block (a tuning knob of tools/sweep.sh; the LDS state tile is [var][angle][PZ_REFL_BLOCK])
+// threads per block (the LDS state tile is [var][angle][PZ_REFL_BLOCK])
 #ifndef PZ_REFL_BLOCK
 #define PZ_REFL_BLOCK 256
 #endif
 
 // Per-angle sweep state (7 doubles per angle).  D1 = c+dn + Gamma EM delta, D2 = c-dn + EM delta of
 // the layer above: the only combinations of (c+dn, c-dn, delta) the next interface and the surface
-// row need.  For NA >= 4 part of the state lives in LDS ([var][angle][lane], so a wave's
+// row need.  For NA >= LDS_MIN_ANGLES part of the state lives in LDS ([var][angle][lane], so a wave's
 // ds_read_b64 / ds_write_b64 hit 64 consecutive 8-byte words: conflict free): all in registers the
 // 5-angle kernel needs ~300 VGPRs, i.e. either one wave per SIMD or ~50 registers spilled to
 // scratch, whose reloads share the vmcnt queue with the plane prefetch.
 constexpr int NSTATE = 7;
 enum { S_T = 0, S_XU, S_EO, S_KAPPA, S_ZETA, S_D1, S_D2 };   // late-use variables last
+constexpr int LDS_MIN_ANGLES = 4;
 
-// NLDS = how many of the state variables (counted from the END of the enum order below) live in
+// NLDS = how many of the state variables (counted from the END of the enum order above) live in
 // LDS when LDS is on; the rest stay in registers.
 // Measured on the 5-angle headline case: 0 -> 50 VGPRs spilled to scratch (0.416 ms), 4 -> no
 // spills, 41 KB LDS per block (0.410 ms), 7 -> 72 KB (0.421 ms): the kernel is VALU-issue bound,
@@ -67,82 +70,7 @@ enum { S_T = 0, S_XU, S_EO, S_KAPPA, S_ZETA, S_D1, S_D2 };   // late-use variabl
 #ifndef PZ_REFL_NLDS
 #define PZ_REFL_NLDS 4
 #endif
-// one reciprocal for all angles of a layer (batch inversion) instead of one per angle
-// FAST kernels address the planes as SGPR base + 32-bit lane offset (the launcher checks that a plane
-// is smaller than 4 GB); 0 = 64-bit lane addresses everywhere (A/B switch)
-#ifndef PZ_REFL_SADDR
-#define PZ_REFL_SADDR 1
-#endif
-// second copy of the interior layer body for layers without cloud (FAST kernels only)
-#ifndef PZ_REFL_FAST_NONZP
-#define PZ_REFL_FAST_NONZP 1
-#endif
-#ifndef PZ_REFL_LEVELS_VARIANT
-#define PZ_REFL_LEVELS_VARIANT 1
-#endif
-#ifndef PZ_REFL_LAYERS_VARIANT
-#define PZ_REFL_LAYERS_VARIANT 1
-#endif
-#ifndef PZ_REFL_CLEAR_VARIANT
-#define PZ_REFL_CLEAR_VARIANT 1
-#endif
-#ifndef PZ_REFL_CLOUD_BODY
-#define PZ_REFL_CLOUD_BODY 1
-#endif
-#ifndef PZ_REFL_NOCLD_BODY
-#define PZ_REFL_NOCLD_BODY 1
-#endif
-// Work the zero-phase default-options kernels that form the level sums themselves (FAST, ZP, DRV 2 / 3 / 4) do not need;
-// each switch removes operations whose result is already held, none changes a bit (=0: the code as it was):
-// PZ_REFL_MERGE_XT: S_T (the running exp(-tau/u1)) and S_XU (exp(-tau/u0)) are one number there -- u0 == u1, both start at
-//   1.0 (fexp2 of 0 * nl1 = -0: rint -0, f = +0, fma(0, p, 1) = 1, ldexp(1, 0)) and every layer multiplies both by et --
-//   so S_XU alone is carried: five multiplies and ten VGPRs per layer in every copy of the body.
-// PZ_REFL_TOPRUN: while no layer above was delta-scaled S_EO is that number too (eo starts at fexp2_cold(-0) = 1.0 and
-//   e0o == e0 in a layer with dtau_og == dtau).  The run of sealed cloud-free layers from the top (all of a DRV = 2
-//   column) is swept by a loop of its own that reads eo from S_XU, keeps no S_EO, loads two planes per layer without
-//   looking at the mask and waits for them by count; S_EO is set from S_XU once where the run ends.
-// PZ_REFL_CLEAR_ENDS: the first and the last layer take straight-line copies of the cloud-free body when they are such
-//   layers (the general body's operations with its flags true, as for the interior copies).  Bit 0: the first, bit 1: the last.
-#ifndef PZ_REFL_MERGE_XT
-#define PZ_REFL_MERGE_XT 1
-#endif
-#ifndef PZ_REFL_TOPRUN
-#define PZ_REFL_TOPRUN 1
-#endif
-#ifndef PZ_REFL_CLEAR_ENDS
-#define PZ_REFL_CLEAR_ENDS 3
-#endif
-// ... and which of them the DRV = 4 kernels take: a third and fourth copy of the last layer beside the general ones gave
-// them a private segment (28 bytes of spills at 254 VGPRs, 44 in the batched form), so only the first layer there
-#ifndef PZ_REFL_CLEAR_ENDS_LAYERS
-#define PZ_REFL_CLEAR_ENDS_LAYERS 1
-#endif
-// PZ_REFL_SMALL_EXP: a cloud-free layer with |dtau| <= a.dt_small in every lane of the wave (one compare and a vote per
-// layer) takes a copy of the cloud-free body whose five exp(-dtau/u) leave out the range reduction (reflected_layer's SX:
-// a trip of two layers is 758 VALU instructions against 793, same bits).  Bit 0: the top run starts with a loop of such
-// copies and leaves it for the general loop at the first trip with a layer that fails the vote.  Bit 1: the masked loop selects such a copy next to its other three --
-// off: with a fourth copy in its dispatch the DRV = 3 and DRV = 4 kernels get a private segment (20-28 and 60 bytes of
-// spills at 254 VGPRs), and the layers it would serve are few (below a cloud deck the optical depths are mostly large).
-#ifndef PZ_REFL_SMALL_EXP
-#define PZ_REFL_SMALL_EXP 1
-#endif
-// PZ_REFL_RUNS: every maximal run of sealed cloud-free interior layers BELOW the top run (under a cloud deck) gets a loop of
-// its own as well: the top run's loads and waits, the cloud-free copy of the body that keeps S_EO.  The masked loop's mask
-// test, vmcnt(0) and dispatch block around each such layer (15-22 VALU) go; same operations on the same numbers.  =0: the
-// masked loop takes those layers one by one.
-#ifndef PZ_REFL_RUNS
-#define PZ_REFL_RUNS 1
-#endif
-enum { ZF_XT = 1, ZF_EOX = 2 };    // reflected_layer's ZF: S_T is S_XU / eo is S_XU too
-// One reciprocal for all angles of a layer (Montgomery batch inversion) instead of one per angle:
-// -1.3 % time at five angles, but an angle's result then depends (in its last bits) on which angles
-// share its lane, i.e. on the angle chunking and on whether a small wavelength shard takes the
-// one-angle-per-wave path.  Off: a column's result is bit-identical however the grid is sharded and
-// the angles are grouped, which the multi-GPU path and its tests rely on.
-#ifndef PZ_REFL_BATCH_RCP
-#define PZ_REFL_BATCH_RCP 0
-#endif
-// PZ_REFL_DIET (common.hpp): the round-5 regrouping of this body's arithmetic; 0 = the round-4 operation order
+
 template <int NA, bool LDS>
 struct ReflState {
     static constexpr int NL = LDS ? PZ_REFL_NLDS : 0;      // variables [NSTATE-NL, NSTATE) in LDS
@@ -172,6 +100,26 @@ struct LayerIn {
     bool af_cloud;   // cum_tau && eo_ok && !same_dt on a layer with cloud
 };
 
+// The copies of the layer body.  All perform the general body's operations on the same numbers, so which copy runs a
+// layer never changes a bit; the later ones leave out what their layer is known not to need.
+//   BODY_GENERAL          any layer: the wave-uniform flags of LayerIn are tested per angle.
+//   BODY_CLOUD            cum_tau and eo_ok hold, same_dt does not (the usual cloud layer: delta-scaled, so dtau_og != dtau
+//                         and the two extra exponentials are always formed), straight-line.
+//   BODY_CLEAR            cum_tau, eo_ok and same_dt hold and no lane has cloud (ftau_cld == 0, checked per wave by the
+//                         caller or known from a seal): every term that carries ftau_cld*cosb drops out.  The remaining
+//                         operations are the general ones with fcg = +0 folded by hand (x + 0, x * 1 and fma(0, y, z)
+//                         are exact).
+//   BODY_CLEAR_TOP        BODY_CLEAR where no layer above was delta-scaled: exp(-tau_og/u0) is S_XU (it starts at
+//                         fexp2_cold(-0) = 1.0 and e0o == e0 in a layer with dtau_og == dtau), so S_EO is neither read nor
+//                         kept.
+//   BODY_CLEAR_TOP_SMALL  BODY_CLEAR_TOP where every lane's |dtau| is at most a.dt_small, so dtau * nl1 lies within +-1/2
+//                         for every angle of the launch and et is formed by fexp2_small -- fexp2 without its four range-
+//                         reduction instructions, the same bits (device_math.hpp).  e0 is et there; EP takes another
+//                         argument and keeps the general form.
+// Assuming the flags (every copy but the general one) removes the 3-4 wave-uniform branches per angle they feed and the
+// fall-back exponentials behind them; DESIGN.md section 6 has what each copy measured.
+enum Body { BODY_GENERAL, BODY_CLOUD, BODY_CLEAR, BODY_CLEAR_TOP, BODY_CLEAR_TOP_SMALL };
+
 // One layer of the sweep.  FIRST / LAST are compile-time so the top row and the bottom-boundary
 // terms cost nothing inside the loop.  ZP: every angle has ubar0 == ubar1 (symmetric 1-D geometry,
 // reference justdoit.py:1513-1532): exp(-dtau (u0+u1)/(u0 u1)) = exp(-dtau/u1)^2, and when the
@@ -180,27 +128,16 @@ struct LayerIn {
 // exponential of its own.  The check is bit-exact and per wave, so arbitrary caller-supplied tau
 // planes still take the direct exp(-tau/u0).
 // FAST: the reference's default options (config.json: quadrature coefficients, TTHG_ray single
-// scattering with frac_c = 2, N=2 multiple scattering) in the symmetric zero-phase geometry
-// (cos_theta = 1), fixed at compile time: no option branches in the layer loop and the option values
-// leave the SGPR file (the generic 5-angle kernel spills 49 SGPRs to VGPR lanes, this one 23).
-// NC: no cloud anywhere in this layer of the wave (ftau_cld == 0 in every lane, checked per wave by
-// the caller): every term that carries ftau_cld*cosb drops out.  The remaining operations are the
-// generic ones with fcg = +0 folded by hand (x + 0, x * 1 and fma(0, y, z) are exact), so the result
-// is bit-identical to the generic body on such a layer.
-// AF: the three wave-uniform shortcuts (cum_tau, eo_ok, same_dt) all hold on this layer, known at compile time
-// in this copy of the body: no per-angle branches and no fall-back exponentials in the instruction stream.  The
-// checks themselves cost nothing; the 3-4 wave-uniform branches per angle they fed did -- with the flags assumed
-// the five-angle launch ran 14 % faster and a one-wave-per-SIMD launch 20-27 % (branch bubbles with nothing to
-// hide them, basic blocks too small to schedule across).  Same operations as the general body takes when
-// the flags are true, so the bits do not change.
-// SDT (with AF): 1 = same_dt holds as well (the cloud-free copy), 2 = it does not (the usual cloud layer: delta-
-// scaled, so dtau_og != dtau and the two extra exponentials are always formed) -- both straight-line.
-// SX (PZ_REFL_SMALL_EXP, with NC, AF, SDT = 1 in the zero-phase kernels): every lane's |dtau| is at most a.dt_small, so
-// dtau * nl1 lies within +-1/2 for every angle of the launch and et is formed by fexp2_small -- fexp2 without its four
-// range-reduction instructions, the same bits (device_math.hpp).  e0 is et there; EP and the cloudy body's dtau_og
-// exponentials take other arguments and keep the general form.
-template <int NA, bool IS3D, bool ZP, bool FIRST, bool LAST, bool LDS, bool FAST = false, bool NC = false,
-          bool AF = false, int SDT = 1, int ZF = 0, bool SX = false>
+// scattering with frac_c = 2, N=2 multiple scattering) fixed at compile time -- with ZP also cos_theta = 1: no option
+// branches in the layer loop and the option values leave the SGPR file (the generic 5-angle kernel spills 49 SGPRs to
+// VGPR lanes, this one 23).
+// KIND: the copy of the body (above).
+// XT: S_T (the running exp(-tau/u1)) and S_XU (exp(-tau/u0)) are one number -- u0 == u1, both start at 1.0 (fexp2 of
+// 0 * nl1 = -0: rint -0, f = +0, fma(0, p, 1) = 1, ldexp(1, 0)), cum_tau holds by construction and every layer multiplies
+// both by et -- so S_XU alone is carried: five multiplies and ten VGPRs per layer in every copy of the body.  The
+// zero-phase default-options kernels that form the level sums themselves (reflected_toa_body's ZDRV).
+template <int NA, bool IS3D, bool ZP, bool FIRST, bool LAST, bool LDS, bool FAST = false, Body KIND = BODY_GENERAL,
+          bool XT = false>
 __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const LayerIn &L,
                                                 ReflState<NA, LDS> &S,
                                                 const ReflectedArgs::Angle (&g)[NA],
@@ -209,14 +146,16 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
 {
     // Every floating-point operation below is written out: contraction is off and each fused
     // multiply-add is an explicit fma().  With the compiler free to contract (hipcc's default) the
-    // template instantiations (angles per lane, FAST, NC, first/last layer) each got their own choice
+    // template instantiations (angles per lane, FAST, the body copy, first/last layer) each got their own choice
     // of fused operations and disagreed in the last bits (5e-12 relative between the one-angle and the
     // five-angle kernel): a column's result depended on how the launch was shaped.  Now it does not.
 #pragma clang fp contract(off)
-    constexpr bool XT = (ZF & ZF_XT) != 0, EOX = (ZF & ZF_EOX) != 0;
-    static_assert(!ZF || (FAST && ZP), "ZF: the zero-phase default-options kernels only");
-    static_assert(!EOX || (NC && AF && SDT == 1), "ZF_EOX: the cloud-free copy only");
-    static_assert(!SX || (FAST && ZP && NC && AF && SDT == 1), "SX: the cloud-free copy of the zero-phase default-options kernels only");
+    // what the copy knows: NC no cloud in the layer; AF cum_tau and eo_ok hold, and same_dt is as SDT says (1: holds,
+    // 2: does not); EOX eo is S_XU; SX small exponent arguments
+    constexpr bool NC = KIND >= BODY_CLEAR, AF = KIND != BODY_GENERAL, EOX = KIND >= BODY_CLEAR_TOP;
+    constexpr bool SX = KIND == BODY_CLEAR_TOP_SMALL;
+    constexpr int SDT = KIND == BODY_CLOUD ? 2 : 1;
+    static_assert(!(XT || EOX) || (FAST && ZP), "XT, BODY_CLEAR_TOP*: the zero-phase default-options kernels only");
     const int tc = FAST ? 0 : tc_;
     const int single_phase = FAST ? 3 : a.single_phase;
     const int multi_phase = FAST ? 0 : a.multi_phase;
@@ -230,16 +169,11 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     else toon_gammas(tc, w0, fcg, g1, g2, lam, lam2);
     const double E = fmin(lam * dt, clip);
     const double EP = fexp2(E * -NEG_LOG2E, K);
-#if PZ_REFL_DIET
     // 1/g2 and 1/EP from one reciprocal (g2 of order w0 <= 1, EP <= e^35: the product stays in range; g2 = 0 -- a layer
-    // that does not scatter -- is NaN in Gamma here as in round 4 and in the reference's (g1 - lamda)/g2, fluxes.py:1141)
+    // that does not scatter -- is NaN in Gamma here as in the reference's (g1 - lamda)/g2, fluxes.py:1141)
     const double r_ge = frcp(g2 * EP);
     const double ig2 = r_ge * EP, EM = r_ge * g2;
     const double gam = (g1 - lam) * ig2;
-#else
-    const double gam = (g1 - lam) * frcp(g2);
-    const double EM = frcp(EP);
-#endif
     // No cloud anywhere in this layer of the wave (ftau_cld == 0 in every lane, checked per wave):
     // TTHG_ray's p_single = ftau_cld tthg + ftau_ray 3/4 (1 + cos^2) is its Rayleigh part alone
     // (bit-identical: 0 * tthg + x = x), without the two Henyey-Greenstein terms.
@@ -265,8 +199,8 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     const double c15 = NC ? 0.0 : 1.5 * fcg;
     const double gp = 1.0 + gam;
     const double gmc = NC ? 0.0 : (1.0 - gam) * c15;
-    const double w2gp = w2pi * gp, w2gmc = NC ? 0.0 : w2pi * gmc;      // PZ_REFL_DIET (2)
-    const double w2A0 = w2pi * A0;                                    // PZ_REFL_DIET (3)
+    const double w2gp = w2pi * gp, w2gmc = NC ? 0.0 : w2pi * gmc;      // common factors of the two mode integrals
+    const double w2A0 = w2pi * A0;                                    // ... and of the undelta-scaled layer source
 
     // ---- elimination factors shared by all angles ----
     double a1i = 0.0, a2i = 0.0, ia = 0.0, rho_n = gam, sfac = 0.0;
@@ -289,7 +223,13 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     // (lu_k + 1).  Every factor is itself good to 1 ulp (lm1 is exact by Sterbenz near the lambda u1 = 1
     // singularity), so the results stay within a few ulp -- which matters: at lambda u1 -> 1 the
     // particular and homogeneous parts cancel with an amplification ~1/|lambda u1 - 1|.
-    // (PZ_REFL_BATCH_RCP: all angles from one reciprocal of the running product, see the macro.)
+    // The reciprocal takes ONE Newton step (frcp1, 2^-46): it is a common factor of every beam term of the layer and of
+    // the mode integrals, so its error scales the layer's particular solution and the homogeneous response to it alike
+    // (device_math.hpp; bounded by tools/headline_error_x87.py and tests/test_refl_coop_gpu.py).
+    // One per angle, not one for all angles of the layer by batch inversion of their running product (-1.3 % time at five
+    // angles): an angle's result would then depend, in its last bits, on which angles share its lane -- on the angle
+    // chunking and on whether a small wavelength shard takes the one-angle-per-wave path.  As it is, a column's result
+    // is bit-identical however the grid is sharded and the angles are grouped; the multi-GPU path and its tests rely on it.
     double den_[NA], lm1_[NA], lp1_[NA], lml_[NA], r3_[NA];
     {
         double q[NA], P[NA];
@@ -301,20 +241,13 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
             lp1_[k] = lu + 1.0;
             lml_[k] = lm1_[k] * lp1_[k];
             q[k] = den_[k] * lml_[k];
+            // The running product that batch inversion would invert.  Nothing reads it and no instruction comes of it, but
+            // without this line hipcc allocates registers differently in the 58 FAST kernels of three and more angles;
+            // it stays until a change that may move the ISA takes it out.
             P[k] = (k == 0) ? q[0] : P[k - 1] * q[k];
         }
-#if PZ_REFL_BATCH_RCP
-        double R = frcp(P[NA - 1]);
 #pragma unroll
-        for (int k = NA - 1; k > 0; --k) {
-            r3_[k] = R * P[k - 1];
-            R = R * q[k];
-        }
-        r3_[0] = R;
-#else
-#pragma unroll
-        for (int k = 0; k < NA; ++k) r3_[k] = PZ_REFL_DIET ? frcp1(q[k]) : frcp(q[k]);
-#endif
+        for (int k = 0; k < NA; ++k) r3_[k] = frcp1(q[k]);
     }
 
 #pragma unroll
@@ -337,7 +270,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
         const double fx = fw * xu;
         const double cmu = am2 * fx, cpu = ap2 * fx;       // c-/c+ at the top of the layer
         double cmd, cpd;                                   // ... and at the bottom
-        if (PZ_REFL_DIET && (AF || L.cum_tau)) {           // xd = xu e0: the bottom terms are the top ones times e0
+        if (AF || L.cum_tau) {                             // xd = xu e0: the bottom terms are the top ones times e0
             cmd = cmu * e0;
             cpd = cpu * e0;
         } else {
@@ -351,19 +284,12 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
         const double h15 = NC ? 0.0 : c15 * u1_k;
         const double Aqq = NC ? B0 * A0 : fma(B0, A0, -(h15 * hz));       // (mpl c+ + mmi c-) / (2 fx)
         const double ee = fma(EP, et, -1.0), ff = fma(-EM, et, 1.0);
-        double vp, vn;
-        if (PZ_REFL_DIET) {
-            // (x + 0 = x - 0 = x exactly: the cloud-free copy and the general body agree bit for bit on a layer without cloud)
-            const double Trd = Tk * rd, wX = w2gp * B0;
-            const double wY = NC ? 0.0 : w2gmc * u1_k;
-            vp = ((Trd * (NC ? wX : wX + wY)) * lp1) * ee;
-            vn = ((Trd * (NC ? wX : wX - wY)) * lm1) * ff;
-        } else {
-            const double X = gp * B0, Y = NC ? 0.0 : gmc * u1_k;
-            const double Tw = Tk * w2pi, Trd = Tw * rd;
-            vp = (Trd * lp1) * ((NC ? X : X + Y) * ee);
-            vn = (Trd * lm1) * ((NC ? X : X - Y) * ff);
-        }
+        // the two mode integrals, their common factors T/(lu^2 - 1) w0/2pi (1 + Gamma) B0 multiplied once
+        // (x + 0 = x - 0 = x exactly: the cloud-free copies and the general body agree bit for bit on a layer without cloud)
+        const double Trd = Tk * rd, wX = w2gp * B0;
+        const double wY = NC ? 0.0 : w2gmc * u1_k;
+        double vp = ((Trd * (NC ? wX : wX + wY)) * lp1) * ee;
+        double vn = ((Trd * (NC ? wX : wX - wY)) * lm1) * ff;
         // exp(-tau_og[i]/u0): the running product of the layers above when tau_og really is the
         // running sum of dtau_og, else formed directly
         const double eo = EOX ? xu : (!FIRST && (AF || L.eo_ok)) ? S.get(S_EO, k) : fexp2_cold(L.tauo * nl0_k, K);
@@ -379,7 +305,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
         if (!LAST && !EOX) S.set(S_EO, k, eo * e0o);
         // S0 = (ssa eo t1 + Aq t2) u0/(u0+u1) with Aq = 2 w2pi fx Aqq; wq2 = 2 u0/(u0+u1) (1 if ZP)
         double S0;
-        if (PZ_REFL_DIET && ZP && (NC || L.nocld) && (AF ? (SDT != 2) : L.same_dt)) {
+        if (ZP && (NC || L.nocld) && (AF ? (SDT != 2) : L.same_dt)) {
             // t1 == t2 and Aqq = B0 A0 (no cloud: the general body's h15 hz is +0): S0 = t2 (ssa eo + (w0/2pi A0) (B0 fx))
             S0 = fma(w2A0, B0 * fx, ssa_h * eo) * t2;
         } else {
@@ -417,11 +343,6 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     S.pEM = EM;
 }
 
-// One or two angles per lane (the 3-D facet kernel, angle tails) need far fewer registers: ask for
-// more waves per SIMD there, the HBM-bound case lives on memory-level parallelism.
-#ifndef PZ_REFL_MINWAVES_FEW
-#define PZ_REFL_MINWAVES_FEW 2
-#endif
 // albedo + xint*gweight*tweight in the reference's operation order, unfused (disco.py:145-146), so the
 // fused disk sum, k_compress and numpy agree bit for bit
 __device__ __forceinline__ double disk_accumulate(double acc, double x, double gw, double tw)
@@ -437,14 +358,48 @@ __device__ __forceinline__ double disk_finish(double c1, double acc, double F, d
     return c1 * acc / F * (cos_theta + 1.0);
 }
 
+// The kernel body.  `bx_in` = this workgroup's column group within its spectrum, `by_in` = its angle group,
+// `angp` = the angle table (the kernel argument's, or the batch entry's).
 // BIG: one wave per SIMD (grids of up to 1 024 column-waves, five angles): the whole 512-entry register file
 // belongs to the wave, so the sweep state stays in registers instead of LDS -- 50 000 columns 0.1365 ms against
 // 0.1636 (round-2 sweep), same bits.  Of no use to the 1e5-column launch: its 1 563 waves need
 // two per SIMD.
-// DRV (3-D only): some planes are NULL and re-derived in the kernel (see below); the full-plane 3-D launch keeps
-// the branch-free load sequence (the conditional loads cost the HBM-bound facet kernel 7 %)
-// The kernel body.  `bx_in` = this workgroup's column group within its spectrum, `by_in` = its angle group,
-// `angp` = the angle table (the kernel argument's, or the batch entry's).
+// DRV: which planes exist.  Planes that compute_opacity derives exactly from others may be left out (NULL) and are
+// re-derived here with the same operations instead of being written to and read from HBM --
+//   tau / tau_og   : running sums of dtau / dtau_og from 0 at the top (optics.py:353-354, 418-420)
+//   gcos2          : 0.5 ftau_ray (optics.py:342)
+//   ftau_cld (with cosb, cosb_og, ftau_ray, gcos2): column without cloud: 0, 0, 0, 1, 0.5 (optics.py:335-342
+//                    with TAUCLD = 0)
+//   dtau_og / w0_og: no delta-scaling (cosb = 0: f = 0, optics.py:412-420 reduce to x*1): dtau / w0
+// all wave-uniform (kernel arguments).  The 3-D entry point and the 1-D default-options launches take these patterns (the
+// product leaves tau / tau_og / gcos2 -- and for a cloud-free atmosphere everything but dtau and w0 -- out of HBM; a 1-D
+// caller asks picaso_reflected_1d_can_derive first); every other 1-D launch is handed all eleven planes.
+//   0  all eleven planes, the branch-free load sequence (the conditional loads cost the HBM-bound facet kernel 7 %).
+//   1  any pattern of the above, looked up per plane at run time.
+//   2  ("CLEAR") ONLY dtau and w0 exist -- the pattern of an atmosphere without cloud -- known at compile time: no flag, no
+//      test and no copy of the body but the cloud-free ones survive.
+//   3  ("LEVELS") the other pattern of the product (a cloudy atmosphere): tau, tau_og and gcos2 left out, the cloud planes
+//      present -- known at compile time, so the two tests of "the level depths are the running sums" (they are: they are
+//      formed here), the exec-mask tests and the branches behind them disappear from every layer.
+//   4  ("LAYERS") 3 plus what a seal knows about the layers (planeseal.hip): bit i of a.lmask says that layer i carries no
+//      cloud in ANY column of the set -- ftau_cld = 0, ftau_ray = 1, dtau_og = dtau, w0_og = w0, bit for bit.  Such a layer
+//      is read and prepared as 2 does it (dtau and w0 alone, the constants put in, no vote, straight to a cloud-free copy
+//      of the body); every other layer is 3 unchanged.  The values put in ARE the stored ones and the votes would have
+//      passed, so the same copy of the body runs on the same numbers.
+//
+// The sweep.  The first and the last layer are peeled out.  Kernels with one, two or (FAST, ZP) five angles per lane
+// prefetch into two register sets used alternately and sweep the interior two layers per trip, in up to three loops:
+//   * the masked loop -- every kernel: per layer the mask test (DRV = 4), prep's votes and the choice between
+//     BODY_CLEAR, BODY_CLOUD and BODY_GENERAL (FAST; the generic kernels have the general body alone);
+//   * the top-run loop -- TOPRUN kernels: the run of known cloud-free layers from the top (DRV = 2: the whole column,
+//     DRV = 4: by the mask) loads two planes per layer without looking at the mask, waits for them by count and runs
+//     BODY_CLEAR_TOP.  It starts in its small-argument form (BODY_CLEAR_TOP_SMALL, a trip of two layers is 758 VALU
+//     instructions against 793) and leaves that for good at the first trip with a layer that fails the vote.  Where the
+//     run ends S_EO is set from S_XU once;
+//   * the deck-run loop -- DECKRUN kernels: every maximal run of known cloud-free interior layers BELOW the top run
+//     (under a cloud deck) is swept like the top run, by BODY_CLEAR, which keeps S_EO; the masked loop's mask test,
+//     vmcnt(0) and dispatch block around each such layer (15-22 VALU) go.
+// The other angle counts keep one prefetch set, a copy per layer and the masked loop's dispatch.
 template <int NA, bool IS3D, bool ZP, bool FAST, bool BIG, int DRV, typename AnglePtr>
 __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const unsigned bx_in, const unsigned by_in,
                                                    AnglePtr angp)
@@ -494,47 +449,23 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
                  *p_fr = a.ftau_ray + col, *p_dto = a.dtau_og + col, *p_tauo = a.tau_og + col,
                  *p_w0o = a.w0_og + col, *p_cbo = a.cosb_og + col;
 
-#ifndef PZ_REFL_LDS_MIN
-#define PZ_REFL_LDS_MIN 4
-#endif
-    constexpr bool LDS = (NA >= PZ_REFL_LDS_MIN) && !IS3D && !BIG;
+    constexpr bool LDS = (NA >= LDS_MIN_ANGLES) && !IS3D && !BIG;
     __shared__ double lds_state[LDS ? (PZ_REFL_NLDS > 0 ? PZ_REFL_NLDS : 1) * NA * PZ_REFL_BLOCK : 1];
     ReflState<NA, LDS> S;
     S.lds = lds_state + threadIdx.x;
     S.rho = S.pgam = S.pEM = 0.0;
-    // 3-D entry point: planes that compute_opacity derives exactly from others may be left out (NULL) and
-    // are re-derived here with the same operations instead of being written to and read from HBM --
-    //   tau / tau_og   : running sums of dtau / dtau_og from 0 at the top (optics.py:353-354, 418-420)
-    //   gcos2          : 0.5 ftau_ray (optics.py:342)
-    //   ftau_cld (with cosb, cosb_og, ftau_ray, gcos2): column without cloud: 0, 0, 0, 1, 0.5 (optics.py:335-342
-    //                    with TAUCLD = 0)
-    //   dtau_og / w0_og: no delta-scaling (cosb = 0: f = 0, optics.py:412-420 reduce to x*1): dtau / w0
-    // all wave-uniform (kernel arguments).  The 1-D default-options launches take the same patterns (round 4: the product
-    // leaves tau / tau_og / gcos2 -- and for a cloud-free atmosphere everything but dtau and w0 -- out of HBM; the caller
-    // asks picaso_reflected_1d_can_derive first); every other 1-D launch is handed all eleven planes
-    // DRV = 2 (1-D default options): the launcher saw that ONLY dtau and w0 exist -- the pattern of an atmosphere without
-    // cloud -- and says so at compile time: no flag, no test and no second copy of the layer body survive in this variant
-    // DRV = 3: the other pattern of the product (a cloudy atmosphere): tau, tau_og and gcos2 left out, the cloud planes
-    // present -- known at compile time, so the two tests of "the level depths are the running sums" (they are: they are
-    // formed here), the exec-mask tests and the branches behind them disappear from every layer (timing build of the
-    // eleven-plane kernel with those two tests compiled out: 0.223 -> 0.207 ms)
-    // DRV = 4 ("LAYERS"): DRV = 3 plus what a seal knows about the layers (planeseal.hip): bit i of a.lmask says that
-    // layer i carries no cloud in ANY column of the set -- ftau_cld = 0, ftau_ray = 1, dtau_og = dtau, w0_og = w0, bit for
-    // bit.  Such a layer is read and prepared as DRV = 2 does it (dtau and w0 alone, the constants put in, no vote, straight
-    // to the cloud-free copy of the body); every other layer is DRV = 3 unchanged.  The values put in ARE the stored ones
-    // and the votes would have passed, so the same copy of the body runs on the same numbers.
     constexpr bool CLEAR = (DRV == 2), LAYERS = (DRV == 4), LEVELS = (DRV == 3) || LAYERS;
-    // the kernels PZ_REFL_MERGE_XT and its companions apply to (see the macros): cum_tau holds by construction, u0 == u1
+    // the zero-phase default-options kernels that form the level sums themselves: cum_tau holds by construction and
+    // u0 == u1, so S_XU stands for S_T in every copy of the body (reflected_layer's XT)
     constexpr bool ZDRV = FAST && ZP && !IS3D && (CLEAR || LEVELS);
-    constexpr int ZX = (ZDRV && PZ_REFL_MERGE_XT) ? ZF_XT : 0;
-    constexpr bool TOPRUN = ZDRV && (CLEAR || LAYERS) && PZ_REFL_TOPRUN;
-    constexpr bool DECKRUN = ZDRV && LAYERS && TOPRUN && PZ_REFL_RUNS;                     // run loops below the top run
-    constexpr bool SMALLX = ZDRV && (PZ_REFL_SMALL_EXP & 1) && TOPRUN;                    // the loop of the top run
-    constexpr bool SMALLM = ZDRV && (PZ_REFL_SMALL_EXP & 2) && PZ_REFL_NOCLD_BODY;        // the copy of the masked loop
+    constexpr bool TOPRUN = ZDRV && (CLEAR || LAYERS);     // cloud-free layers are known before they are loaded: run loops
+    constexpr bool DECKRUN = ZDRV && LAYERS;               // ... below the top run as well
+    // a first / last layer known to be cloud-free takes a straight-line cloud-free copy of the body.  The last layer of the
+    // DRV = 4 kernels does not: a third and fourth copy of it beside the general ones gave them a private segment
+    constexpr bool CLEAR_FIRST = TOPRUN, CLEAR_LAST = ZDRV && CLEAR;
     const double dt_small = a.dt_small;
     // wave-uniform; a NaN fails it
-    auto small_dt = [&](double dt) -> bool { return (SMALLX || SMALLM) && __all(__builtin_fabs(dt) <= dt_small); };
-    constexpr int CLEAR_ENDS = !ZDRV ? 0 : CLEAR ? PZ_REFL_CLEAR_ENDS : LAYERS ? (PZ_REFL_CLEAR_ENDS & PZ_REFL_CLEAR_ENDS_LAYERS) : 0;
+    auto small_dt = [&](double dt) -> bool { return __all(__builtin_fabs(dt) <= dt_small); };
     // the mask, read once
     unsigned long long m0 = 0, m1 = 0;
     if constexpr (LAYERS) {
@@ -560,8 +491,8 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         S.set(S_D1, k, 0.0);
         S.set(S_D2, k, 0.0);
         S.set(S_EO, k, 0.0);
-        // ZX: tau_i is +0.0, the product -0.0 and fexp2 of it exactly 1.0 (see PZ_REFL_MERGE_XT)
-        S.set(S_XU, k, ZX ? 1.0 : fexp2(mul_unfused(tau_i, ZP ? g[k].nl1 : g[k].nl0), K));
+        // ZDRV: tau_i is +0.0, the product -0.0 and fexp2 of it exactly 1.0 (see reflected_layer's XT)
+        S.set(S_XU, k, ZDRV ? 1.0 : fexp2(mul_unfused(tau_i, ZP ? g[k].nl1 : g[k].nl0), K));
     }
 
     // Software prefetch with two register sets used alternately (loop unrolled by two): the eleven
@@ -569,14 +500,15 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     // between the sets, so they stay in flight for a whole layer (a copy would force the wave to
     // drain vmcnt at the end of every layer, which costs the HBM-bound facet kernel ~25 %).
     // FAST: planes addressed as (uniform base) + (32-bit lane offset): one v_add_u32 per layer for all
-    // eleven loads (global_load ... saddr) instead of eleven 64-bit lane address adds (-2.5 % time)
+    // eleven loads (global_load ... saddr) instead of eleven 64-bit lane address adds (-2.5 % time); the launcher
+    // checks that a plane is smaller than 4 GB
     const unsigned voff0 = (unsigned)(col * 8);
     const unsigned pitch8 = (unsigned)(pitch * 8);
     auto ld = [&](const double *base, unsigned off) {
         return *(const double *)((const char *)base + off);
     };
     auto load = [&](LayerIn &L, int i, bool in_loop = false) {
-        if constexpr (FAST && PZ_REFL_SADDR && DRV) {      // 1-D with planes left out: only what exists is loaded
+        if constexpr (FAST && DRV) {               // planes left out: only what exists is loaded
             const unsigned o = voff0 + (unsigned)i * pitch8;
             if constexpr (LAYERS) {
                 // The number of loads now differs from layer to layer, and a wait for the OTHER register set counted in
@@ -615,7 +547,7 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
             if (!derive_tauo) L.tauo = ld(a.tau_og, o);
             return;
         }
-        if constexpr (FAST && PZ_REFL_SADDR) {
+        if constexpr (FAST) {
             const unsigned o = voff0 + (unsigned)i * pitch8;
             L.dt = ld(a.dtau, o);
             L.tau_n = ld(a.tau + pitch, o);
@@ -700,60 +632,49 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         tau_i = L.tau_n;
         tauo_pred = L.tauo + L.dto;
     };
+    // one layer by one copy of the body
+#define PZ_BODY(FIRST_, LAST_, KIND_, L_) \
+    reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, KIND_, ZDRV>(a, L_, S, g, K, F, clip, tc, b_top)
+    // a layer of the masked loop, and the first and the last layer: whichever copy the mask and prep's votes allow
 #define PZ_LAYER(FIRST_, LAST_, L_, I_)                                                                  \
     do {                                                                                                 \
         const bool lclear_ = layer_clear(I_);                                                            \
         prep(L_, lclear_);                                                                               \
-        /* a first / last layer known to be cloud-free (the seal's mask, DRV = 2): the straight-line copy, if PZ_REFL_CLEAR_ENDS says so */ \
-        constexpr bool kcopy_ = PZ_REFL_NOCLD_BODY && ZDRV && ((FIRST_) || (LAST_)) &&                   \
-                                (!(FIRST_) || (CLEAR_ENDS & 1)) && (!(LAST_) || (CLEAR_ENDS & 2));       \
-        constexpr int kzf_ = kcopy_ ? (ZX | ((FIRST_) ? ZF_EOX : 0)) : 0;                                \
-        if (kcopy_ && (CLEAR || lclear_))                                                                \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, kcopy_, kcopy_, 1, kzf_>(a, L_, S, g, K, F, clip, tc, b_top); \
-        else if (SMALLM && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf && small_dt(L_.dt))              \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, SMALLM, SMALLM, 1, SMALLM ? ZX : 0, SMALLM>(a, L_, S, g, K, F, clip, tc, b_top); \
-        else if (PZ_REFL_NOCLD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.nocld && L_.allf)             \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, true, true, 1, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
-        else if (PZ_REFL_CLOUD_BODY && FAST && !(FIRST_) && !(LAST_) && L_.af_cloud)                      \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, false, true, 2, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
+        constexpr bool interior_ = !(FIRST_) && !(LAST_);                                                \
+        /* a first / last layer known to be cloud-free (the seal's mask, DRV = 2): the straight-line copy; nothing */ \
+        /* above the first layer is delta-scaled */                                                      \
+        constexpr bool kend_ = !interior_ && (!(FIRST_) || CLEAR_FIRST) && (!(LAST_) || CLEAR_LAST);      \
+        constexpr Body kcopy_ = !kend_ ? BODY_GENERAL : (FIRST_) ? BODY_CLEAR_TOP : BODY_CLEAR;          \
+        if (kend_ && (CLEAR || lclear_))                                                                 \
+            PZ_BODY(FIRST_, LAST_, kcopy_, L_);                                                          \
+        else if (FAST && interior_ && L_.nocld && L_.allf)                                               \
+            PZ_BODY(FIRST_, LAST_, BODY_CLEAR, L_);                                                      \
+        else if (FAST && interior_ && L_.af_cloud)                                                       \
+            PZ_BODY(FIRST_, LAST_, BODY_CLOUD, L_);                                                      \
         else                                                                                             \
-            reflected_layer<NA, IS3D, ZP, FIRST_, LAST_, LDS, FAST, false, false, 1, ZX>(a, L_, S, g, K, F, clip, tc, b_top); \
+            PZ_BODY(FIRST_, LAST_, BODY_GENERAL, L_);                                                    \
         if constexpr (CLEAR) __builtin_amdgcn_sched_barrier(0);   /* straight-line code: keep the layers apart */ \
     } while (0)
-    // a layer of the clear run from the top: known cloud-free, nothing above it delta-scaled
-#define PZ_RUN_LAYER(L_, SX_)                                                                            \
+    // a layer of a run (TOPRUN / DECKRUN kernels): known cloud-free, KIND_ as the loop says
+#define PZ_RUN_LAYER(KIND_, L_)                                                                          \
     do {                                                                                                 \
         prep(L_, true);                                                                                  \
-        reflected_layer<NA, IS3D, ZP, false, false, LDS, FAST, TOPRUN, TOPRUN, 1, TOPRUN ? (ZX | ZF_EOX) : 0, TOPRUN && (SX_)>(a, L_, S, g, K, F, clip, tc, b_top); \
+        PZ_BODY(false, false, KIND_, L_);                                                                \
         __builtin_amdgcn_sched_barrier(0);                                                               \
     } while (0)
 
-    // a layer of a clear run below the top run: known cloud-free, S_EO kept
-#define PZ_DECK_LAYER(L_)                                                                                \
-    do {                                                                                                 \
-        prep(L_, true);                                                                                  \
-        reflected_layer<NA, IS3D, ZP, false, false, LDS, FAST, DECKRUN, DECKRUN, 1, DECKRUN ? ZX : 0>(a, L_, S, g, K, F, clip, tc, b_top); \
-        __builtin_amdgcn_sched_barrier(0);                                                               \
-    } while (0)
-
-    // Two register sets used alternately (no copy) for one or two angles per lane -- the HBM-bound 3-D facet
-    // kernel -- and for five: there the eleven v_mov_b64 of the copy are 2.3 % of the launch (0.2357 ->
-    // 0.2302 ms, same box, no spills at 254 VGPRs).  Three angles spill with a second set (14 VGPRs), four
-    // and six to eight (chunked launches, rarely used) are left on the copying form.  (Early in round 1 the
-    // second set made the five-angle kernel spill: 0.98 ms vs 0.36 ms; the state has since moved to LDS.)
-#ifndef PZ_REFL_TWOSETS_5
-#define PZ_REFL_TWOSETS_5 1
-#endif
-#ifndef PZ_REFL_TWOSETS_NONZP
-#define PZ_REFL_TWOSETS_NONZP 0
-#endif
     // a layer of a run: dtau and w0 alone
     auto load_clear = [&](LayerIn &L, int l) {
         const unsigned o = voff0 + (unsigned)l * pitch8;
         L.dt = ld(a.dtau, o);
         L.w0 = ld(a.w0, o);
     };
-    constexpr bool TWO_SETS = (NA <= 2) || (PZ_REFL_TWOSETS_5 && NA == 5 && FAST && (ZP || PZ_REFL_TWOSETS_NONZP));   // generic five-angle kernel: 30 VGPRs spilled with it
+    // Two register sets used alternately (no copy) for one or two angles per lane -- the HBM-bound 3-D facet
+    // kernel -- and for five in the zero-phase default-options kernels: there the eleven v_mov_b64 of the copy are
+    // 2.3 % of the launch (0.2357 -> 0.2302 ms, same box, no spills at 254 VGPRs).  Three angles spill with a second
+    // set (14 VGPRs), the generic five-angle kernel spills 30; four and six to eight (chunked launches, rarely used)
+    // are left on the copying form.
+    constexpr bool TWO_SETS = (NA <= 2) || (NA == 5 && FAST && ZP);
     LayerIn A, B;
     load(A, 0);
     if (n == 1) {
@@ -762,7 +683,7 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         load(B, 1);
         PZ_LAYER(true, false, A, 0);
         int i = 1;                               // B holds layer i
-        if constexpr (TOPRUN || CLEAR_ENDS) {
+        if constexpr (TOPRUN) {
             // r: the number of cloud-free layers from the top (scalar bit operations on the mask; DRV = 2: all of them)
             int r = n;
             if constexpr (LAYERS) {
@@ -770,36 +691,32 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
                 r = r < n ? r : n;
             }
             if (r >= 1) {
-                if constexpr (TOPRUN) {
-                    // layers i, i+1 and the two prefetched ones (i+1, i+2) all belong to the run: two loads each, so the
-                    // compiler's own counted vmcnt waits do, and no mask is looked at
-                    if constexpr (SMALLX) {
-                        // The small-argument loop: a trip runs while both of its layers pass the vote, then the sweep
-                        // moves to the general loop below for the rest of the run and never comes back.  Both votes are
-                        // taken before the trip on values loaded a trip ago -- B, and dtau of layer i + 1 read one layer
-                        // further ahead than the rest of A (two more VGPRs) -- so the loop has one exit and each trip is
-                        // one straight-line block of two layers; the row index is clamped to the last layer of the planes.
-                        if (i + 2 < r) {
-                            double dt_a = ld(a.dtau, voff0 + (unsigned)(i + 1) * pitch8);
-                            bool go = small_dt(B.dt) && small_dt(dt_a);
-                            while (go) {
-                                A.dt = dt_a;
-                                A.w0 = ld(a.w0, voff0 + (unsigned)(i + 1) * pitch8);
-                                PZ_RUN_LAYER(B, true);
-                                load_clear(B, i + 2);
-                                dt_a = ld(a.dtau, voff0 + (unsigned)(i + 3 < n ? i + 3 : n - 1) * pitch8);
-                                PZ_RUN_LAYER(A, true);
-                                i += 2;
-                                go = i + 2 < r && small_dt(B.dt) && small_dt(dt_a);
-                            }
-                        }
-                    }
-                    for (; i + 2 < r; i += 2) {
-                        load_clear(A, i + 1);
-                        PZ_RUN_LAYER(B, false);
+                // The top-run loop.  Layers i, i+1 and the two prefetched ones (i+1, i+2) all belong to the run: two loads
+                // each, so the compiler's own counted vmcnt waits do, and no mask is looked at.
+                // Its small-argument form first: a trip runs while both of its layers pass the vote, then the sweep
+                // moves to the general form below for the rest of the run and never comes back.  Both votes are
+                // taken before the trip on values loaded a trip ago -- B, and dtau of layer i + 1 read one layer
+                // further ahead than the rest of A (two more VGPRs) -- so the loop has one exit and each trip is
+                // one straight-line block of two layers; the row index is clamped to the last layer of the planes.
+                if (i + 2 < r) {
+                    double dt_a = ld(a.dtau, voff0 + (unsigned)(i + 1) * pitch8);
+                    bool go = small_dt(B.dt) && small_dt(dt_a);
+                    while (go) {
+                        A.dt = dt_a;
+                        A.w0 = ld(a.w0, voff0 + (unsigned)(i + 1) * pitch8);
+                        PZ_RUN_LAYER(BODY_CLEAR_TOP_SMALL, B);
                         load_clear(B, i + 2);
-                        PZ_RUN_LAYER(A, false);
+                        dt_a = ld(a.dtau, voff0 + (unsigned)(i + 3 < n ? i + 3 : n - 1) * pitch8);
+                        PZ_RUN_LAYER(BODY_CLEAR_TOP_SMALL, A);
+                        i += 2;
+                        go = i + 2 < r && small_dt(B.dt) && small_dt(dt_a);
                     }
+                }
+                for (; i + 2 < r; i += 2) {
+                    load_clear(A, i + 1);
+                    PZ_RUN_LAYER(BODY_CLEAR_TOP, B);
+                    load_clear(B, i + 2);
+                    PZ_RUN_LAYER(BODY_CLEAR_TOP, A);
                 }
                 // the run ends here (the layers left of it, at most two, take the masked loop): from now on S_EO is kept.
                 // Layer 0 was cloud-free, so whichever copy of the body ran it, S_EO is S_XU at this point, bit for bit.
@@ -807,11 +724,11 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
                 for (int k = 0; k < NA; ++k) S.set(S_EO, k, S.get(S_XU, k));
             }
         }
-        for (; i + 2 <= n - 1; i += 2) {         // layers i and i+1 are interior, layer i+2 exists
+        for (; i + 2 <= n - 1; i += 2) {         // the masked loop: layers i and i+1 are interior, layer i+2 exists
             if constexpr (DECKRUN) {
-                // A run of sealed cloud-free interior layers below the top run (under a cloud deck, between two): swept
-                // like the top run -- two loads per layer under the compiler's counted waits, no mask test, no dispatch --
-                // by the cloud-free copy of the body that keeps S_EO (a layer above was delta-scaled, so S_EO is not S_XU).
+                // The deck-run loop: a run of sealed cloud-free interior layers below the top run (under a cloud deck, between
+                // two) is swept like the top run -- two loads per layer under the compiler's counted waits, no mask test, no
+                // dispatch -- by BODY_CLEAR, which keeps S_EO (a layer above was delta-scaled, so S_EO is not S_XU).
                 // e: one past the run that starts at layer i (scalar bit operations on the mask), the last layer left out.
                 const unsigned long long w = i < 64 ? (m0 >> i) | (i ? m1 << (64 - i) : 0ull) : m1 >> (i - 64);
                 int e = i + ((~w) ? __builtin_ctzll(~w) : 64);
@@ -820,9 +737,9 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
                     // as in the top run: layers i .. i + 2 belong to the run, B holds layer i on the way in and out
                     for (; i + 2 < e; i += 2) {
                         load_clear(A, i + 1);
-                        PZ_DECK_LAYER(B);
+                        PZ_RUN_LAYER(BODY_CLEAR, B);
                         load_clear(B, i + 2);
-                        PZ_DECK_LAYER(A);
+                        PZ_RUN_LAYER(BODY_CLEAR, A);
                     }
                     if (!(i + 2 <= n - 1)) break;
                 }
@@ -852,7 +769,7 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     }
 #undef PZ_LAYER
 #undef PZ_RUN_LAYER
-#undef PZ_DECK_LAYER
+#undef PZ_BODY
 
     // ---- surface row (fluxes.py:178-183) and output ----
     // EP(1 - rs G) pos + EM(G - rs) neg = b_surface - c+dn + rs c-dn with neg = delta - rho pos,
@@ -903,7 +820,7 @@ __device__ __forceinline__ void xcd_decode(unsigned b, unsigned nrep, unsigned n
 }
 
 template <int NA, bool IS3D, bool ZP, bool FAST = false, bool BIG = false, int DRV = 0>
-__global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : NA <= 2 ? PZ_REFL_MINWAVES_FEW : PZ_REFL_MINWAVES)) void k_reflected_toa(const ReflectedArgs a)
+__global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : PZ_REFL_MINWAVES)) void k_reflected_toa(const ReflectedArgs a)
 {
     // Angle groups as separate workgroups (ny > 1): every group re-reads the eleven planes of its columns.
     // Consecutive workgroups go to consecutive XCDs (8, each with its own L2), so the launch is 1-D and, for
@@ -924,7 +841,7 @@ __global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : NA <= 2 ? PZ_REFL_MINWAVE
 // spectrum's planes, outputs and angle table in the device table a.batch.  A separate instantiation so that the
 // single-spectrum kernels keep their register allocation; same operations, same bits.
 template <int NA, bool IS3D, bool ZP, bool FAST = false, bool BIG = false, int DRV = 0>
-__global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : NA <= 2 ? PZ_REFL_MINWAVES_FEW : PZ_REFL_MINWAVES)) void k_reflected_toa_batch(const ReflectedArgs a)
+__global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : PZ_REFL_MINWAVES)) void k_reflected_toa_batch(const ReflectedArgs a)
 {
     unsigned spec, bx, by = 0;
     const unsigned ny = a.ny > 1 ? (unsigned)a.ny : 1u;
@@ -964,6 +881,16 @@ static bool fast_options(const ReflectedArgs &a, bool zp)
            a.frac_c == 2.0;
 }
 
+// Launches one kernel of the family: its batched form when the arguments carry a batch table, else the single-spectrum one.
+template <int NA, bool IS3D, bool ZP, bool FAST = false, bool BIG = false, int DRV = 0>
+static void launch_kernel(picaso_ctx *ctx, const dim3 grid, const ReflectedArgs &a)
+{
+    if (a.batch)
+        hipLaunchKernelGGL((k_reflected_toa_batch<NA, IS3D, ZP, FAST, BIG, DRV>), grid, dim3(PZ_REFL_BLOCK), 0, ctx->stream, a);
+    else
+        hipLaunchKernelGGL((k_reflected_toa<NA, IS3D, ZP, FAST, BIG, DRV>), grid, dim3(PZ_REFL_BLOCK), 0, ctx->stream, a);
+}
+
 template <int NA>
 static int launch1d(picaso_ctx *ctx, const ReflectedArgs &a_in)
 {
@@ -982,7 +909,6 @@ static int launch1d(picaso_ctx *ctx, const ReflectedArgs &a_in)
     if constexpr (NA == 5)
         big = a.ny <= 1 && (long)nspec * ncg * (block / 64) <= 1024 && getenv("PICASO_AMD_REFL_NO_BIG") == nullptr;
     bool fast = fast_options(a, zp);
-#define PZ_GO(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(block), 0, ctx->stream, a)
     // planes left out (re-derived in the kernel): the default-options kernels only -- reflected_1d_can_derive() is the
     // caller's way to know
     const bool drv = !(a.tau && a.tau_og && a.gcos2 && a.ftau_cld && a.dtau_og);
@@ -996,44 +922,24 @@ static int launch1d(picaso_ctx *ctx, const ReflectedArgs &a_in)
         }
         if (!fast) return fail(ctx, "reflected: planes may be left out only with the reference's default options");
         // only dtau and w0: the compile-time form (five angles, symmetric geometry: the shape of a spectrum() call)
-        const bool only2 = !a.tau && !a.tau_og && !a.gcos2 && !a.ftau_cld && !a.dtau_og && PZ_REFL_CLEAR_VARIANT;
-        const bool levels3 = !a.tau && !a.tau_og && !a.gcos2 && a.ftau_cld && a.dtau_og && PZ_REFL_LEVELS_VARIANT;
+        const bool only2 = !a.tau && !a.tau_og && !a.gcos2 && !a.ftau_cld && !a.dtau_og;
+        const bool levels3 = !a.tau && !a.tau_og && !a.gcos2 && a.ftau_cld && a.dtau_og;
         // the seal's clear-layer mask (api.hip asks for it): the fused five-angle shape only, never the BIG form
-        const bool layers4 = levels3 && a.use_lmask && PZ_REFL_LAYERS_VARIANT;
-        if (a.batch) {
-            if (zp && big) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, true, 1>)); }
-            else if (zp && layers4 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 4>)); }
-            else if (zp && only2 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 2>)); }
-            else if (zp && levels3 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 3>)); }
-            else if (zp) PZ_GO((k_reflected_toa_batch<NA, false, true, true, false, 1>));
-            else PZ_GO((k_reflected_toa_batch<NA, false, false, true, false, 1>));
-        } else if (zp && big) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, true, 1>)); }
-        else if (zp && layers4 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, false, 4>)); }
-        else if (zp && only2 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, false, 2>)); }
-        else if (zp && levels3 && NA == 5) { if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, false, 3>)); }
-        else if (zp) PZ_GO((k_reflected_toa<NA, false, true, true, false, 1>));
-        else PZ_GO((k_reflected_toa<NA, false, false, true, false, 1>));
+        const bool layers4 = levels3 && a.use_lmask;
+        if (zp && big) { if constexpr (NA == 5) launch_kernel<NA, false, true, true, true, 1>(ctx, grid, a); }
+        else if (zp && layers4 && NA == 5) { if constexpr (NA == 5) launch_kernel<NA, false, true, true, false, 4>(ctx, grid, a); }
+        else if (zp && only2 && NA == 5) { if constexpr (NA == 5) launch_kernel<NA, false, true, true, false, 2>(ctx, grid, a); }
+        else if (zp && levels3 && NA == 5) { if constexpr (NA == 5) launch_kernel<NA, false, true, true, false, 3>(ctx, grid, a); }
+        else if (zp) launch_kernel<NA, false, true, true, false, 1>(ctx, grid, a);
+        else launch_kernel<NA, false, false, true, false, 1>(ctx, grid, a);
         PZ_HIP(ctx, hipGetLastError());
         return 0;
     }
-    if (a.batch) {
-        if (zp && fast && big) {
-            if constexpr (NA == 5) PZ_GO((k_reflected_toa_batch<NA, false, true, true, true>));
-        } else if (zp && fast) PZ_GO((k_reflected_toa_batch<NA, false, true, true>));
-        else if (fast && PZ_REFL_FAST_NONZP) PZ_GO((k_reflected_toa_batch<NA, false, false, true>));
-        else if (zp) PZ_GO((k_reflected_toa_batch<NA, false, true>));
-        else PZ_GO((k_reflected_toa_batch<NA, false, false>));
-    } else if (zp && fast && big) {
-        if constexpr (NA == 5) PZ_GO((k_reflected_toa<NA, false, true, true, true>));
-    } else if (zp && fast)
-        PZ_GO((k_reflected_toa<NA, false, true, true>));
-    else if (fast && PZ_REFL_FAST_NONZP)        // default options at a non-zero phase angle
-        PZ_GO((k_reflected_toa<NA, false, false, true>));
-    else if (zp)
-        PZ_GO((k_reflected_toa<NA, false, true>));
-    else
-        PZ_GO((k_reflected_toa<NA, false, false>));
-#undef PZ_GO
+    if (zp && fast && big) { if constexpr (NA == 5) launch_kernel<NA, false, true, true, true>(ctx, grid, a); }
+    else if (zp && fast) launch_kernel<NA, false, true, true>(ctx, grid, a);
+    else if (fast) launch_kernel<NA, false, false, true>(ctx, grid, a);        // default options at a non-zero phase angle
+    else if (zp) launch_kernel<NA, false, true>(ctx, grid, a);
+    else launch_kernel<NA, false, false>(ctx, grid, a);
     PZ_HIP(ctx, hipGetLastError());
     return 0;
 }
@@ -1041,43 +947,27 @@ static int launch1d(picaso_ctx *ctx, const ReflectedArgs &a_in)
 int launch_reflected_toa(picaso_ctx *ctx, const ReflectedArgs &a, bool is3d)
 {
     if (a.ncol <= 0 || a.nlayer < 1) return fail(ctx, "reflected: empty problem");
-    // 3-D: the reference's default options (TTHG_ray, N = 2, frac_c = 2; 3-D is quadrature-only anyway) fixed at compile
-    // time like the 1-D launches, and with them the two plane patterns of the product known at compile time as well --
-    // only dtau and w0 (a map without cloud), or everything but tau / tau_og / gcos2 (cloud tables): same bits as the
-    // generic instantiations (PICASO_AMD_REFL3D_GENERIC=1), which every other option set and plane pattern keeps
-    const bool all3 = a.tau && a.tau_og && a.gcos2 && a.ftau_cld && a.dtau_og;
-    const bool fast3 = is3d && a.single_phase == 3 && a.multi_phase == 0 && a.frac_c == 2.0 &&
-                       (double)a.pitch * (a.nlayer + 1) * 8.0 < 4294967296.0 && !getenv("PICASO_AMD_REFL3D_GENERIC");
-    const bool only2_3 = !a.tau && !a.tau_og && !a.gcos2 && !a.ftau_cld && !a.dtau_og;
-    const bool levels3_3 = !a.tau && !a.tau_og && !a.gcos2 && a.ftau_cld && a.dtau_og;
-    if (is3d && a.batch) {                         // a.tau etc.: the presence pattern of EVERY spectrum's planes
-        const int block = PZ_REFL_BLOCK;
-        ReflectedArgs b = a;
-        b.bps = (unsigned)((a.ncol + block - 1) / block);
-        b.batch_interleave = 0;
-        const dim3 grid(b.bps * (unsigned)a.nspec);
-#define PZ_GO3(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(block), 0, ctx->stream, b)
-        if (fast3 && all3) PZ_GO3((k_reflected_toa_batch<1, true, false, true, false, 0>));
-        else if (fast3 && only2_3) PZ_GO3((k_reflected_toa_batch<1, true, false, true, false, 2>));
-        else if (fast3 && levels3_3) PZ_GO3((k_reflected_toa_batch<1, true, false, true, false, 3>));
-        else if (fast3) PZ_GO3((k_reflected_toa_batch<1, true, false, true, false, 1>));
-        else if (all3) PZ_GO3((k_reflected_toa_batch<1, true, false>));
-        else PZ_GO3((k_reflected_toa_batch<1, true, false, false, false, 1>));
-#undef PZ_GO3
-        PZ_HIP(ctx, hipGetLastError());
-        return 0;
-    }
     if (is3d) {
-        const int block = PZ_REFL_BLOCK;
-        const dim3 grid((unsigned)((a.ncol + block - 1) / block));
-#define PZ_GO3(KERNEL) hipLaunchKernelGGL(KERNEL, grid, dim3(block), 0, ctx->stream, a)
-        if (fast3 && all3) PZ_GO3((k_reflected_toa<1, true, false, true, false, 0>));
-        else if (fast3 && only2_3) PZ_GO3((k_reflected_toa<1, true, false, true, false, 2>));
-        else if (fast3 && levels3_3) PZ_GO3((k_reflected_toa<1, true, false, true, false, 3>));
-        else if (fast3) PZ_GO3((k_reflected_toa<1, true, false, true, false, 1>));
-        else if (all3) PZ_GO3((k_reflected_toa<1, true, false>));
-        else PZ_GO3((k_reflected_toa<1, true, false, false, false, 1>));
-#undef PZ_GO3
+        // 3-D: the reference's default options (TTHG_ray, N = 2, frac_c = 2; 3-D is quadrature-only anyway) fixed at compile
+        // time like the 1-D launches, and with them the two plane patterns of the product known at compile time as well --
+        // only dtau and w0 (a map without cloud), or everything but tau / tau_og / gcos2 (cloud tables): same bits as the
+        // generic instantiations (PICASO_AMD_REFL3D_GENERIC=1), which every other option set and plane pattern keeps.
+        // A batch: a.tau etc. are the presence pattern of EVERY spectrum's planes.
+        const bool all3 = a.tau && a.tau_og && a.gcos2 && a.ftau_cld && a.dtau_og;
+        const bool fast3 = a.single_phase == 3 && a.multi_phase == 0 && a.frac_c == 2.0 &&
+                           (double)a.pitch * (a.nlayer + 1) * 8.0 < 4294967296.0 && !getenv("PICASO_AMD_REFL3D_GENERIC");
+        const bool only2_3 = !a.tau && !a.tau_og && !a.gcos2 && !a.ftau_cld && !a.dtau_og;
+        const bool levels3_3 = !a.tau && !a.tau_og && !a.gcos2 && a.ftau_cld && a.dtau_og;
+        ReflectedArgs b = a;                        // (the single-spectrum kernels read neither of the two)
+        b.bps = (unsigned)((a.ncol + PZ_REFL_BLOCK - 1) / PZ_REFL_BLOCK);
+        b.batch_interleave = 0;
+        const dim3 grid(b.bps * (a.batch ? (unsigned)a.nspec : 1u));
+        if (fast3 && all3) launch_kernel<1, true, false, true, false, 0>(ctx, grid, b);
+        else if (fast3 && only2_3) launch_kernel<1, true, false, true, false, 2>(ctx, grid, b);
+        else if (fast3 && levels3_3) launch_kernel<1, true, false, true, false, 3>(ctx, grid, b);
+        else if (fast3) launch_kernel<1, true, false, true, false, 1>(ctx, grid, b);
+        else if (all3) launch_kernel<1, true, false>(ctx, grid, b);
+        else launch_kernel<1, true, false, false, false, 1>(ctx, grid, b);
         PZ_HIP(ctx, hipGetLastError());
         return 0;
     }

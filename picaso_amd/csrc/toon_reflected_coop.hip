@@ -101,7 +101,7 @@ __device__ __forceinline__ void frcp_n(const double (&b)[NA], double (&y)[NA])
     RC_FOR_K e[kk] = fma(-b[kk], y[kk], 1.0);
     RC_FOR_K y[kk] = fma(y[kk], e[kk], y[kk]);
 }
-// frcp1 (one Newton step, 2^-46) over NA arguments: the per-angle 1/(den (lu - 1)(lu + 1)) of PZ_REFL_DIET
+// frcp1 (one Newton step, 2^-46) over NA arguments: the per-angle 1/(den (lu - 1)(lu + 1)) of reflected_layer
 template <int NA>
 __device__ __forceinline__ void frcp1_n(const double (&b)[NA], double (&y)[NA])
 {
@@ -155,8 +155,7 @@ __device__ __forceinline__ void rc_angle(const double (*in)[64], const double (*
     RC_FOR_K lml[kk] = lm1[kk] * lp1[kk];
     RC_FOR_K q3[kk] = den[kk] * lml[kk];
     fexp2_n<NA>(targ, K, et);
-    if (PZ_REFL_DIET) frcp1_n<NA>(q3, r3);
-    else frcp_n<NA>(q3, r3);
+    frcp1_n<NA>(q3, r3);
     if (ZP) {
         RC_FOR_K e0[kk] = et[kk];
     } else {
@@ -178,10 +177,10 @@ __device__ __forceinline__ void rc_angle(const double (*in)[64], const double (*
     }
     RC_FOR_K fw[kk] = Fw0h * rden[kk];
     RC_FOR_K fx[kk] = fw[kk] * st[kk].XU;
-    double cmu[NA], cpu[NA], cmd[NA], cpd[NA], B0[NA], Aqq[NA], X[NA], Y[NA], Tw[NA], Trd[NA], ee[NA], ff[NA];
+    double cmu[NA], cpu[NA], cmd[NA], cpd[NA], B0[NA], Aqq[NA], X[NA], Y[NA], Trd[NA], ee[NA], ff[NA];
     RC_FOR_K cmu[kk] = am2[kk] * fx[kk];
     RC_FOR_K cpu[kk] = ap2[kk] * fx[kk];
-    if (PZ_REFL_DIET && cum_tau) {                      // reflected_layer, PZ_REFL_DIET (1)
+    if (cum_tau) {                                      // xd = xu e0: the bottom terms are the top ones times e0
         RC_FOR_K cmd[kk] = cmu[kk] * e0[kk];
         RC_FOR_K cpd[kk] = cpu[kk] * e0[kk];
     } else {
@@ -192,29 +191,19 @@ __device__ __forceinline__ void rc_angle(const double (*in)[64], const double (*
     RC_FOR_K B0[kk] = fma(gcq, g[kk].q2, 1.0);
     if (PLAIN) {
         RC_FOR_K Aqq[kk] = B0[kk] * A0;
-        RC_FOR_K Y[kk] = 0.0;
     } else {
         RC_FOR_K Aqq[kk] = fma(B0[kk], A0, -((c15 * g[kk].u1) * hz[kk]));
-        RC_FOR_K Y[kk] = gmc * g[kk].u1;
     }
     RC_FOR_K ee[kk] = fma(EP, et[kk], -1.0);
     RC_FOR_K ff[kk] = fma(-EM, et[kk], 1.0);
     double vp[NA], vn[NA], eo[NA], t2[NA], t1[NA], e0o[NA];
-    const double w2A0 = w2pi * A0;
-    if (PZ_REFL_DIET) {                                 // reflected_layer, PZ_REFL_DIET (2)
-        const double w2gp = w2pi * gp, w2gmc = PLAIN ? 0.0 : w2pi * gmc;
-        RC_FOR_K Trd[kk] = st[kk].T * rd[kk];
-        RC_FOR_K X[kk] = w2gp * B0[kk];
-        RC_FOR_K Y[kk] = PLAIN ? 0.0 : w2gmc * g[kk].u1;
-        RC_FOR_K vp[kk] = ((Trd[kk] * (PLAIN ? X[kk] : X[kk] + Y[kk])) * lp1[kk]) * ee[kk];
-        RC_FOR_K vn[kk] = ((Trd[kk] * (PLAIN ? X[kk] : X[kk] - Y[kk])) * lm1[kk]) * ff[kk];
-    } else {
-        RC_FOR_K X[kk] = gp * B0[kk];
-        RC_FOR_K Tw[kk] = st[kk].T * w2pi;
-        RC_FOR_K Trd[kk] = Tw[kk] * rd[kk];
-        RC_FOR_K vp[kk] = (Trd[kk] * lp1[kk]) * ((PLAIN ? X[kk] : X[kk] + Y[kk]) * ee[kk]);
-        RC_FOR_K vn[kk] = (Trd[kk] * lm1[kk]) * ((PLAIN ? X[kk] : X[kk] - Y[kk]) * ff[kk]);
-    }
+    // the mode integrals, their common factors multiplied once
+    const double w2A0 = w2pi * A0, w2gp = w2pi * gp, w2gmc = PLAIN ? 0.0 : w2pi * gmc;
+    RC_FOR_K Trd[kk] = st[kk].T * rd[kk];
+    RC_FOR_K X[kk] = w2gp * B0[kk];
+    RC_FOR_K Y[kk] = PLAIN ? 0.0 : w2gmc * g[kk].u1;
+    RC_FOR_K vp[kk] = ((Trd[kk] * (PLAIN ? X[kk] : X[kk] + Y[kk])) * lp1[kk]) * ee[kk];
+    RC_FOR_K vn[kk] = ((Trd[kk] * (PLAIN ? X[kk] : X[kk] - Y[kk])) * lm1[kk]) * ff[kk];
     if (!first && eo_ok) {
         RC_FOR_K eo[kk] = st[kk].EO;
     } else {
@@ -233,7 +222,7 @@ __device__ __forceinline__ void rc_angle(const double (*in)[64], const double (*
     }
     if (!last) RC_FOR_K st[kk].EO = eo[kk] * e0o[kk];
     double s1[NA], S0[NA], kap[NA], Tn[NA], delta_n[NA];
-    if (PZ_REFL_DIET && ZP && nocld && same_dt) {       // reflected_layer, PZ_REFL_DIET (3)
+    if (ZP && nocld && same_dt) {                       // the layer source of a layer that is not delta-scaled
         RC_FOR_K S0[kk] = fma(w2A0, B0[kk] * fx[kk], ssa_h * eo[kk]) * t2[kk];
     } else {
         RC_FOR_K s1[kk] = (ssa_h * (ZP ? 1.0 : g[kk].wq2)) * (eo[kk] * t1[kk]);
@@ -307,13 +296,8 @@ __device__ __forceinline__ void rc_shared(const ReflectedArgs &a, const double (
     }
     const double E = fmin(lam * dt, clip);
     const double EP = fexp2(E * -NEG_LOG2E, K);
-#if PZ_REFL_DIET
-    const double r_ge = frcp(g2 * EP);                 // reflected_layer, PZ_REFL_DIET (5)
+    const double r_ge = frcp(g2 * EP);                 // 1/g2 and 1/EP from one reciprocal, as reflected_layer
     const double gam = (g1 - lam) * (r_ge * EP), EM = r_ge * g2;
-#else
-    const double gam = (g1 - lam) * frcp(g2);
-    const double EM = frcp(EP);
-#endif
     const double ssa_h = (w0o * F * (0.125 / PI)) * ps;
     const double w2pi = w0 * (0.5 / PI);
     const double Fw0h = (0.5 * F) * w0;
@@ -405,8 +389,7 @@ __device__ __forceinline__ void rc_shared_plain_round(const double (*in)[RW_NV][
     RC_FOR_J E[j] = fmin(lam[j] * dt[j], 35.0);                 // fluxes.py:1174
     RC_FOR_J targ[j] = E[j] * -NEG_LOG2E;
     fexp2_n<NL>(targ, K, EP);
-#if PZ_REFL_DIET
-    {                                                           // reflected_layer, PZ_REFL_DIET (5)
+    {                                                           // 1/g2 and 1/EP from one reciprocal, as reflected_layer
         double pge[NL], rge[NL];
         RC_FOR_J pge[j] = g2[j] * EP[j];
         frcp_n<NL>(pge, rge);
@@ -414,11 +397,6 @@ __device__ __forceinline__ void rc_shared_plain_round(const double (*in)[RW_NV][
         RC_FOR_J EM[j] = rge[j] * g2[j];
     }
     RC_FOR_J gam[j] = (g1[j] - lam[j]) * ig2[j];
-#else
-    frcp_n<NL>(g2, ig2);
-    RC_FOR_J gam[j] = (g1[j] - lam[j]) * ig2[j];
-    frcp_n<NL>(EP, EM);
-#endif
     double ps[NL], ssa_h[NL], w2pi[NL], Fw0h[NL], A0[NL];
     RC_FOR_J ps[j] = fr[j] * (0.75 * fma(cos_theta, cos_theta, 1.0));
     RC_FOR_J ssa_h[j] = (w0o[j] * F * (0.125 / PI)) * ps[j];
@@ -769,10 +747,10 @@ int launch_reflected_coop(picaso_ctx *ctx, const ReflectedArgs &a)
     const dim3 grid((unsigned)((a.ncol + 63) / 64)), block(64 * ((a.na + RC_APW - 1) / RC_APW + 2));
     const int drv = reflected_coop_pattern(a);
     if (drv < 0) return fail(ctx, "reflected (cooperative kernel): unsupported set of planes");
-#define PZ_GO(Z, D) hipLaunchKernelGGL((k_reflected_coop<Z, D>), grid, block, 0, ctx->stream, a)
-    if (zp) { if (drv == 0) PZ_GO(true, 0); else if (drv == 2) PZ_GO(true, 2); else PZ_GO(true, 3); }
-    else { if (drv == 0) PZ_GO(false, 0); else if (drv == 2) PZ_GO(false, 2); else PZ_GO(false, 3); }
-#undef PZ_GO
+#define RC_GO(Z, D) hipLaunchKernelGGL((k_reflected_coop<Z, D>), grid, block, 0, ctx->stream, a)
+    if (zp) { if (drv == 0) RC_GO(true, 0); else if (drv == 2) RC_GO(true, 2); else RC_GO(true, 3); }
+    else { if (drv == 0) RC_GO(false, 0); else if (drv == 2) RC_GO(false, 2); else RC_GO(false, 3); }
+#undef RC_GO
     PZ_HIP(ctx, hipGetLastError());
     return 0;
 }

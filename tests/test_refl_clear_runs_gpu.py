@@ -1,5 +1,5 @@
-"""Runs of cloud-free layers in the zero-phase reflected sweep (csrc/toon_reflected.hip: ``PZ_REFL_MERGE_XT``,
-``PZ_REFL_TOPRUN``, ``PZ_REFL_CLEAR_ENDS``).
+"""Runs of cloud-free layers in the zero-phase reflected sweep (csrc/toon_reflected.hip: ``reflected_layer``'s ``XT``,
+the top-run loop with ``BODY_CLEAR_TOP``, ``CLEAR_FIRST`` / ``CLEAR_LAST``).
 
 The kernels that form the level sums themselves (``k_reflected_toa<5, false, true, true, false, 2 | 3 | 4>`` and their
 batched forms) carry one beam product instead of three while nothing above was delta-scaled, sweep the run of sealed

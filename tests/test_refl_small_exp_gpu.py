@@ -1,4 +1,4 @@
-"""Small exponent arguments in the zero-phase reflected sweep (csrc/toon_reflected.hip ``PZ_REFL_SMALL_EXP``,
+"""Small exponent arguments in the zero-phase reflected sweep (csrc/toon_reflected.hip ``BODY_CLEAR_TOP_SMALL``,
 ``fexp2_small`` in csrc/device_math.hpp).
 
 A cloud-free layer of the top run whose ``|dtau| <= dt_small = 0.34 min(u)`` in every lane of its wave forms its five
