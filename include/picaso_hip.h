@@ -225,6 +225,12 @@ int picaso_reflected_1d_can_derive(int nlevel, long plane_pitch, int numg, int n
  * In the run of cloud-free layers from the top, that launch (and the cloud-free one that is handed dtau and w0 alone)
  * forms exp(-dtau/u) without range reduction while |dtau| <= 0.34 min(ubar) holds in every column of a wave: the same
  * bits with four instructions fewer per exponential.  PICASO_AMD_REFL_NO_SMALL_EXP=1 (read per launch) switches that off.
+ * The pass keeps two more facts with the mask, neither a flag nor handed out: which layers are cloudy AND delta-scaled in
+ * every column (!(ftau_cld[i] == 0.0) and !(dtau_og[i] == dtau[i]), so a NaN counts as cloudy, as it does to the kernels'
+ * tests), and whether every w0 lies in [0, 1] (a NaN fails that).  The same launch sweeps a run of such deck layers
+ * without the per-layer tests, and, when the w0 fact holds for every member and 0.34 min(ubar) sqrt(3) log2(e) <= 1/2,
+ * forms exp(lambda dtau) of a layer that passes the test above without range reduction too: the same bits.
+ * PICASO_AMD_REFL_NO_CLOUD_RUNS=1 (read per launch) switches both off.
  * picaso_reflected_seal_layers: clear_out[i] = 1 / 0 for the first min(cap, nlayer) layers of the sealed set that owns
  * the byte at any_plane_ptr, *nlayer_out = its layer count -- 0 when there is no such set or it recorded no mask.
  * picaso_reflected_seal_layers_stat: *mask_launches = launches on the context's device that used a mask (each is also

@@ -588,6 +588,22 @@ static double refl_dt_small(const double *ubar0, const double *ubar1, int count)
     return 0.34 * umin;
 }
 
+// ReflectedArgs::ep_small for a call with these angles (a batch: every member's table), given that every w0 of every
+// member lies in [0, 1] (the seals looked).  In a layer that passes the dt_small vote |dtau| <= fl(0.34 umin) in every
+// lane.  Quadrature, no cloud: g1 = fl(fl(sqrt(3)/2) fl(2 - w0)) <= sqrt(3) (1 + eps)^3 and g2 >= 0, so lam =
+// fsqrt(fl(fl(g1 g1) - fl(g2 g2))) <= g1 (1 + eps)^3 (a NaN w0 fails the seal's test; w0 outside [0, 1] could make lam
+// larger).  The kernel forms E = fl(lam dtau) -- far below the clip -- and t = fl(E log2(e)): |t| <= 0.34 umin sqrt(3)
+// log2(e) (1 + eps)^9, and (1 + eps)^9 < 1 + 2^-40.  So when 0.34 umin sqrt(3) log2(e) (1 + 2^-40) <= 1/2 as computed
+// below (the left side carries five roundings of its own, 2^-50 relative, inside the same margin), |t| <= 1/2 and
+// fexp2_small(t) is fexp2(t) bit for bit (device_math.hpp).  That is umin <= 0.5885: the five-angle Gauss table
+// (smallest u 0.0917) passes by far; a table with a larger smallest angle keeps the general EP.
+static bool refl_ep_small(const double *ubar0, const double *ubar1, int count)
+{
+    const double dts = refl_dt_small(ubar0, ubar1, count);      // 0.34 umin, negative when switched off or unknown
+    if (!(dts >= 0.0)) return false;
+    return dts * 1.7320508075688772935 * 1.4426950408889634074 * (1.0 + 0x1p-40) <= 0.5;
+}
+
 // A batched call (picaso_get_reflected_1d_batch_dev): host arrays of nspec device pointers and the geometries
 struct ReflBatchHost {
     int nspec;
@@ -609,9 +625,11 @@ struct ReflBatchHost {
 static bool reflected_seal_applies(picaso_ctx *ctx, int nlevel, int nwno, long plane_pitch, int numg, int numt,
                                    const double *const one[11], const double *ubar0, const double *ubar1, double cos_theta,
                                    int single_phase, int multi_phase, double frac_c, int toon_coefficients,
-                                   const ReflBatchHost *bt, std::vector<unsigned long long> &masks, bool &use_masks)
+                                   const ReflBatchHost *bt, std::vector<unsigned long long> &masks, bool &use_masks,
+                                   std::vector<unsigned long long> &cmasks, bool &w0_unit)
 {
     use_masks = false;
+    w0_unit = false;
     const int nang = numg * numt, nspec = bt ? bt->nspec : 1, ngeom = bt ? bt->ngeom : 1;
     if (nang != 5) return false;
     for (int s = 0; s < ngeom; ++s) {
@@ -636,17 +654,23 @@ static bool reflected_seal_applies(picaso_ctx *ctx, int nlevel, int nwno, long p
     }
     // The clear-layer masks of the seals (DRV = 4, "LAYERS"): the fused launch only -- the cooperative kernel has no such
     // variant -- when every member's seal recorded one and at least one layer of one member is clear; else LEVELS as before
+    // With them go the seals' deck-layer masks and what they found about w0 (every member's must hold)
     masks.assign(2 * (size_t)nspec, 0ull);
-    bool all_valid = true, any_clear = false;
+    cmasks.assign(2 * (size_t)nspec, 0ull);
+    bool all_valid = true, any_clear = false, all_unit = true;
     for (int s = 0; s < nspec; ++s) {
         const double *pl[11];
         for (int j = 0; j < 11; ++j) pl[j] = bt ? bt->plane[j][s] : one[j];
-        bool valid = false;
-        if (!seal_derivable(ctx->device, pl, nlevel, nwno, plane_pitch, &masks[2 * (size_t)s], &valid)) return false;
+        bool valid = false, unit = false;
+        if (!seal_derivable(ctx->device, pl, nlevel, nwno, plane_pitch, &masks[2 * (size_t)s], &valid,
+                            &cmasks[2 * (size_t)s], &unit))
+            return false;
         all_valid = all_valid && valid;
+        all_unit = all_unit && unit;
         any_clear = any_clear || masks[2 * (size_t)s] || masks[2 * (size_t)s + 1];
     }
     use_masks = !coop && all_valid && any_clear && !getenv("PICASO_AMD_REFL_NO_LAYER_MASK");
+    w0_unit = use_masks && all_unit;
     return true;
 }
 
@@ -694,11 +718,12 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
     ReflBatchHost bt_sealed;
     std::vector<const double *> absent;
     std::vector<unsigned long long> lmasks;      // two words per spectrum, see ReflectedArgs::lmask
-    bool use_lmask = false;
+    std::vector<unsigned long long> cmasks;      // ... and ReflectedArgs::cmask
+    bool use_lmask = false, w0_unit = false;
     if (!derived && ncolper == 1 && get_toa_intensity && !get_lvl_flux) {
         const double *const pl[11] = {dtau, tau, w0, cosb, gcos2, ftau_cld, ftau_ray, dtau_og, tau_og, w0_og, cosb_og};
         if (reflected_seal_applies(ctx, nlevel, nwno, plane_pitch, numg, numt, pl, ubar0, ubar1, cos_theta, single_phase,
-                                   multi_phase, frac_c, toon_coefficients, bt, lmasks, use_lmask)) {
+                                   multi_phase, frac_c, toon_coefficients, bt, lmasks, use_lmask, cmasks, w0_unit)) {
             tau = tau_og = gcos2 = nullptr;
             if (bt) {
                 absent.assign((size_t)nspec, nullptr);
@@ -734,6 +759,11 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
     a.use_lmask = use_lmask ? 1 : 0;
     if (use_lmask) { a.lmask[0] = lmasks[0]; a.lmask[1] = lmasks[1]; }
     a.dt_small = refl_dt_small(ubar0, ubar1, (bt ? bt->ngeom : 1) * nang);
+    // the cloud-run loop and the small-argument EP of the LAYERS kernel; PICASO_AMD_REFL_NO_CLOUD_RUNS=1 (the A/B switch,
+    // read per launch) leaves the masks 0 and the flag off: every deck layer then takes the masked loop, EP its general form
+    const bool cloud_runs = use_lmask && !getenv("PICASO_AMD_REFL_NO_CLOUD_RUNS");
+    if (cloud_runs) { a.cmask[0] = cmasks[0]; a.cmask[1] = cmasks[1]; }
+    a.ep_small = (cloud_runs && w0_unit && refl_ep_small(ubar0, ubar1, (bt ? bt->ngeom : 1) * nang)) ? 1 : 0;
     const bool fuse = albedo && gweight && tweight;
     a.albedo = fuse ? albedo : nullptr;
     a.albedo_scale = ((numt == 1) ? 2.0 * 3.14159265358979323846 : 1.0) * 0.5;   // disco.py:140-141
@@ -758,6 +788,8 @@ static int reflected_1d_core(picaso_ctx *ctx, int nlevel, int nwno, int ncolper,
             it.u0_tab = it.u1_tab = nullptr;
             it.lmask[0] = use_lmask ? lmasks[2 * (size_t)s] : 0ull;
             it.lmask[1] = use_lmask ? lmasks[2 * (size_t)s + 1] : 0ull;
+            it.cmask[0] = cloud_runs ? cmasks[2 * (size_t)s] : 0ull;
+            it.cmask[1] = cloud_runs ? cmasks[2 * (size_t)s + 1] : 0ull;
             ct1 = ct1 && it.cos_theta == 1.0;
             const double *u0 = ubar0 + (bt->ngeom > 1 ? (size_t)s * nang : 0), *u1 = ubar1 + (bt->ngeom > 1 ? (size_t)s * nang : 0);
             for (int k = 0; k < count; ++k) {

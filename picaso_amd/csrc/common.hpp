@@ -157,7 +157,14 @@ struct ReflectedArgs {
         // -log2(e)/u1, -log2(e)(1/u0 + 1/u1): exp(-x/u) = 2^(x nl); wq2 = 2 u0/(u0+u1);
         // q2 = (3 ubar2^2 u1^2 - 1)/2, ubar2 = 0.767 (fluxes.py:1280); wgt, wgt2 = gweight[g], tweight[t]
     } ang[MAX_ANGLES];
-    const double *u0_tab, *u1_tab;          // 3-D
+    // 3-D: the tables of |ubar|.  1-D, DRV = 4 only, in the same sixteen bytes (a 1-D launch has no tables, and the
+    // argument block of every other kernel keeps its size and offsets): bit i set = layer i of the sealed set is cloudy
+    // AND delta-scaled in every column (!(ftau_cld == 0) and !(dtau_og == dtau), planeseal.hip) -- prep()'s two votes are
+    // known to fail, the layer is BODY_CLOUD's.  Disjoint from lmask; 0 without cloud runs.  A batched launch: the entry's.
+    union {
+        struct { const double *u0_tab, *u1_tab; };
+        unsigned long long cmask[2];
+    };
     double *xint;                           // 1-D: this launch's first angle row, (na, nwno); 3-D: (nfac, nwno)
     double *albedo;                         // nullable; 1-D fused compress_disco accumulator
     double albedo_scale;                    // sym_fac*0.5*(cos_theta+1)
@@ -176,6 +183,10 @@ struct ReflectedArgs {
     // kernel then reads dtau and w0 of that layer alone.  0 everywhere else.  A batched launch: the entry's own mask.
     unsigned long long lmask[2];
     int use_lmask;                          // the launcher's request for that variant (every member's mask is valid)
+    // DRV = 4 only, wave-uniform: a top-run layer that passes the dt_small vote may form EP = 2^(lam dtau log2 e) without
+    // range reduction as well.  Set when every w0 of every member lies in [0, 1] (the seal looked) and the angle table
+    // is small enough (api.hip, refl_ep_small); 0 everywhere else.
+    int ep_small;
     // The zero-phase default-options kernels (DRV 2 / 3 / 4): a cloud-free layer whose |dtau| <= dt_small in every lane of
     // the wave forms exp(-dtau/u) without range reduction (fexp2_small).  0.34 min(u) over every angle of the call (a
     // batch: of every member): dtau * nl1 as the kernel rounds it then lies within +-0.4906.  Negative: never.
@@ -186,7 +197,10 @@ struct ReflBatchItem {
     const double *surf_reflect, *F0PI;
     double *xint, *albedo;
     double cos_theta;
-    const double *u0_tab, *u1_tab;          // 3-D: this spectrum's (nfac) tables of ubar0, ubar1
+    union {
+        struct { const double *u0_tab, *u1_tab; };      // 3-D: this spectrum's (nfac) tables of ubar0, ubar1
+        unsigned long long cmask[2];                    // 1-D: its deck-layer mask (ReflectedArgs::cmask), set after them
+    };
     ReflectedArgs::Angle ang[MAX_ANGLES];   // 1-D: this launch chunk's angles of this spectrum
     unsigned long long lmask[2];            // this spectrum's clear-layer mask (ReflectedArgs::lmask)
 };

@@ -43,13 +43,17 @@ sealreg::Registry &registry()
 }  // namespace
 
 bool seal_derivable(int device, const double *const planes[11], int nlevel, int nwno, long pitch,
-                    unsigned long long *layer_mask, bool *mask_valid)
+                    unsigned long long *layer_mask, bool *mask_valid, unsigned long long *deck_mask, bool *w0_unit)
 {
-    uint64_t m[2];
-    const bool ok = registry().derivable(device, planes, nlevel, nwno, pitch, m, mask_valid);
+    uint64_t m[2], c[2];
+    const bool ok = registry().derivable(device, planes, nlevel, nwno, pitch, m, mask_valid, c, w0_unit);
     if (layer_mask) {
         layer_mask[0] = m[0];
         layer_mask[1] = m[1];
+    }
+    if (deck_mask) {
+        deck_mask[0] = c[0];
+        deck_mask[1] = c[1];
     }
     return ok;
 }
@@ -71,9 +75,20 @@ void seal_drop_device(int device) { registry().drop_device(device); }
 // or than w0's in w0_og -- those two values the LAYERS kernel puts in without loading them.  The lanes of a wave vote
 // per layer; a wave that found a layer not clear ORs its eight bits (a run of SEAL_ROWS layers lies inside one 32-bit
 // word) into the array with one vector atomic from its first lane.  A cloud-free set issues none.
+//
+// Two more facts from the same loads, kept with the mask and never handed to a caller (the LAYERS kernel's cloud-run loop
+// and its small-argument EP, toon_reflected.hip):
+//   * the deck mask: a layer is NOT a deck layer when some column has ftau_cld == 0 or dtau_og == dtau -- the two
+//     comparisons prep() votes on, so a column with a NaN in either plane counts as cloudy and delta-scaled there as it
+//     does here.  Voted and ORed like the clear mask into a second set of words; most layers of most sets are no deck
+//     layers and most waves would send the same bits, so a wave looks at the word first and sends only bits it misses (a
+//     stale look costs an atomic, never a bit);
+//   * one word that stays 0 while every w0 read lies in [0, 1] (a NaN fails that).
 constexpr int SEAL_BLOCK = 256, SEAL_ROWS = 8;
 static_assert(32 % SEAL_ROWS == 0, "the layers of one block lie inside one word of the mask");
-constexpr int SEAL_WORDS = 1 + sealreg::MASK_LAYERS / 32;      // the device buffer: flags found bad, then the mask words
+constexpr int SEAL_MASK_WORDS = sealreg::MASK_LAYERS / 32;
+// the device buffer: flags found bad, the clear-mask words, the deck-mask words, w0 found outside [0, 1]
+constexpr int SEAL_WORDS = 1 + 2 * SEAL_MASK_WORDS + 1;
 
 __global__ __launch_bounds__(SEAL_BLOCK) void k_planes_seal(int nlayer, int nwno, long pitch, const double *dtau,
                                                              const double *tau, const double *gcos2,
@@ -89,6 +104,8 @@ __global__ __launch_bounds__(SEAL_BLOCK) void k_planes_seal(int nlayer, int nwno
     int bad = 0;
     unsigned notclear = 0;                           // wave-uniform: bit (i & 31) = some lane of this wave saw cloud in layer i
     unsigned lane_cloudy = 0;                        // this lane's own findings, bit (i - i0)
+    unsigned notdeck = 0, lane_notdeck = 0;          // the same for "not cloudy and delta-scaled"
+    bool w0_out = false;
     double t = tau[(long)i0 * pitch + col], to = tau_og[(long)i0 * pitch + col];
     if (i0 == 0) {                                   // the sums start from +0.0 (the bit pattern: -0.0 is another start)
         if (__double_as_longlong(t) != 0) bad |= PICASO_SEAL_TAU;
@@ -108,18 +125,30 @@ __global__ __launch_bounds__(SEAL_BLOCK) void k_planes_seal(int nlayer, int nwno
         }
         if (!(gcos2[o] == 0.5 * fr)) bad |= PICASO_SEAL_GCOS2;
         if (notclear_out) {
-            const bool cloudy = !(ftau_cld[o] == 0.0) || !(dto == dt) ||
+            const double fc = ftau_cld[o], w = w0[o];
+            const bool cloudy = !(fc == 0.0) || !(dto == dt) ||
                                 __double_as_longlong(fr) != __double_as_longlong(1.0) ||
-                                __double_as_longlong(w0_og[o]) != __double_as_longlong(w0[o]);
+                                __double_as_longlong(w0_og[o]) != __double_as_longlong(w);
             if (cloudy) lane_cloudy |= 1u << (i - i0);
+            if (fc == 0.0 || dto == dt) lane_notdeck |= 1u << (i - i0);
+            if (!(w >= 0.0 && w <= 1.0)) w0_out = true;
         }
     }
     // (the votes after the loop: a vote inside it would keep the loop from being unrolled)
 #pragma unroll
     for (int b = 0; b < SEAL_ROWS; ++b)
         if (__any((lane_cloudy >> b) & 1u)) notclear |= 1u << ((i0 & 31) + b);
+#pragma unroll
+    for (int b = 0; b < SEAL_ROWS; ++b)
+        if (__any((lane_notdeck >> b) & 1u)) notdeck |= 1u << ((i0 & 31) + b);
+    const bool any_w0_out = __any(w0_out);
     if (bad) atomicOr(bad_out, bad);
     if (notclear && (threadIdx.x & 63) == 0) atomicOr(notclear_out + (i0 >> 5), notclear);   // lane 0 is active if any is
+    if (notclear_out && (threadIdx.x & 63) == 0) {
+        unsigned *deck_word = notclear_out + SEAL_MASK_WORDS + (i0 >> 5), *w0_word = notclear_out + 2 * SEAL_MASK_WORDS;
+        if (notdeck & ~__hip_atomic_load(deck_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(deck_word, notdeck);
+        if (any_w0_out && !__hip_atomic_load(w0_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(w0_word, 1u);
+    }
 }
 
 }  // namespace pz
@@ -165,7 +194,9 @@ int picaso_reflected_planes_seal_dev(picaso_ctx *ctx, int nlevel, int nwno, long
     s.nwno = nwno;
     s.pitch = plane_pitch;
     s.flags = PICASO_SEAL_LEVELS & ~found[0];
-    sealreg::mask_from_device_words(s, with_mask ? (const unsigned *)found + 1 : nullptr);
+    sealreg::mask_from_device_words(s, with_mask ? (const unsigned *)found + 1 : nullptr,
+                                    with_mask ? (const unsigned *)found + 1 + SEAL_MASK_WORDS : nullptr,
+                                    with_mask && found[1 + 2 * SEAL_MASK_WORDS] == 0);
     registry().record(ctx->device, s);
     if (flags_out) *flags_out = s.flags;
     return 0;

@@ -7,9 +7,12 @@ namespace pz {
 
 // true when the eleven addresses (REFLECTED_PLANES order) with these sizes carry a seal whose flags are all set;
 // layer_mask (two words) / mask_valid (both may be null): bit i set = layer i of that set is cloud-free in every column;
-// not valid and all 0 when the seal recorded no mask (more than 128 layers) or there is no seal
+// not valid and all 0 when the seal recorded no mask (more than 128 layers) or there is no seal.
+// deck_mask (two words) / w0_unit, handed out with a valid mask only: bit i set = layer i is cloudy and delta-scaled in every
+// column (!(ftau_cld == 0) and !(dtau_og == dtau)); every w0 of the set lies in [0, 1]
 bool seal_derivable(int device, const double *const planes[11], int nlevel, int nwno, long pitch,
-                    unsigned long long *layer_mask = nullptr, bool *mask_valid = nullptr);
+                    unsigned long long *layer_mask = nullptr, bool *mask_valid = nullptr,
+                    unsigned long long *deck_mask = nullptr, bool *w0_unit = nullptr);
 // a launch took the LEVELS variant because of a seal (with_layer_mask: the LAYERS variant, which is counted as both)
 void seal_count_hit(int device, bool with_layer_mask = false);
 // drop every seal of the device with a plane that overlaps [p, p + bytes): the bytes are about to change or to go away

@@ -22,6 +22,12 @@ struct Seal {
     // bit i: layer i is cloud-free in every column (k_planes_seal); meaningful only with mask_valid
     uint64_t clear[2];
     bool mask_valid;
+    // bit i: layer i is cloudy AND delta-scaled in every column -- !(ftau_cld == 0) and !(dtau_og == dtau), the solver's
+    // own two comparisons negated per column, so a NaN counts as cloudy as it does in the solver's votes; meaningful only
+    // with mask_valid.  Disjoint from clear[].
+    uint64_t deck[2];
+    // every w0 of the set lies in [0, 1] (a NaN fails it); false without a mask
+    bool w0_unit;
 
     // bytes of plane j the solver may read: rows of `pitch` elements, the last one `nwno` long
     size_t extent(int j) const
@@ -50,14 +56,24 @@ struct Seal {
 
 // The mask of a seal from what k_planes_seal left behind: `notclear` holds one bit per layer (32 per word, MASK_LAYERS / 32
 // words) set by the waves that found a column with cloud.  Bits at and above nlayer stay 0 in the result.
-inline void mask_from_device_words(Seal &s, const unsigned *notclear)
+// `notdeck`, in the same layout, holds the bits set by the waves that found a column that is not both cloudy and delta-
+// scaled; `w0_unit` is what the pass found for w0.  Without them (or without a mask) the seal records no deck layer.
+inline void mask_from_device_words(Seal &s, const unsigned *notclear, const unsigned *notdeck = nullptr,
+                                   bool w0_unit = false)
 {
     const int nlayer = s.nlevel - 1;
     s.clear[0] = s.clear[1] = 0;
+    s.deck[0] = s.deck[1] = 0;
+    s.w0_unit = false;
     s.mask_valid = notclear != nullptr && nlayer <= MASK_LAYERS;
     if (!s.mask_valid) return;
-    for (int i = 0; i < nlayer; ++i)
-        if (!((notclear[i >> 5] >> (i & 31)) & 1u)) s.clear[i >> 6] |= (uint64_t)1 << (i & 63);
+    s.w0_unit = w0_unit;
+    for (int i = 0; i < nlayer; ++i) {
+        const bool clear = !((notclear[i >> 5] >> (i & 31)) & 1u);
+        if (clear) s.clear[i >> 6] |= (uint64_t)1 << (i & 63);
+        // (a layer no wave found cloudy is no deck layer, whatever the second set of words says)
+        if (!clear && notdeck && !((notdeck[i >> 5] >> (i & 31)) & 1u)) s.deck[i >> 6] |= (uint64_t)1 << (i & 63);
+    }
 }
 
 struct DeviceSeals {
@@ -93,12 +109,15 @@ struct Registry {
         ++records;
     }
 
-    // mask, mask_valid (may be null): the seal's clear-layer mask and whether it recorded one (both words 0 when not)
+    // mask, mask_valid (may be null): the seal's clear-layer mask and whether it recorded one (both words 0 when not);
+    // deck, w0_unit (may be null): its deck-layer mask and its finding about w0, handed out with the mask only
     bool derivable(int device, const double *const planes[11], int nlevel, int nwno, long pitch, uint64_t *mask,
-                   bool *mask_valid)
+                   bool *mask_valid, uint64_t *deck = nullptr, bool *w0_unit = nullptr)
     {
         if (mask) mask[0] = mask[1] = 0;
         if (mask_valid) *mask_valid = false;
+        if (deck) deck[0] = deck[1] = 0;
+        if (w0_unit) *w0_unit = false;
         if (records.load(std::memory_order_relaxed) == 0) return false;
         std::lock_guard<std::mutex> lock(mu);
         auto it = dev.find(device);
@@ -112,6 +131,11 @@ struct Registry {
                         mask[1] = s.clear[1];
                     }
                     if (mask_valid) *mask_valid = true;
+                    if (deck) {
+                        deck[0] = s.deck[0];
+                        deck[1] = s.deck[1];
+                    }
+                    if (w0_unit) *w0_unit = s.w0_unit;
                 }
                 return ok;
             }

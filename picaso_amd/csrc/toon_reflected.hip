@@ -116,9 +116,12 @@ struct LayerIn {
 //                         for every angle of the launch and et is formed by fexp2_small -- fexp2 without its four range-
 //                         reduction instructions, the same bits (device_math.hpp).  e0 is et there; EP takes another
 //                         argument and keeps the general form.
+//   BODY_CLEAR_TOP_SMALL_EP  BODY_CLEAR_TOP_SMALL in a launch with a.ep_small: every w0 lies in [0, 1], so lam <= sqrt(3),
+//                         and the angle table is small enough that lam * dtau * log2(e) lies within +-1/2 as well (the
+//                         launcher's proof, api.hip refl_ep_small): EP by fexp2_small too, the same bits.
 // Assuming the flags (every copy but the general one) removes the 3-4 wave-uniform branches per angle they feed and the
 // fall-back exponentials behind them; DESIGN.md section 6 has what each copy measured.
-enum Body { BODY_GENERAL, BODY_CLOUD, BODY_CLEAR, BODY_CLEAR_TOP, BODY_CLEAR_TOP_SMALL };
+enum Body { BODY_GENERAL, BODY_CLOUD, BODY_CLEAR, BODY_CLEAR_TOP, BODY_CLEAR_TOP_SMALL, BODY_CLEAR_TOP_SMALL_EP };
 
 // One layer of the sweep.  FIRST / LAST are compile-time so the top row and the bottom-boundary
 // terms cost nothing inside the loop.  ZP: every angle has ubar0 == ubar1 (symmetric 1-D geometry,
@@ -153,7 +156,7 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     // what the copy knows: NC no cloud in the layer; AF cum_tau and eo_ok hold, and same_dt is as SDT says (1: holds,
     // 2: does not); EOX eo is S_XU; SX small exponent arguments
     constexpr bool NC = KIND >= BODY_CLEAR, AF = KIND != BODY_GENERAL, EOX = KIND >= BODY_CLEAR_TOP;
-    constexpr bool SX = KIND == BODY_CLEAR_TOP_SMALL;
+    constexpr bool SX = KIND >= BODY_CLEAR_TOP_SMALL, SEP = KIND == BODY_CLEAR_TOP_SMALL_EP;
     constexpr int SDT = KIND == BODY_CLOUD ? 2 : 1;
     static_assert(!(XT || EOX) || (FAST && ZP), "XT, BODY_CLEAR_TOP*: the zero-phase default-options kernels only");
     const int tc = FAST ? 0 : tc_;
@@ -168,7 +171,8 @@ __device__ __forceinline__ void reflected_layer(const ReflectedArgs &a, const La
     if (NC) toon_gammas_nocld(tc, w0, g1, g2, lam, lam2);
     else toon_gammas(tc, w0, fcg, g1, g2, lam, lam2);
     const double E = fmin(lam * dt, clip);
-    const double EP = fexp2(E * -NEG_LOG2E, K);
+    // SEP: the launcher's proof and the caller's vote say |E log2(e)| <= 1/2 in every lane: same bits
+    const double EP = SEP ? fexp2_small(E * -NEG_LOG2E, K) : fexp2(E * -NEG_LOG2E, K);
     // 1/g2 and 1/EP from one reciprocal (g2 of order w0 <= 1, EP <= e^35: the product stays in range; g2 = 0 -- a layer
     // that does not scatter -- is NaN in Gamma here as in the reference's (g1 - lamda)/g2, fluxes.py:1141)
     const double r_ge = frcp(g2 * EP);
@@ -388,7 +392,7 @@ __device__ __forceinline__ double disk_finish(double c1, double acc, double F, d
 //      passed, so the same copy of the body runs on the same numbers.
 //
 // The sweep.  The first and the last layer are peeled out.  Kernels with one, two or (FAST, ZP) five angles per lane
-// prefetch into two register sets used alternately and sweep the interior two layers per trip, in up to three loops:
+// prefetch into two register sets used alternately and sweep the interior two layers per trip, in up to four loops:
 //   * the masked loop -- every kernel: per layer the mask test (DRV = 4), prep's votes and the choice between
 //     BODY_CLEAR, BODY_CLOUD and BODY_GENERAL (FAST; the generic kernels have the general body alone);
 //   * the top-run loop -- TOPRUN kernels: the run of known cloud-free layers from the top (DRV = 2: the whole column,
@@ -398,7 +402,11 @@ __device__ __forceinline__ double disk_finish(double c1, double acc, double F, d
 //     run ends S_EO is set from S_XU once;
 //   * the deck-run loop -- DECKRUN kernels: every maximal run of known cloud-free interior layers BELOW the top run
 //     (under a cloud deck) is swept like the top run, by BODY_CLEAR, which keeps S_EO; the masked loop's mask test,
-//     vmcnt(0) and dispatch block around each such layer (15-22 VALU) go.
+//     vmcnt(0) and dispatch block around each such layer (15-22 VALU) go;
+//   * the cloud-run loop -- DECKRUN kernels: every run of layers the seal found cloudy and delta-scaled in EVERY column
+//     (a.cmask) is swept by BODY_CLOUD with eight loads per layer under counted waits: prep's two votes are known to
+//     fail, so they, the mask test, the vmcnt(0) and the dispatch go here too.
+// The top run's small-argument form has a second copy for launches with a.ep_small (BODY_CLEAR_TOP_SMALL_EP).
 // The other angle counts keep one prefetch set, a copy per layer and the masked loop's dispatch.
 template <int NA, bool IS3D, bool ZP, bool FAST, bool BIG, int DRV, typename AnglePtr>
 __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const unsigned bx_in, const unsigned by_in,
@@ -471,6 +479,12 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     if constexpr (LAYERS) {
         m0 = a.lmask[0];
         m1 = a.lmask[1];
+    }
+    // the deck mask (layers cloudy and delta-scaled in every column), read once; 0 without cloud runs
+    unsigned long long c0 = 0, c1 = 0;
+    if constexpr (LAYERS) {
+        c0 = a.cmask[0];
+        c1 = a.cmask[1];
     }
     auto layer_clear = [&](int i) -> bool {          // wave-uniform: the mask is a kernel argument / a table entry
         if constexpr (LAYERS) return (((i & 64) ? m1 : m0) >> (i & 63)) & 1ull;
@@ -663,6 +677,32 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         __builtin_amdgcn_sched_barrier(0);                                                               \
     } while (0)
 
+    // a layer of a cloud run (DECKRUN kernels): the seal knows that prep's two votes fail in every wave -- every column has
+    // !(ftau_cld == 0) and !(dtau_og == dtau) -- so prep's LEVELS branch is taken without them, straight to BODY_CLOUD
+#define PZ_CLOUD_LAYER(L_)                                                                               \
+    do {                                                                                                 \
+        L_.gcos2 = 0.5 * L_.fr;                                                                          \
+        L_.tau_n = tau_i + L_.dt;                                                                        \
+        L_.tauo = tauo_pred;                                                                             \
+        L_.cum_tau = L_.eo_ok = L_.af_cloud = true;                                                      \
+        L_.same_dt = L_.nocld = L_.allf = false;                                                         \
+        tau_i = L_.tau_n;                                                                                \
+        tauo_pred = L_.tauo + L_.dto;                                                                    \
+        PZ_BODY(false, false, BODY_CLOUD, L_);                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+    } while (0)
+    // ... its loads: the eight planes of a LEVELS layer, no mask looked at, no wait by name
+    auto load_cloud = [&](LayerIn &L, int l) {
+        const unsigned o = voff0 + (unsigned)l * pitch8;
+        L.dt = ld(a.dtau, o);
+        L.w0 = ld(a.w0, o);
+        L.g = ld(a.cosb, o);
+        L.fc = ld(a.ftau_cld, o);
+        L.fr = ld(a.ftau_ray, o);
+        L.cbo = ld(a.cosb_og, o);
+        L.dto = ld(a.dtau_og, o);
+        L.w0o = ld(a.w0_og, o);
+    };
     // a layer of a run: dtau and w0 alone
     auto load_clear = [&](LayerIn &L, int l) {
         const unsigned o = voff0 + (unsigned)l * pitch8;
@@ -701,16 +741,24 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
                 if (i + 2 < r) {
                     double dt_a = ld(a.dtau, voff0 + (unsigned)(i + 1) * pitch8);
                     bool go = small_dt(B.dt) && small_dt(dt_a);
-                    while (go) {
-                        A.dt = dt_a;
-                        A.w0 = ld(a.w0, voff0 + (unsigned)(i + 1) * pitch8);
-                        PZ_RUN_LAYER(BODY_CLEAR_TOP_SMALL, B);
-                        load_clear(B, i + 2);
-                        dt_a = ld(a.dtau, voff0 + (unsigned)(i + 3 < n ? i + 3 : n - 1) * pitch8);
-                        PZ_RUN_LAYER(BODY_CLEAR_TOP_SMALL, A);
-                        i += 2;
-                        go = i + 2 < r && small_dt(B.dt) && small_dt(dt_a);
+#define PZ_SMALL_LOOP(KIND_)                                                                             \
+                    while (go) {                                                                         \
+                        A.dt = dt_a;                                                                     \
+                        A.w0 = ld(a.w0, voff0 + (unsigned)(i + 1) * pitch8);                             \
+                        PZ_RUN_LAYER(KIND_, B);                                                          \
+                        load_clear(B, i + 2);                                                            \
+                        dt_a = ld(a.dtau, voff0 + (unsigned)(i + 3 < n ? i + 3 : n - 1) * pitch8);       \
+                        PZ_RUN_LAYER(KIND_, A);                                                          \
+                        i += 2;                                                                          \
+                        go = i + 2 < r && small_dt(B.dt) && small_dt(dt_a);                              \
                     }
+                    // a.ep_small (DRV = 4, a kernel argument, looked at once): a second copy of the loop whose EP takes
+                    // fexp2_small as well
+                    if constexpr (LAYERS) {
+                        if (a.ep_small) PZ_SMALL_LOOP(BODY_CLEAR_TOP_SMALL_EP)
+                    }
+                    PZ_SMALL_LOOP(BODY_CLEAR_TOP_SMALL)
+#undef PZ_SMALL_LOOP
                 }
                 for (; i + 2 < r; i += 2) {
                     load_clear(A, i + 1);
@@ -726,6 +774,26 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
         }
         for (; i + 2 <= n - 1; i += 2) {         // the masked loop: layers i and i+1 are interior, layer i+2 exists
             if constexpr (DECKRUN) {
+                // The cloud-run loop: a run of sealed deck layers (a.cmask) is swept two per trip by BODY_CLOUD straight-line:
+                // eight loads per layer under the compiler's counted waits, no vote, no mask test, no wait by name, no
+                // dispatch.  ec: one past the run that starts at layer i, the last layer left out.  A trip needs layers i
+                // and i + 1 in the run; layer i + 2, which it prefetches, need not be: the eight planes are whatever the
+                // masked loop or a deck run would have loaded for it and more (a clear layer's six extra values are
+                // overwritten by prep), and i + 2 <= ec <= n - 1 is a row of the planes.  So a run is swept to its end
+                // when its length is even and to its last layer but one when odd.  Ahead of the deck-run loop, so that the clear
+                // layers under a deck go straight on to that.
+                const unsigned long long wc = i < 64 ? (c0 >> i) | (i ? c1 << (64 - i) : 0ull) : c1 >> (i - 64);
+                int ec = i + ((~wc) ? __builtin_ctzll(~wc) : 64);
+                ec = ec < n - 1 ? ec : n - 1;
+                if (i + 2 <= ec) {
+                    for (; i + 2 <= ec; i += 2) {
+                        load_cloud(A, i + 1);
+                        PZ_CLOUD_LAYER(B);
+                        load_cloud(B, i + 2);
+                        PZ_CLOUD_LAYER(A);
+                    }
+                    if (!(i + 2 <= n - 1)) break;
+                }
                 // The deck-run loop: a run of sealed cloud-free interior layers below the top run (under a cloud deck, between
                 // two) is swept like the top run -- two loads per layer under the compiler's counted waits, no mask test, no
                 // dispatch -- by BODY_CLEAR, which keeps S_EO (a layer above was delta-scaled, so S_EO is not S_XU).
@@ -769,6 +837,7 @@ __device__ __forceinline__ void reflected_toa_body(const ReflectedArgs &a, const
     }
 #undef PZ_LAYER
 #undef PZ_RUN_LAYER
+#undef PZ_CLOUD_LAYER
 #undef PZ_BODY
 
     // ---- surface row (fluxes.py:178-183) and output ----
@@ -866,7 +935,10 @@ __global__ __launch_bounds__(PZ_REFL_BLOCK, (BIG ? 1 : PZ_REFL_MINWAVES)) void k
     b.surf_reflect = it.surf_reflect; b.F0PI = it.F0PI; b.xint = it.xint; b.albedo = it.albedo;
     b.cos_theta = it.cos_theta;
     b.u0_tab = it.u0_tab; b.u1_tab = it.u1_tab;
-    if constexpr (DRV == 4) { b.lmask[0] = it.lmask[0]; b.lmask[1] = it.lmask[1]; }
+    if constexpr (DRV == 4) {
+        b.lmask[0] = it.lmask[0]; b.lmask[1] = it.lmask[1];
+        b.cmask[0] = it.cmask[0]; b.cmask[1] = it.cmask[1];
+    }
     reflected_toa_body<NA, IS3D, ZP, FAST, BIG, DRV>(b, bx, by, it.ang);
 }
 

@@ -1,5 +1,5 @@
 // The seal registry (picaso_amd/csrc/planeseal_registry.hpp) driven without a device: record, look up, replace,
-// invalidate and drop seals and their clear-layer masks over made-up plane addresses.  Meant for a sanitizer build on the
+// invalidate and drop seals, their clear-layer and deck-layer masks and their w0 fact over made-up plane addresses.  Meant for a sanitizer build on the
 // CPU -- the registry is the host code behind picaso_reflected_planes_seal_dev / _seal_layers / _seal_stat:
 //
 //     c++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all \
@@ -32,7 +32,7 @@ struct FakeSet {
     {
         for (int j = 0; j < 11; ++j) pl[j] = block.data() + (size_t)j * nlevel * pitch;
     }
-    Seal seal(int flags, const unsigned *notclear) const
+    Seal seal(int flags, const unsigned *notclear, const unsigned *notdeck = nullptr, bool w0_unit = false) const
     {
         Seal s{};
         for (int j = 0; j < 11; ++j) s.plane[j] = pl[j];
@@ -40,7 +40,7 @@ struct FakeSet {
         s.nwno = nwno;
         s.pitch = pitch;
         s.flags = flags;
-        mask_from_device_words(s, notclear);
+        mask_from_device_words(s, notclear, notdeck, w0_unit);
         return s;
     }
 };
@@ -79,6 +79,28 @@ int main()
     EXPECT(r.layers(0, a.pl[2], 0, nullptr) == 90);
     EXPECT(r.layers(0, a.block.data() + a.block.size(), 200, clear) == 0);             // one past the set
 
+    // the deck mask and the w0 fact: handed out with a valid mask only, the deck mask disjoint from the clear mask and
+    // empty above nlayer; words of 32 layers, bits set = NOT a deck layer
+    {
+        uint64_t c[2] = {1, 1};
+        bool unit = true;
+        EXPECT(r.derivable(0, a.pl, 91, 600, 600, m, &valid, c, &unit) && valid && c[0] == 0 && c[1] == 0 && !unit);   // recorded without
+        unsigned nk[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0};
+        for (int i = 50; i < 58; ++i) nk[i >> 5] &= ~(1u << (i & 31));      // 49 and 58: cloudy, but not in every column
+        nk[0] &= ~(1u << 3);                                                // says "deck", but layer 3 is clear: not a deck layer
+        r.record(0, a.seal(7, nc, nk, true));
+        EXPECT(r.derivable(0, a.pl, 91, 600, 600, m, &valid, c, &unit) && valid && unit);
+        for (int i = 0; i < 128; ++i) EXPECT((((c[i >> 6] >> (i & 63)) & 1) != 0) == (i >= 50 && i < 58));
+        EXPECT((c[0] & m[0]) == 0 && (c[1] & m[1]) == 0);
+        EXPECT(r.derivable(0, a.pl, 91, 600, 600, m, &valid, c, nullptr) && r.derivable(0, a.pl, 91, 600, 600, m, &valid, nullptr, &unit));
+        EXPECT(!r.derivable(0, a.pl, 91, 599, 600, m, &valid, c, &unit) && c[0] == 0 && c[1] == 0 && !unit);          // another shape
+        r.record(0, a.seal(7, nc, nk, false));                              // a w0 outside [0, 1]: the masks stay
+        EXPECT(r.derivable(0, a.pl, 91, 600, 600, m, &valid, c, &unit) && valid && !unit && c[0] != 0);
+        r.record(0, a.seal(7 & ~1, nc, nk, true));                          // not sealed: nothing is handed out
+        EXPECT(!r.derivable(0, a.pl, 91, 600, 600, m, &valid, c, &unit) && c[0] == 0 && c[1] == 0 && !unit);
+        r.record(0, a.seal(7, nc));
+    }
+
     // counters
     r.count_hit(0, false);
     r.count_hit(0, true);
@@ -101,6 +123,18 @@ int main()
     EXPECT(r.derivable(0, b.pl, 129, 64, 70, m, &valid) && valid && m[0] == ~(uint64_t)1 && m[1] == (~(uint64_t)0 >> 1));
     r.record(0, c.seal(7, nullptr));
     EXPECT(r.derivable(0, c.pl, 130, 64, 64, m, &valid) && !valid && m[0] == 0 && m[1] == 0);
+    {
+        // 128 layers, every one a deck layer but the first; more than 128 layers: no mask, so no deck mask and no w0 fact
+        unsigned all[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu}, nk[4] = {1u, 0, 0, 0};
+        uint64_t k[2];
+        bool unit;
+        r.record(0, b.seal(7, all, nk, true));
+        EXPECT(r.derivable(0, b.pl, 129, 64, 70, m, &valid, k, &unit) && valid && unit && m[0] == 0 && m[1] == 0);
+        EXPECT(k[0] == ~(uint64_t)1 && k[1] == ~(uint64_t)0);
+        r.record(0, b.seal(7, nb));
+        r.record(0, c.seal(7, nullptr, nk, true));
+        EXPECT(r.derivable(0, c.pl, 130, 64, 64, m, &valid, k, &unit) && !valid && !unit && k[0] == 0 && k[1] == 0);
+    }
     EXPECT(r.layers(0, c.pl[0], 200, clear) == 0);
     r.stat(0, &seals, nullptr, nullptr);
     EXPECT(seals == 3);
