@@ -1193,6 +1193,22 @@ int picaso_ck_from_xsec_dev(picaso_ctx *ctx, long n_lbl, const double *xsec, int
  * context's stream; returns at once.  The next row of cross sections travels on a second context's stream while the kernels
  * of the current one run; picaso_ctx_wait / picaso_sync order it. */
 int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, size_t bytes);
+/* The mixture behind a PREMIXED table (reference opacity_factory.py:1617, 1707-1713, compute_sum_molecular): one step of
+ *   total_sum = 0;  for gas: total_sum += weight * dset
+ * on device arrays, so that the sum of a P-T point goes to picaso_ck_from_xsec_dev without leaving HBM:
+ *   acc[j] = (first ? 0.0 : acc[j]) + weight * v[j],   j in [0, n_out)
+ *   v = src                                    src_grid, out_grid NULL (then n_src == n_out)
+ *   v = np.interp(out_grid, src_grid, src)     otherwise (:1710-1711): numpy's bracket, knot hits, clamps and NaN retry
+ * The product and the sum are separate IEEE operations: acc is numpy's sum bit for bit.  With `first` the sum starts as
+ * 0.0 + weight * v (a product of -0.0 becomes +0.0).  NaNs in src propagate.
+ * acc: device (n_out), read unless `first`, written.  src: device (n_src).  src_grid (n_src, nondecreasing), out_grid (n_out):
+ * device, built on the host.  guess_start, guess_step: with guess_step > 0, knot j of src_grid is looked for near
+ * (x - guess_start) / guess_step and the bracket is corrected against src_grid itself (a uniform grid: its first knot and
+ * its step); a wrong guess costs time, never the result.  guess_step <= 0: binary search.
+ * Returns after the launch, like the other _dev entry points.  Errors, nothing launched: n_out < 1, a grid with n_src < 2,
+ * a row longer than INT_MAX, n_src != n_out without grids, one grid without the other, a NaN weight. */
+int picaso_xsec_axpy_dev(picaso_ctx *ctx, long n_out, double *acc, int first, double weight, const double *src, long n_src,
+                         const double *src_grid, const double *out_grid, double guess_start, double guess_step);
 
 /* ---- prediction bands: order statistics of every column (reference retrieval.py:199-310, get_evaluations) --------------
  * The reference stacks the model at n_draws posterior samples and reduces the stack per wavelength (and per pressure level)

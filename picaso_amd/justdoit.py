@@ -37,6 +37,7 @@ from .regrid import RegridPlan, regrid_plan                                     
 from .contribution import thermal_contribution, transmission_contribution           # noqa: F401  (jdi.thermal_contribution)
 from .attenuation import cloud_optics_1d, heatmap_taus, photon_attenuation, taumap   # noqa: F401  (jdi.photon_attenuation)
 from .opacity_factory import compute_ck, compute_ck_molecular                        # noqa: F401  (jdi.compute_ck)
+from .opacity_factory import compute_ck_premixed, compute_sum_molecular, weighted_sum      # noqa: F401
 from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
                        _fetch, _interp_axis, _lon_period, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
                        _resident_vector, _setup_atmosphere, _trapz_resident)
