@@ -1294,6 +1294,48 @@ int picaso_gcm_facet_tables_dev(picaso_ctx *ctx, int nlon, int nlat, int npres, 
 int picaso_param_cloud_tables_dev(picaso_ctx *ctx, int S, int K, int nlayer, int nin, int average, const double *layers,
                                   const double *params, const double *wavelength, double *out /* (S, 3, nlayer, nin) */);
 
+/* ---- Mie efficiencies of a list of spheres (picaso_amd/mie.py states the series; csrc/mie.hip) ----
+ * the producer of a Mie table: what virga's calc_new_mieff does in Python per (wavelength, radius).  x (size parameter 2 pi r /
+ * lambda), m_re, m_im (refractive index n + ik): host, n entries each.  nstop, nmx: host, n entries each, the two truncation
+ * orders of every element as the caller forms them (picaso_amd/mie.py: _orders), sorted by nmx so that the 64 neighbours a wave
+ * takes run about the same number of steps (any order is correct, a sorted one is fast):
+ *   nstop = int(x + 4 x^(1/3) + 2),  nmx = int(max(nstop, |m x|) + 15 + 8 |m x|^(1/3))
+ * nstop = nmx = 0 marks an element that is not evaluated; so does x <= 0, m_im < 0 or a NaN, which the kernel sees for itself.
+ * Such an element gives NaN and touches no scratch.  Per element the downward recurrences of D_n(m x) and D_n(x) from
+ * D_nmx = 0, psi by ratios, chi upward, a_n and b_n, and the three sums over n = 1 .. nstop in increasing n; complex quotients
+ * by Smith's algorithm, IEEE divisions, nothing contracted.  An element's bits depend on its own x, m, nstop and nmx alone.
+ * scratch: device, scratch_bytes bytes; a wave of 64 consecutive elements takes 3 * 64 * 8 bytes per term up to the largest
+ * nstop among them (D_n for the upward pass, term-major).  out: device, (3, n) = qext, qsca, g qsca.
+ * Every index the kernel forms follows from nstop and nmx, and both are checked here.  Errors, nothing launched: n < 1, an
+ * nmx above PICASO_MIE_NMX_CAP, an element without 0 <= nstop < nmx (or both 0), a list that needs more scratch than
+ * scratch_bytes (picaso_last_error says how much), a NULL array.  Returns when the results are in `out`. */
+#define PICASO_MIE_NMX_CAP 1048576
+int picaso_mie_q_dev(picaso_ctx *ctx, long n, const double *x, const double *m_re, const double *m_im, const int *nstop,
+                     const int *nmx, double *scratch, size_t scratch_bytes, double *out /* (3, n) */);
+
+/* ---- cloud tables of a batch of Mie clouds (reference parameterizations.py:94-198 cloud_flex_fsed / cloud_brewster_mie on
+ * virga's calc_optics_user_r_dist, :672-750 picaso_format, :753-792 cloud_averaging; picaso_amd/mie.py) ----
+ * S samples of K decks each, 1 <= K <= 4.  tables: host, ntable device addresses; table t is (3, nradii[t], nwave) = qext, qscat,
+ * cos_qscat with the wavelength index fastest and the wavenumber increasing.  nradii: host (ntable), each in [1, rmax].
+ * deck_table: host (S, K), the table of every deck, -1 for an empty deck (a sample with fewer decks than K; average = 1 only).
+ * deck_kind: host (S, K), 0 = brewster_mie, 1 = flex_fsed.  wgt: device (S, K, rmax), per deck
+ * (ndz * (PI * radius[r]**2)) * distribution[r].  factor: device (S, K, nlayer), the layer factor (brewster_mie: opd_profile;
+ * flex_fsed: p_decay / max(p_decay)).  inside: device (S, K, nlayer), 1.0 where picaso_format keeps the layer, else 0.0.
+ * Per deck and wavelength: opd, opd_scat, opd_cos = the left-to-right sums over r from 0 of q[r][w] * wgt[r]; w0 = opd_scat / opd
+ * where opd > 0 else 0; g0 = opd_cos / opd_scat where opd_scat > 0 else 0; v = opd / max_w(opd) for brewster_mie (the max
+ * exact, NaN if any opd is NaN, as np.max), v = opd for flex_fsed.  Per element: inside (factor[l] * v, w0, g0), outside
+ * (opd * 0, w0 * 0, g0 * 0) -- +0 for finite values that are not negative.  average == 0 (K must be 1) stores them; average ==
+ * 1 is cloud_averaging in deck order as in picaso_param_cloud_tables_dev, empty decks left out.  Rounded products, ordered
+ * sums and IEEE quotients, nothing contracted: the bits of the host functions.
+ * work: device, S * K * (3 * nwave + 1) doubles of scratch.  out: device, (S, 3, nlayer, nwave) as picaso_param_cloud_tables_dev
+ * writes it.  Bad arguments (a count out of range, a table index outside [-1, ntable), a kind outside {0, 1}, an empty deck with
+ * average = 0, a NULL array): an error code, picaso_last_error says which, nothing is launched.  Returns when the rows are
+ * written. */
+int picaso_mie_cloud_tables_dev(picaso_ctx *ctx, int S, int K, int nlayer, int nwave, int average, int ntable,
+                                const double *const *tables, const int *nradii, const int *deck_table, const int *deck_kind,
+                                int rmax, const double *wgt, const double *factor, const double *inside, double *work,
+                                double *out /* (S, 3, nlayer, nwave) */);
+
 #ifdef __cplusplus
 }
 #endif

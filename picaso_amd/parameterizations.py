@@ -11,8 +11,9 @@ The grey clouds have a second form.  ``cloud_tables_batch`` turns the deck descr
 returns one ``ParamCloudTable`` per sample: for ``inputs.clouds(df=...)`` a dictionary like any other, for the one-call
 spectrum path rows that already lie where the fused opacity launch reads them -- no host table, no digest, no upload.
 
-Not built, each refused with what is missing: the Mie clouds (``load_cld_optical`` / ``mieff_dir``, ``cloud_virga``,
-``cloud_flex_fsed`` / ``flex_cloud``, ``cloud_brewster_mie``: virga), the Madhusudhan-Seager profiles (astropy's
+Not built as methods, each refused with what is missing: the Mie clouds (``load_cld_optical`` / ``mieff_dir``,
+``cloud_virga``, ``cloud_flex_fsed`` / ``flex_cloud``, ``cloud_brewster_mie``: virga; the functions of ``picaso_amd.mie``
+that take a ``Parameterize`` do the last two and their batch), the Madhusudhan-Seager profiles (astropy's
 ``convolve``), ``chem_visscher`` (``chemeq_visscher_2121``) and ``pt_knots`` with an arbitrary ``scipy.interpolate`` name.
 """
 import numpy as np
@@ -40,7 +41,8 @@ class Parameterize():
     def __init__(self, load_cld_optical=None, mieff_dir=None):
         if load_cld_optical is not None or mieff_dir is not None:
             raise _missing("Parameterize(load_cld_optical=, mieff_dir=)",
-                           "virga's Mie tables (virga.justdoit.get_mie), which are outside this package")
+                           "virga's Mie tables (virga.justdoit.get_mie), which are outside this package; "
+                           "picaso_amd.mie.get_mie(gas, directory) reads a .mieff file and mie.compute_mieff makes a table here")
         self.mieff_dir = mieff_dir
 
     def add_class(self, picaso_inputs_class):
@@ -60,15 +62,18 @@ class Parameterize():
 
     # ------------------------------------------------------------------------------------------ refused forms
     def cloud_virga(self, **virga_kwargs):
-        raise _missing("cloud_virga", "inputs.virga and virga's Mie tables, which are outside this package")
+        raise _missing("cloud_virga", "inputs.virga and virga's Mie tables, which are outside this package (virga's cloud "
+                       "model is not built; picaso_amd.mie has the size-distribution clouds, mie.cloud_flex_fsed and "
+                       "mie.cloud_brewster_mie)")
 
     def cloud_flex_fsed(self, *args, **kwargs):
         raise _missing("cloud_flex_fsed / flex_cloud", "virga's Mie tables and calc_optics_user_r_dist, which are outside "
-                       "this package")
+                       "this package; picaso_amd.mie.cloud_flex_fsed(param, table, ...) does the job here on a mie.MieTable")
     flex_cloud = cloud_flex_fsed
 
     def cloud_brewster_mie(self, *args, **kwargs):
-        raise _missing("cloud_brewster_mie", "virga's Mie tables and calc_optics_user_r_dist, which are outside this package")
+        raise _missing("cloud_brewster_mie", "virga's Mie tables and calc_optics_user_r_dist, which are outside this package; "
+                       "picaso_amd.mie.cloud_brewster_mie(param, table, ...) does the job here on a mie.MieTable")
 
     def pt_madhu_seager_09_noinversion(self, *args, **kwargs):
         raise _missing("pt_madhu_seager_09_noinversion", "astropy.convolution.convolve for its smoothing, which is not "
