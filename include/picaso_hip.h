@@ -1141,6 +1141,23 @@ int picaso_lsf_convolve_dev(picaso_ctx *ctx, long nwno, const double *wl, int no
                             const double *den, const int *lo, const int *hi, int nrows, const picaso_regrid_row *rows,
                             double *out /* (nrows, nobs) */);
 
+/* ---- several instruments from one spectrum (reference driver.py:232-236, the loop over observation_data in MODEL) ------
+ * One table of nmean + ngauss points reduces the rows of picaso_mean_regrid_dev to the grids of several data sets.  Point
+ * p covers the model columns [lo[p], hi[p]) and writes out[r][col[p]] (row stride nmean + ngauss).  Points [0, nmean):
+ * picaso_mean_regrid_dev's bin mean (np.bincount's chain from +0.0, divided by the count; empty: NaN).  Points
+ * [nmean, nmean + ngauss): picaso_lsf_convolve_dev's window with centre[p], den[p], in its order of sums.  Windows may
+ * overlap, repeat and be empty.  scale: a column's element is v[i] * scale, one rounded product formed before the sum or
+ * the weight (the reference scales the flux, then bins: driver.py:230); scale == 1.0: no product, and every point has the
+ * bits of the member entry above for the same range.  wl (nwno; may be NULL when ngauss == 0), lo, hi, col, centre, den
+ * (nmean + ngauss; centre and den are read for the Gaussian points only): device.  lo / hi are clamped into [0, nwno] and a
+ * point whose col lies outside [0, nmean + ngauss) writes nothing.  rows: host; out: device (nrows, nmean + ngauss).  At
+ * most two launches on the context's stream, no synchronisation.
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_instruments_reduce_dev(picaso_ctx *ctx, long nwno, const double *wl /* (nwno); may be NULL when ngauss == 0 */,
+                                  int nmean, int ngauss, const int *lo, const int *hi, const int *col,
+                                  const double *centre, const double *den, double scale,
+                                  int nrows, const picaso_regrid_row *rows, double *out /* (nrows, nmean + ngauss) */);
+
 /* ---- model grids fitted to data (reference analyze.py:305-388 fit_grid, :923-1000 custom_interp) ------------------------
  * grid: device (nrows, nwave), the spectra of a grid of models.  Sample s is a table of kcount[s] (row, weight) pairs and
  * a divisor, and its column i is

@@ -168,12 +168,18 @@ def resolve(convolve, opa):
     raise Exception("convolve must be a convolve_plan() or {'wl': array, 'R': scalar_or_array}")
 
 
-def reduction(regrid, convolve, opa):
-    """The plan of a public call from its two keywords (None: a plain call); both at once is an error."""
-    if regrid is not None and convolve is not None:
+def reduction(regrid, convolve, opa, instruments=None):
+    """The plan of a public call from its three keywords (None: a plain call); more than one at once is an error."""
+    given = sum(k is not None for k in (regrid, convolve, instruments))
+    if given > 1 and instruments is None:
         raise Exception("regrid= and convolve= are two ways from the model grid to the data's: give one of them")
+    if given > 1:
+        raise Exception("regrid=, convolve= and instruments= are three ways from the model grid to the data's: give one "
+                        "of them (instruments= takes a binned and a convolved data set together)")
     if regrid is not None:
         return _regrid.resolve(regrid, opa)
     if convolve is not None:
         return resolve(convolve, opa)
+    if instruments is not None:
+        return _regrid.resolve_instruments(instruments, opa)
     return None

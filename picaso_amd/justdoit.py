@@ -33,7 +33,7 @@ from .options import Options                                                    
 from .planes import cloud_free_top as _cloud_free_top                               # noqa: F401  (jdi._cloud_free_top)
 from .convolve import ConvolvePlan, conv_non_uniform_R, convolve_plan               # noqa: F401  (jdi.convolve_plan)
 from .solvebatch import SolveBatch
-from .regrid import RegridPlan, regrid_plan                                         # noqa: F401  (jdi.regrid_plan)
+from .regrid import RegridPlan, regrid_plan, InstrumentsPlan, instruments_plan     # noqa: F401  (jdi.regrid_plan)
 from .contribution import thermal_contribution, transmission_contribution           # noqa: F401  (jdi.thermal_contribution)
 from .attenuation import cloud_optics_1d, heatmap_taus, photon_attenuation, taumap   # noqa: F401  (jdi.photon_attenuation)
 from .opacity_factory import compute_ck, compute_ck_molecular                        # noqa: F401  (jdi.compute_ck)
@@ -175,6 +175,10 @@ _UNIT_CGS = {   # plain-string stand-ins for the astropy units of the reference'
     "g": 1.0, "kg": 1e3, "mjup": 1.8981246e30, "m_jup": 1.8981246e30, "jupitermass": 1.8981246e30,
     "mearth": 5.9721679e27, "m_earth": 5.9721679e27, "earthmass": 5.9721679e27, "msun": 1.98840987e33,
     "m_sun": 1.98840987e33, "au": 1.495978707e13,
+    # the lengths and angles of the reference's sample retrieval configuration (driver.toml: distance = {unit='parsec'},
+    # separation = {unit='AU'}; the phase of driver.py:502-505); an angle's "cgs" value is the radian
+    "parsec": 3.0856775814913674e18, "pc": 3.0856775814913674e18,
+    "radian": 1.0, "radians": 1.0, "rad": 1.0, "degree": np.pi / 180.0, "degrees": np.pi / 180.0, "deg": np.pi / 180.0,
 }
 
 
@@ -192,7 +196,7 @@ def _to_cgs(value, unit, what):
                             % (what, unit, sorted(_UNIT_CGS)))
         return float(value) * _UNIT_CGS[key]
     if hasattr(unit, "to") or hasattr(value * unit, "to"):            # astropy
-        target = {"gravity": "cm/s2", "radius": "cm", "mass": "g"}[what]
+        target = {"gravity": "cm/s2", "radius": "cm", "mass": "g", "distance": "cm", "angle": "rad"}[what]
         return float((value * unit).to(target).value)
     raise Exception("%s: cannot interpret unit %r" % (what, unit))
 
@@ -1334,11 +1338,21 @@ class inputs:
                             "opacity object that was built with one")
         self._chemistry_3d(table, "premix_3d")
 
-    def chemeq_visscher_1060(self, *a, **k):
-        raise NotImplementedError("chemeq_visscher_1060 (the chemistry grids shipped with the reference) is not implemented: "
-                                  "use an opacity object that carries full_abunds")
+    def chemeq_visscher_1060(self, c_o=None, log_mh=None):
+        """Abundances of the profile from the 1060-point Visscher grid nearest to ``c_o`` (relative to solar) and ``log_mh``
+        (reference justdoit.py:3066-3090): ``chemistry.visscher_1060`` chooses and reads the file under
+        ``$picaso_refdata/chemistry/visscher_grid_1060``, ``chem_interp`` adds its species to the profile, on the host.
+        Without both arguments (``premix_atmosphere``'s ``'visscher'`` branch calls it so) it says what is missing."""
+        from . import chemistry
+        if c_o is None or log_mh is None:
+            raise NotImplementedError("chemeq_visscher_1060 needs c_o (relative to solar) and log_mh to choose its visscher "
+                                      "grid file: call chemeq_visscher_1060(c_o, log_mh), or use an opacity object that "
+                                      "carries full_abunds")
+        self.chem_interp(chemistry.visscher_1060(c_o, log_mh))
 
-    chemeq_visscher_2121 = chemeq_visscher_1060
+    def chemeq_visscher_2121(self, *a, **k):
+        raise NotImplementedError("chemeq_visscher_2121 is not implemented as a method: the 1-D route is "
+                                  "chem_interp(chemistry.visscher_2121(cto_absolute, log_mh))")
 
     def premix_atmosphere_photochem(self, *a, **k):
         raise NotImplementedError("premix_atmosphere_photochem needs the photochem package, which is not part of this package")
@@ -1356,8 +1370,10 @@ class inputs:
         disequilibrium climate loop asks for it before every quench.  The quench switch without any Kzz (``find_kzz()`` is
         ``None``: not a disequilibrium run, which prepares ``inputs['atmosphere']['kzz']``) stays a ``NotImplementedError``:
         the switch could not be honoured.  ``chem_params['no_ph3']`` then zeroes PH3.
-        Without a table and without a ``chem_method`` the reference's exception is raised.  Not implemented: the
-        ``visscher`` grids, photochem, and ``vol_rainout`` / ``cold_trap`` (which need virga's vapour-pressure curves)."""
+        Without a table and without a ``chem_method`` the reference's exception is raised.  Not implemented: a
+        ``'visscher'`` ``chem_method`` (as in the reference the branch calls ``chemeq_visscher_1060()`` without ``c_o`` and
+        ``log_mh``, which says so), photochem, and ``vol_rainout`` / ``cold_trap`` (which need virga's vapour-pressure
+        curves)."""
         table = getattr(opa, "full_abunds", None)
         approx = self.inputs["approx"]
         chem_method = approx.get("chem_method", None)
@@ -1591,13 +1607,17 @@ class inputs:
         return all_out
 
     def spectrum(self, opacityclass, calculation="reflected", dimension="1d", full_output=False,
-                 plot_opacity=False, as_dict=True, devices=None, gather="host", options=None, regrid=None, convolve=None):
+                 plot_opacity=False, as_dict=True, devices=None, gather="host", options=None, regrid=None, convolve=None,
+                 instruments=None):
         """Run the spectrum (reference justdoit.py:4779-4840).  ``devices=N`` (or a list of device indices):
         the wavelength grid is cut into N contiguous blocks, one per GPU (``picaso(devices=...)``).  ``regrid``
         (``regrid_plan(...)``, ``{'R': r}`` or ``{'newx': array}``): every spectral array comes back binned on the device,
         bit for bit ``mean_regrid`` of the plain call's (``picaso(regrid=...)``).  ``convolve`` (``convolve_plan(...)`` or
         ``{'wl': array, 'R': scalar_or_array}``): every spectral array comes back convolved with a Gaussian line-spread
-        function of resolving power ``R`` at the wavelengths ``wl``, on the device (``picaso(convolve=...)``)."""
+        function of resolving power ``R`` at the wavelengths ``wl``, on the device (``picaso(convolve=...)``).  ``instruments``
+        (``instruments_plan(...)`` or ``{name: {'newx': x} | {'wl': wl, 'R': R}}``): several data sets, binned or convolved
+        each, from this one spectrum in one launch (``picaso(instruments=...)``; a plan with a ``scale`` scales every spectral
+        array, the flux ratios too).  One of the three at most."""
         if dimension not in ("1d", "3d"):
             raise Exception("dimension must be '1d' or '3d'")
         have = self.inputs["atmosphere"].get("profile" if dimension == "1d" else "profile_3d")
@@ -1608,10 +1628,10 @@ class inputs:
             raise Exception("Need to set gravity with the gravity() function")
         return picaso(self, opacityclass, dimension=dimension, calculation=calculation,
                       full_output=full_output, plot_opacity=plot_opacity, as_dict=as_dict, devices=devices,
-                      gather=gather, options=options, regrid=regrid, convolve=convolve)
+                      gather=gather, options=options, regrid=regrid, convolve=convolve, instruments=instruments)
 
     def spectrum_async(self, opacityclass, calculation="reflected", dimension="1d", full_output=False, as_dict=True,
-                       options=None, regrid=None, convolve=None):
+                       options=None, regrid=None, convolve=None, instruments=None):
         """``spectrum()`` without the wait: set-up and every launch of this spectrum are enqueued (result copies
         included) and a ``PendingSpectrum`` comes back at once; its ``result()`` is ``spectrum()``'s dictionary, bit for
         bit.  A retrieval that asks for sample i + 1 before it reads sample i hides the host set-up of one call behind the
@@ -1626,13 +1646,13 @@ class inputs:
         if self.inputs["planet"]["gravity"] is None:
             raise Exception("Need to set gravity with the gravity() function")
         return picaso_async(self, opacityclass, dimension=dimension, calculation=calculation, full_output=full_output,
-                            as_dict=as_dict, options=options, regrid=regrid, convolve=convolve)
+                            as_dict=as_dict, options=options, regrid=regrid, convolve=convolve, instruments=instruments)
 
 
 @_lib.serialized
 def picaso(bundle, opacityclass, dimension="1d", calculation="reflected", full_output=False,
            plot_opacity=False, as_dict=True, defer=False, devices=None, gather="host", options=None, _raw=False,
-           _shared=None, _batch=None, regrid=None, convolve=None, _reduce=None):
+           _shared=None, _batch=None, regrid=None, convolve=None, _reduce=None, instruments=None):
     """Spectrum driver (reference ``picaso()``, justdoit.py:65-621).
 
     The work is ``spectrum.Spectrum``: plan (ATMSETUP, opacity planes) -> enqueue (every leg's solver launches) ->
@@ -1658,10 +1678,22 @@ def picaso(bundle, opacityclass, dimension="1d", calculation="reflected", full_o
     ``conv_non_uniform_R(array, 1e4 / wavenumber, R, wl)`` of itself -- within ``(2 counts + 10) 2^-53`` of
     ``conv(|array|)``: the weights are formed on the device once for all arrays (csrc/convolve.hip) and summed in an order
     of their own -- and ``convolve_counts`` (model columns within 39 sigma of every point) added.  The rest as for
-    ``regrid``.  ``_reduce``: either plan, resolved by the caller."""
+    ``regrid``.
+
+    ``instruments`` (an ``instruments_plan(...)`` or ``{name: {'newx': x} | {'wl': wl, 'R': R}}``; not together with the
+    other two): several data sets from one spectrum.  Every spectral array has the values of ``regrid=`` or ``convolve=``
+    for each instrument, bit for bit, one behind the other in the order given; ``wavenumber`` is concatenated likewise,
+    ``instrument_slices`` (``{name: slice}``) cuts them apart and ``instrument_counts`` holds the members' counts.  One
+    ``picaso_instruments_reduce_dev`` call behind the legs (csrc/instruments.hip).  A plan made with a ``scale``
+    (``instruments_plan(..., scale=k)``, ``plan.with_scale(k)``) multiplies every spectral array of the call by it, the
+    ratios ``fpfs_*``, ``albedo`` and ``transit_depth`` too: it is meant for a call that reads ``thermal``.  ``_reduce``: any of the three plans,
+    resolved by the caller."""
     opt = _options.current(options)
-    plan = _reduce if _reduce is not None else _convolve.reduction(regrid, convolve, opacityclass)
+    plan = _reduce if _reduce is not None else _convolve.reduction(regrid, convolve, opacityclass, instruments)
     if plan is not None and (devices is not None or _raw or _shared is not None):
+        if plan.kind == "instruments":
+            raise NotImplementedError("instruments= with devices=N is not supported: bins and windows straddle the "
+                                      "wavelength blocks, and no run with more than one rank has been made")
         if plan.kind == "convolve":
             raise NotImplementedError("convolve= with devices=N is not supported: windows straddle the wavelength "
                                       "blocks, and no run with more than one rank has been made")
@@ -1768,7 +1800,7 @@ class PendingSpectrum:
 
 @_lib.serialized
 def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", full_output=False, as_dict=True,
-                 options=None, regrid=None, convolve=None):
+                 options=None, regrid=None, convolve=None, instruments=None):
     """``picaso()`` up to and including the last launch; returns a ``PendingSpectrum``.
 
     What the C driver covers (``onecall.prepare``: the plain 1-D Toon / SH and 3-D spectra) is enqueued through it on one of
@@ -1777,12 +1809,12 @@ def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", 
     patchy clouds, level fluxes, ``full_output`` ...) is ``picaso(defer=True)`` with its result copies already on the
     stream.  Either way the dictionary is the one ``picaso()`` returns for the same inputs.  The case must not be given a
     new star before ``result()`` (the flux ratios are formed there); atmosphere, clouds and geometry may change at once.
-    ``regrid`` / ``convolve``: as ``picaso`` -- the reduction is enqueued behind the legs and ``result()`` returns the binned
-    or convolved dictionary."""
+    ``regrid`` / ``convolve`` / ``instruments``: as ``picaso`` -- the reduction is enqueued behind the legs and ``result()``
+    returns the binned or convolved dictionary."""
     from . import onecall
     from . import driver as drv
     opt = _options.current(options)
-    plan = _convolve.reduction(regrid, convolve, opacityclass)
+    plan = _convolve.reduction(regrid, convolve, opacityclass, instruments)
     legs = any(leg in calculation for leg in ("reflected", "thermal", "transmission"))
     if not full_output and not legs:
         out = {"wavenumber": opacityclass.wno} if plan is None else plan.empty_output()
@@ -1824,7 +1856,7 @@ def picaso_async(bundle, opacityclass, dimension="1d", calculation="reflected", 
 # ------------------------------------------------------------------------------------------------
 @_lib.serialized
 def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=False, as_dict=True, batch_size=4,
-                   options=None, regrid=None, convolve=None):
+                   options=None, regrid=None, convolve=None, instruments=None):
     """``[case.spectrum(opacityclass, calculation) for case in cases]`` (1-D) with the solvers of up to
     ``batch_size`` spectra in ONE launch each: what a retrieval or a model grid asks of the reference one
     ``spectrum()`` call and one process at a time (driver.py:405-426).  ``cases``: ``inputs`` objects, each with its
@@ -1834,10 +1866,16 @@ def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=Fal
     host sets up and enqueues chunk k + 1, and only then waits for k's result copies (``picaso_memcpy_d2h_async`` into
     pinned blocks, ``picaso_mark_wait``) and runs its integrals.  HBM: the planes of a chunk stay resident until its
     launch (0.8 GB per cloudy 1e5 x 90 spectrum, 0.2 GB per cloud-free one), two chunks at a time.  ``regrid`` /
-    ``convolve``: as ``picaso``; one plan is shared by all members."""
+    ``convolve`` / ``instruments``: as ``picaso``; one plan is shared by all members.  ``instruments`` may also be a list of
+    ``InstrumentsPlan``s, one per case (a retrieval whose flux scale is fitted: ``plan.with_scale(k)`` per sample)."""
     opt = _options.current(options)
-    plan = _convolve.reduction(regrid, convolve, opacityclass)
     cases = list(cases)
+    if isinstance(instruments, (list, tuple)):
+        if len(instruments) != len(cases):
+            raise Exception("spectrum_batch: %d instrument plans for %d cases" % (len(instruments), len(cases)))
+        plans = [_convolve.reduction(regrid, convolve, opacityclass, ins) for ins in instruments]
+    else:
+        plans = [_convolve.reduction(regrid, convolve, opacityclass, instruments)] * len(cases)
     outs = []
     in_flight = []                 # chunks whose launches and result copies are on the stream
     B = max(1, int(batch_size))
@@ -1850,7 +1888,7 @@ def spectrum_batch(cases, opacityclass, calculation="reflected", full_output=Fal
                 raise Exception("Need to set gravity with the gravity() function")
         batch = SolveBatch()
         fins = []
-        for case in chunk:
+        for case, plan in zip(chunk, plans[c0:c0 + B]):
             fins.append(picaso(case, opacityclass, dimension="1d", calculation=calculation, full_output=full_output,
                                as_dict=as_dict, defer=True, options=opt, _batch=batch, _reduce=plan))
         batch.flush()

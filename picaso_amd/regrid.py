@@ -155,6 +155,144 @@ def resolve(regrid, opa):
     raise Exception("regrid must be a regrid_plan(), {'R': r} or {'newx': array}")
 
 
+class InstrumentsPlan(Reduction):
+    """Several instruments on one wavenumber grid: the points of its members -- a ``RegridPlan`` (bin means) or a
+    ``ConvolvePlan`` (Gaussian windows) each, with their own host tables, unchanged -- concatenated in the given order, for
+    ONE call of ``picaso_instruments_reduce_dev`` (csrc/instruments.hip) behind the legs: the reference's loop over
+    ``observation_data`` (driver.py:232-236) without a second spectrum and without the full-resolution copies.
+
+    ``members`` (``{name: plan}``), ``slices`` (``{name: slice}`` into every output array), ``nout`` (the sum),
+    ``out_wavenumber`` and ``counts`` (the members', concatenated), and per point in instrument order ``lo``, ``hi`` (int32),
+    ``centre``, ``den`` (0.0 at a mean point, which reads neither).  The device tables hold the same points with the mean
+    points first: device point ``p`` is instrument point ``col[p]``, ``nmean`` of them are means, ``ngauss`` Gaussian.
+    ``scale``: every column of EVERY row of the call is multiplied by it before it is summed (one rounded product), as the
+    reference scales the flux before it bins it (driver.py:230) -- the flux ratios of a planet (``fpfs_*``), ``albedo``
+    and ``transit_depth`` included, so a scale belongs to a call that reads ``thermal`` alone, as ``retrieve.MODEL``'s; ``with_scale(k)`` gives the same plan, tables shared, with another scale."""
+    kind, counts_key = "instruments", "instrument_counts"
+
+    def __init__(self, wno, members, scale=1.0):
+        if not members:
+            raise Exception("instruments_plan: at least one instrument is needed")
+        self.members = dict(members)
+        lo, hi, centre, den, is_mean, self.slices = [], [], [], [], [], {}
+        n0 = 0
+        for name, m in self.members.items():
+            if isinstance(m, RegridPlan):
+                lo.append(m.start[:-1]), hi.append(m.start[1:])
+                centre.append(np.zeros(m.nout)), den.append(np.zeros(m.nout))
+            elif m.kind == "convolve":
+                lo.append(m.lo), hi.append(m.hi), centre.append(m.centre), den.append(m.den)
+            else:
+                raise Exception("instruments_plan: instrument %r is neither a regrid nor a convolve plan" % (name,))
+            is_mean.append(np.full(m.nout, isinstance(m, RegridPlan)))
+            self.slices[name] = slice(n0, n0 + m.nout)
+            n0 += m.nout
+        first = next(iter(self.members.values()))
+        self.wno, self.nwno, self.nout = wno, first.nwno, n0
+        self.lo, self.hi = np.concatenate(lo).astype(np.int32), np.concatenate(hi).astype(np.int32)
+        self.centre, self.den = np.concatenate(centre).astype(float), np.concatenate(den).astype(float)
+        is_mean = np.concatenate(is_mean)
+        self.col = np.concatenate((np.flatnonzero(is_mean), np.flatnonzero(~is_mean))).astype(np.int32)
+        self.nmean, self.ngauss = int(is_mean.sum()), int((~is_mean).sum())
+        self.out_wavenumber = np.concatenate([m.out_wavenumber for m in self.members.values()])
+        self.counts = np.concatenate([np.asarray(m.counts, dtype=np.int64) for m in self.members.values()])
+        for a in (self.lo, self.hi, self.centre, self.den, self.col, self.out_wavenumber, self.counts):
+            a.flags.writeable = False
+        self.scale = float(scale)
+        self._dev = {}
+        self._siblings = {}                             # scale -> plan, shared by every sibling (with_scale)
+        _plans.add(self)
+
+    def with_scale(self, scale):
+        """This plan with another ``scale``.  The sibling shares the host tables, the device tables (``_dev``, which
+        ``destroy_context`` empties through any of them: every sibling is registered) and the record of siblings already
+        made, so equal scales give the same object again."""
+        scale = float(scale)
+        if scale == self.scale:
+            return self
+        import copy
+        other = self._siblings.get(scale)
+        if other is None:
+            if len(self._siblings) > 64:
+                self._siblings.clear()
+            other = self._siblings[scale] = copy.copy(self)      # shallow: _dev and _siblings are the same objects
+            other.scale = scale
+            _plans.add(other)
+        return other
+
+    def device_tables(self, ctx):
+        """``(ints, doubles, model_wl)`` in HBM on ``ctx``'s device, in device order: ``ints`` holds ``lo``, ``hi``, ``col``
+        (int32, carried by a float64 DeviceArray of the same bytes), ``doubles`` holds ``centre`` then ``den``, ``model_wl``
+        is the first Gaussian member's (None without one)."""
+        key = getattr(ctx, "value", ctx)
+        hit = self._dev.get(key)
+        if hit is None:
+            n = self.nout
+            ints = np.zeros((3 * n + 1) // 2 * 2, dtype=np.int32)
+            ints[:n], ints[n:2 * n], ints[2 * n:3 * n] = self.lo[self.col], self.hi[self.col], self.col
+            dbl = np.concatenate((self.centre[self.col], self.den[self.col]))
+            wl = next((m.device_tables(ctx)[0] for m in self.members.values() if m.kind == "convolve"), None)
+            hit = self._dev[key] = (DeviceArray.from_host(ints.view(np.float64), ctx), DeviceArray.from_host(dbl, ctx), wl)
+        return hit
+
+    def launch(self, ctx, nrows, crows, out_addr):
+        tables = d_int, d_dbl, d_wl = self.device_tables(ctx)
+        n = self.nout
+        _lib.check(_lib.load().picaso_instruments_reduce_dev(
+            ctx, self.nwno, _lib.addr(d_wl), self.nmean, self.ngauss, d_int.addr, d_int.addr + 4 * n, d_int.addr + 8 * n,
+            d_dbl.addr, d_dbl.addr + 8 * n, self.scale, nrows, crows, out_addr), ctx)
+        return tables
+
+    def output(self, vals, lists, bond_albedo=None, effective_temperature=None):
+        out = output(self, vals, lists, bond_albedo, effective_temperature)
+        out["instrument_slices"] = dict(self.slices)
+        return out
+
+    def empty_output(self):
+        return dict(Reduction.empty_output(self), instrument_slices=dict(self.slices))
+
+
+def _member_key(spec):
+    if not isinstance(spec, dict) or not spec or not (set(spec) <= {"newx", "R"} or set(spec) == {"wl", "R"}):
+        raise Exception("instruments: every instrument is {'newx': array}, {'R': r} (bins) or {'wl': array, 'R': r} "
+                        "(a Gaussian line-spread function)")
+    return tuple((k, np.shape(spec[k]), np.ascontiguousarray(spec[k], dtype=float).tobytes()) for k in sorted(spec))
+
+
+def instruments_plan(opacityclass_or_wno, instruments, scale=1.0):
+    """The ``InstrumentsPlan`` of a wavenumber grid (an opacity object, or the array itself) for ``instruments``:
+    ``{name: {'newx': x}}`` (bins around ``x``, ``mean_regrid``'s; ``{'R': r}`` likewise) or ``{name: {'wl': wl, 'R': R}}``
+    (``conv_non_uniform_R``'s Gaussian at the wavelengths ``wl``), in the order the output is wanted.  With an opacity
+    object the plan is kept on it by content, as its members are: equal names and values give the same plan again."""
+    from . import convolve as _convolve
+    if not isinstance(instruments, dict) or not instruments:
+        raise Exception("instruments must be a non-empty dictionary {name: {'newx': x} | {'wl': wl, 'R': R}}")
+    wno = getattr(opacityclass_or_wno, "wno", None)
+
+    def member(spec):
+        if "wl" in spec:
+            return _convolve.convolve_plan(opacityclass_or_wno, spec["wl"], spec["R"])
+        return regrid_plan(opacityclass_or_wno, newx=spec.get("newx"), R=spec.get("R"))
+    keys = tuple((name, _member_key(spec)) for name, spec in instruments.items())
+    if wno is None:
+        return InstrumentsPlan(opacityclass_or_wno, {n: member(s) for n, s in instruments.items()}, scale)
+    cache = opacityclass_or_wno.__dict__.setdefault("_instrument_plans", {})
+    hit = cache.get(keys)
+    if hit is None or hit.wno is not wno:
+        if len(cache) > 16:
+            cache.clear()
+        hit = cache[keys] = InstrumentsPlan(wno, {n: member(s) for n, s in instruments.items()}, 1.0)
+    return hit.with_scale(scale)
+
+
+def resolve_instruments(instruments, opa):
+    """``instruments=`` of the public calls -> a plan on ``opa``'s grid: an ``InstrumentsPlan`` or the dictionary of
+    ``instruments_plan``."""
+    if isinstance(instruments, InstrumentsPlan):
+        return instruments.check_grid(opa)
+    return instruments_plan(opa, instruments)
+
+
 def spectral_rows(albedo, thermal, transit, stellar, sa, radius_star, planet_radius):
     """The rows of one call in the order of the output dictionary -- ``[(key, op, a, b, c, k1, k2)]`` -- and the keys that
     stay list-valued placeholders, exactly where ``_post_reflected`` / ``_post_thermal`` / ``_post_final`` put them
