@@ -79,9 +79,14 @@ __global__ __launch_bounds__(TRANSIT_BLOCK * TRANSIT_WAVES) void k_transit(const
                 for (int j = 0; j < i0 + STEP * k; ++j)
                     t[k] = t[k] + (2.0 * tl[(i0 + STEP * k - j - 1) * TRANSIT_BLOCK]) * dl[(long)(i0 + STEP * k) * n + j];
         }
+        // exp(-800) is 0 like every np.exp below -745.2, and fexp(-t) is 0 as well while its range reduction holds (a slant
+        // depth of 1e6 gave 0 before the clamp and gives it now), so no finite depth that was right changes a bit.  Far past
+        // it the reduction has nothing left to stand on: a layer of DTAU = inf or 1e300 gave NaN where np.exp(-inf) is 0 and
+        // the chord counts in full (k_thermal_cf and k_transit_cf clamp alike).  The comparison is false for a NaN: it stays.
 #pragma unroll
         for (int k = 0; k < TRANSIT_ROWS; ++k)
-            if (i0 + STEP * k < n && nt < MAXT) term[nt++] = (1.0 - fexp(-t[k])) * zdz[i0 + STEP * k];   // (:2660-2661)
+            if (i0 + STEP * k < n && nt < MAXT)
+                term[nt++] = (1.0 - fexp(-(t[k] > 800.0 ? 800.0 : t[k]))) * zdz[i0 + STEP * k];           // (:2660-2661)
     }
     __syncthreads();                                    // every wave is done with TAU: the tile now takes the terms
     {

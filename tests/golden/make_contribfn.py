@@ -6,7 +6,8 @@
 (:1697-1779) on synthetic ``full_output`` dictionaries: 150 wavenumbers (two full 64-lane tiles and a partial one) with a
 gap and one isolated point, so that R = 60 leaves bins empty and one bin with a single column; 13, 3 and 2 levels (the
 last two: fewer chords than waves, a single layer, an empty thermal result); a T(p) that is not isothermal, a cloud slab,
-one opaque layer (dtau 1e4), one all-zero column and one column with a NaN in taugas.
+one opaque layer (dtau 1e4), one all-zero column and one column with a NaN in taugas.  The scenes and the numpy restatement
+of get_transit_1d are tests/contribfn_cases.py's, which the tests share (they cannot import this file: it loads the reference).
 
 Stored per scene ``s<nlevel>``: the inputs, the reference's thermal CF for tau_max 1 and 1e3 and its CF_bin (tau_max 1,
 R = 60), the reference's transmission CF (its own arguments: layer pressure in bar, layer temperature, constants 1), and
@@ -23,11 +24,12 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import ref_shim  # noqa: E402
+from contribfn_cases import COL_NAN, COL_OPAQUE, COL_ZERO, NWNO, scene, transit_terms  # noqa: E402
 
-NWNO, R_BIN = 150, 60
-COL_OPAQUE, COL_ZERO, COL_NAN = 17, 70, 131          # one in each 64-lane tile
+R_BIN = 60
 TAU_MAXES = (1.0, 1e3)
 
 
@@ -43,77 +45,6 @@ def _justplotit():
         if parent and isinstance(sys.modules.get(parent), ref_shim._Dummy) and isinstance(mod, ref_shim._Dummy):
             setattr(sys.modules[parent], child, mod)
     return importlib.import_module("picaso.justplotit")
-
-
-def scene(nlevel):
-    """A ``full_output`` dictionary with the reference's keys."""
-    nlayer = nlevel - 1
-    rng = np.random.default_rng(100 + nlevel)
-    wno = np.concatenate((np.linspace(2000.0, 2400.0, 99), [2700.0], np.linspace(3000.0, 3300.0, 50)))
-    assert wno.size == NWNO
-    plev = np.logspace(-5, 1.5, nlevel)                                    # bar
-    x = (np.log10(plev) + 5) / 6.5
-    tlev = 220.0 + 1100.0 * x ** 1.5 - 60.0 * np.sin(3 * x)               # not isothermal
-    play, tlay = np.sqrt(plev[1:] * plev[:-1]), 0.5 * (tlev[1:] + tlev[:-1])
-    mmw = np.full(nlayer, 2.3) + 0.02 * np.arange(nlayer)
-    k_b, amu, g, radius = 1.380649e-16, 1.66053906660e-24, 2500.0, 7.0e9
-    scale_h = k_b * tlay / (mmw * amu * g)
-    dz_lay = scale_h * np.log(plev[1:] / plev[:-1])
-    z = radius + np.concatenate((np.cumsum(dz_lay[::-1])[::-1], [0.0]))    # decreasing, the bottom at `radius`
-    dz = np.concatenate(([dz_lay[0]], dz_lay))
-    # the reference's call makes every slant depth 1e-6 k_b / amu = 83 times the physical one (bar, constants 1), some
-    # 5e3 times the vertical depth on this planet: the column density is scaled up so that slant depths stay of order one
-    colden = 5.0e3 * (plev[1:] - plev[:-1]) * 1e6 / g
-    lam = (wno - wno[0]) / (wno[-1] - wno[0])
-    depth = np.diff(plev)[:, None] / plev[-1]
-    taugas = 30.0 * depth ** 0.8 * 10.0 ** (1.5 * np.sin(9 * lam)[None, :] - 1.0) * rng.uniform(0.7, 1.3, (nlayer, NWNO))
-    tauray = 2.0 * depth * (wno[None, :] / 3300.0) ** 4
-    taucld = np.zeros((nlayer, NWNO))
-    slab = slice(nlayer // 2, nlayer // 2 + max(1, nlayer // 4))
-    taucld[slab] = 0.4 * (1.0 + 0.3 * lam)[None, :]
-    k_opaque = nlayer // 3
-    taugas[k_opaque, COL_OPAQUE] = 1e4
-    taugas[:, COL_ZERO] = tauray[:, COL_ZERO] = taucld[:, COL_ZERO] = 0.0
-    taugas[min(1, nlayer - 1), COL_NAN] = np.nan
-    shape3 = (nlayer, NWNO, 1)
-    return {"wavenumber": wno, "taugas": taugas.reshape(shape3), "taucld": taucld.reshape(shape3),
-            "tauray": tauray.reshape(shape3),
-            "layer": {"pressure": play, "temperature": tlay, "column_density": colden, "mmw": mmw},
-            "level": {"pressure": plev, "temperature": tlev, "z": z, "dz": dz}}
-
-
-def transit_terms(full, dtype):
-    """get_transit_1d (reference fluxes.py:2581-2663) with the reference's arguments (justplotit.py:1728-1738), restated
-    in ``dtype``: ``(F, D)`` -- the transit depth and ``D[k] = sum_{i>k} z_i dz_i exp(-(TAUALL_i - c_ik)) (1 - exp(-c_ik))``,
-    so that ``norm - F_k = 2 D[k]`` (rstar = 1)."""
-    T = dtype
-    z, dz = full["level"]["z"].astype(T), full["level"]["dz"].astype(T)
-    player, tlayer = full["layer"]["pressure"].astype(T), full["layer"]["temperature"].astype(T)
-    colden, mmw = full["layer"]["column_density"].astype(T), full["layer"]["mmw"].astype(T)
-    dtau = ((full["taugas"][:, :, 0] + full["taucld"][:, :, 0]) + full["tauray"][:, :, 0]).astype(T)
-    n = z.size
-    dl = np.zeros((n, n), dtype=T)
-    seg = T(0)
-    for i in range(n):
-        for j in range(i):
-            ref, inner, outer = z[i], z[i - j], z[i - j - 1]
-            if inner != ref and outer != ref:
-                seg = np.sqrt(outer ** 2 - ref ** 2) - np.sqrt(inner ** 2 - ref ** 2)
-            elif inner == ref:
-                seg = np.sqrt(outer ** 2 - ref ** 2)
-            dl[i, j] = seg * player[i - j - 1] / tlayer[i - j - 1]
-    tau = dtau / colden[:, None] * mmw[:, None]
-    tauall = np.zeros((n, dtau.shape[1]), dtype=T)
-    for i in range(n):
-        for j in range(i):
-            tauall[i] = tauall[i] + 2 * tau[i - j - 1] * dl[i, j]
-    F = (z.min() / T(1)) ** 2 + T(2) * ((T(1) - np.exp(-tauall)) * (z * dz)[:, None]).sum(axis=0)
-    D = np.zeros((n - 1, dtau.shape[1]), dtype=T)
-    for k in range(n - 1):
-        for i in range(k + 1, n):
-            c = 2 * tau[k] * dl[i, i - k - 1]
-            D[k] = D[k] + (z[i] * dz[i]) * np.exp(-(tauall[i] - c)) * -np.expm1(-c)
-    return F, D
 
 
 def main():
