@@ -1353,6 +1353,43 @@ int picaso_mie_cloud_tables_dev(picaso_ctx *ctx, int S, int K, int nlayer, int n
                                 int rmax, const double *wgt, const double *factor, const double *inside, double *work,
                                 double *out /* (S, 3, nlayer, nwave) */);
 
+/* ---- the rows of an opacity database (reference opacity_factory.py:280-362 restructure_opacity; :850-1055
+ * insert_molecular_1460; csrc/contfactory.hip) ----
+ * picaso_continuum_rows_dev replaces, for ntemp temperatures of a CIA file in one call, the reference's loop over
+ * temperatures and pairs.  Every array is device memory, built on the host in numpy and uploaded by the caller
+ * (picaso_amd/opacity_factory.py: continuum_rows):
+ *   old_wno (nold, nondecreasing), log_opa (ntemp, nmol, nold): the file's grid and log10 opacities;
+ *   new_wno (nwno): the new grid;
+ *   ov_wno (nov, ascending), ov_log (ntemp, nov): the H2H2 overtone table's grid and, per temperature, log10 of its nearest
+ *   column; bell_wno (nbell, ascending), bell_kappa (ntemp, nbell): Bell's H2- grid and, per temperature, the nearest row;
+ *   par (ntemp, picaso_continuum_npar()): what depends on the temperature alone, in the order of csrc/contfactory.hip's
+ *   ContPar (switches as 0.0 / 1.0).
+ * out (ntemp, nmol + 3, nwno): the pairs in the file's order, then H2-, H-bf, H-ff.  Per point: np.interp with fills of -33
+ * (numpy's bracket, knot rule and NaN retry) and 10**x (within 4 ulp; -33 itself gives par's own 10**-33); for row h2h2
+ * (-1: there is none) the overtone override inside [ov_wno[0], ov_wno[nov - 1]] and the Linsky fill where the value is 1e-33
+ * and wno >= 1000; np.interp of Bell's row with fills of 1e-33 (bit for bit); John's H-bf polynomial; the Bell-Berrington
+ * H-ff sums (bit for bit).  Products, sums and IEEE quotients in numpy's order, nothing contracted.
+ * smooth != 0: a temperature whose H2H2 row took a Linsky point below 12000 cm-1 has the points [smooth_lo, smooth_lo +
+ * smooth_n) of that row replaced by their median filter of `window` points (odd), zeros beyond the region's ends, as
+ * scipy.signal.medfilt: an exact order statistic of the unfiltered values, by an LDS sort while window <= lds_cap and by a
+ * radix select beyond (lds_cap: 0 = the default and largest, 8 192).  Values must not be NaN there.
+ * work: device scratch of ntemp * (smooth_n + 1) doubles.  Returns after the launches.  ntemp <= 65 535 per call.
+ * Bad arguments: an error code, picaso_last_error says which, nothing is launched. */
+int picaso_continuum_npar(void);
+int picaso_continuum_rows_dev(picaso_ctx *ctx, int ntemp, int nmol, int h2h2, long nold, const double *old_wno,
+                              const double *log_opa, long nwno, const double *new_wno, int nov, const double *ov_wno,
+                              const double *ov_log, int nbell, const double *bell_wno, const double *bell_kappa,
+                              const double *par, long smooth_lo, long smooth_n, long window, long lds_cap, int smooth,
+                              double *work, double *out /* (ntemp, nmol + 3, nwno) */);
+/* One row of line-by-line cross sections on the points of a new grid (reference opacity_factory.py:1026-1029):
+ *   out[j] = np.interp(out_grid[j], src_grid, src, left, right);   out[j] < floor becomes floor (a NaN stays)
+ * numpy's bracket, knot rule, fills and NaN retry: out is numpy's bit for bit.  All arrays device; src_grid (n_src >= 2,
+ * nondecreasing) and out_grid (n_out) are built on the host.  guess_start, guess_step: as picaso_xsec_axpy_dev.
+ * Returns after the launch.  Errors, nothing launched: n_out < 1, n_src < 2, a row longer than INT_MAX, a NULL array. */
+int picaso_xsec_resample_dev(picaso_ctx *ctx, long n_out, double *out, const double *src, long n_src, const double *src_grid,
+                             const double *out_grid, double guess_start, double guess_step, double left, double right,
+                             double floor);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,10 @@ from .contribution import thermal_contribution, transmission_contribution       
 from .attenuation import cloud_optics_1d, heatmap_taus, photon_attenuation, taumap   # noqa: F401  (jdi.photon_attenuation)
 from .opacity_factory import compute_ck, compute_ck_molecular                        # noqa: F401  (jdi.compute_ck)
 from .opacity_factory import compute_ck_premixed, compute_sum_molecular, weighted_sum      # noqa: F401
+from .opacity_factory import (build_skeleton, continuum_avail, continuum_rows, continuum_rows_numpy,   # noqa: F401
+                              create_grid_minR, delete_molecule, get_continuum, get_molecular, insert_hitran_cia,
+                              insert_molecular_1460, insert_wno_grid, molecular_avail, open_local, restruct_continuum,
+                              restructure_opacity)
 from .spectrum import (Spectrum, setup_facets_3d, _atmosphere_block, _bond_denominator, _constant_planes,   # noqa: F401
                        _fetch, _interp_axis, _lon_period, _ones, _post_final, _post_reflected, _post_thermal, _postprocess,
                        _resident_vector, _setup_atmosphere, _trapz_resident)

@@ -16,9 +16,19 @@ climate solver run on) is the same binning of the abundance-weighted sum of the 
 ``jdi.compute_ck_premixed`` forms that sum in HBM (``picaso_xsec_axpy_dev``, csrc/xsecsum.hip: numpy's sum bit for bit) and
 bins it there; ``jdi.weighted_sum`` is the array form of the sum, ``jdi.compute_sum_molecular`` writes the reference's
 intermediate file, ``premix_abundances`` selects the abundances as the reference does.
+
+The other file an opacity object needs, the sqlite DATABASE (``header``, ``molecular``, ``continuum``), is written here too:
+``build_skeleton`` and the readers keep the reference's schema; ``restruct_continuum`` / ``restructure_opacity`` put the CIA
+file and the other continuum sources on a new grid (``continuum_rows``: ``picaso_continuum_rows_dev``, csrc/contfactory.hip,
+with an exact median filter; ``continuum_rows_numpy``: the reference's arithmetic on the host); ``insert_molecular_1460``
+resamples cross-section rows (``picaso_xsec_resample_dev``).  DESIGN section 5q.
 """
 import ctypes
+import glob
+import io
+import math
 import os
+import sqlite3
 
 import numpy as np
 
@@ -767,3 +777,767 @@ def compute_sum_molecular(ck_molecules, og_directory, chemistry_file, output_dir
             if verbose:
                 print("completed", i, p, t)
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the sqlite opacity database: its schema and readers (reference opacity_factory.py:578-739, 1262-1470)
+# ---------------------------------------------------------------------------------------------------------------------
+def adapt_array(arr):
+    """A numpy array as the blob the reference stores: the bytes of ``np.save``."""
+    buf = io.BytesIO()
+    np.save(buf, arr)
+    return sqlite3.Binary(buf.getvalue())
+
+
+def convert_array(blob):
+    return np.load(io.BytesIO(blob)).copy()
+
+
+def open_local(db_f):
+    """``(cursor, connection)`` of a database whose ``array`` columns travel as numpy arrays both ways."""
+    conn = sqlite3.connect(db_f, detect_types=sqlite3.PARSE_DECLTYPES)
+    sqlite3.register_adapter(np.ndarray, adapt_array)
+    sqlite3.register_converter("array", convert_array)
+    return conn.cursor(), conn
+
+
+_SCHEMA = (("header", "id INTEGER PRIMARY KEY, pressure_unit VARCHAR, temperature_unit VARCHAR, wavenumber_grid array, "
+                      "continuum_unit VARCHAR, molecular_unit VARCHAR"),
+           ("molecular", "id INTEGER PRIMARY KEY, ptid INTEGER, molecule VARCHAR, pressure FLOAT, temperature FLOAT, "
+                         "opacity array"),
+           ("continuum", "id INTEGER PRIMARY KEY, molecule VARCHAR, temperature FLOAT, opacity array"))
+_HEADER_INSERT = ("INSERT INTO header (pressure_unit, temperature_unit, wavenumber_grid, continuum_unit, molecular_unit) "
+                  "values (?,?,?,?,?)")
+_HEADER_UNITS = ("bar", "kelvin", "cm-1 amagat-2", "cm2/molecule")
+
+
+def build_skeleton(db_f):
+    """An empty database with the reference's three tables ``header``, ``molecular`` and ``continuum`` (:622-669); tables
+    of these names that the file already holds are dropped."""
+    cur, conn = open_local(db_f)
+    for name, columns in _SCHEMA:
+        cur.execute("DROP TABLE IF EXISTS %s" % name)
+        cur.execute("CREATE TABLE %s (%s)" % (name, columns))
+    conn.commit()
+    conn.close()
+
+
+def _insert_header(cur, wno_grid):
+    cur.execute(_HEADER_INSERT, _HEADER_UNITS[:2] + (np.array(wno_grid),) + _HEADER_UNITS[2:])
+
+
+def insert_wno_grid(wno_grid, cur, con):
+    """Write the header row (the units and ``wno_grid``, cm-1), commit and close the connection, as the reference does."""
+    _insert_header(cur, wno_grid)
+    con.commit()
+    con.close()
+
+
+def create_grid_minR(min_wavelength, max_wavelength, minimum_R):
+    """``(grid, step)``: wavenumbers in constant steps between the two wavelengths (micron); the step gives the resolution
+    ``minimum_R`` at ``min_wavelength``, so every other point is resolved better (:692-710)."""
+    dwvno = 1e4 / (min_wavelength ** 2) * (min_wavelength / minimum_R)
+    return np.arange(1e4 / max_wavelength, 1e4 / min_wavelength, dwvno), dwvno
+
+
+def continuum_avail(db_file):
+    """``(molecules, temperatures)`` of the continuum table, each unique and sorted."""
+    cur, conn = open_local(db_file)
+    cur.execute("SELECT molecule FROM continuum")
+    molecules = [str(m) for m in np.unique(cur.fetchall())]
+    cur.execute("SELECT temperature FROM continuum")
+    temperatures = list(np.unique(cur.fetchall()))
+    conn.close()
+    return molecules, temperatures
+
+
+def molecular_avail(db_file):
+    """``(molecules, pt_pairs)``: the gases of the molecular table and its ``(ptid, pressure, temperature)`` by ptid."""
+    cur, conn = open_local(db_file)
+    cur.execute("SELECT ptid, pressure, temperature FROM molecular")
+    pt_pairs = sorted(set(cur.fetchall()), key=lambda x: x[0])
+    cur.execute("SELECT molecule FROM molecular")
+    molecules = [str(m) for m in np.unique(cur.fetchall())]
+    conn.close()
+    return molecules, pt_pairs
+
+
+def find_nearest_1d(array, value):
+    """Index of the entry of ``array`` nearest ``value``; among equal entries the last (:1281-1289)."""
+    u, first, count = np.unique(array, return_index=True, return_counts=True)
+    i = np.abs(u - value).argmin(axis=0)
+    return first[i] + (count[i] - 1)
+
+
+def _select_in(cur, table, columns, molecules, key, values):
+    cur.execute("SELECT %s FROM %s WHERE molecule in (%s) AND %s in (%s)"
+                % (columns, table, ", ".join("?" * len(molecules)), key, ", ".join("?" * len(values))),
+                list(molecules) + list(values))
+    return cur.fetchall()
+
+
+def get_continuum(db_file, species, temperature):
+    """``{species: {T: opacity}, 'wavenumber': grid}`` for the lists ``species`` and ``temperature``; every temperature
+    is replaced by the nearest one of the table (:1290-1356)."""
+    if not isinstance(temperature, list):
+        raise Exception("Make Temperature a list, even if it is single valued")
+    if not isinstance(species, list):
+        raise Exception("Make Species Input a list, even if it is single valued")
+    cur, conn = open_local(db_file)
+    cur.execute("SELECT temperature FROM continuum")
+    have = np.unique(cur.fetchall())
+    nearest = [float(have[find_nearest_1d(have, t)]) for t in temperature]
+    out = {s: {} for s in species}
+    for mol, t, opacity in _select_in(cur, "continuum", "molecule,temperature,opacity", species, "temperature", nearest):
+        out[mol][t] = opacity
+    cur.execute("SELECT wavenumber_grid FROM header")
+    out["wavenumber"] = cur.fetchone()[0]
+    conn.close()
+    return out
+
+
+def get_molecular(db_file, species, temperature, pressure):
+    """``{species: {T: {P: opacity}}, 'wavenumber': grid}``: ``temperature[i]`` and ``pressure[i]`` are a pair, replaced
+    by the nearest pair of the table (plain distance in (P, T), :1358-1440)."""
+    for name, v in (("temperature", temperature), ("pressure", pressure), ("Species", species)):
+        if not isinstance(v, list):
+            raise Exception("Make %s a list, even if it is single valued" % name)
+    if len(temperature) != len(pressure):
+        raise Exception("Temperature and Pressure must be the same size because these are treated as pairs. "
+                        "t=[500,600], p=[1.0, 0.01] will grab [500,1.0 ] and [600,0.01]")
+    cur, conn = open_local(db_file)
+    cur.execute("SELECT ptid, pressure, temperature FROM molecular")
+    pt_pairs = sorted(set(cur.fetchall()), key=lambda x: x[0])
+    ids = [min(pt_pairs, key=lambda c: math.hypot(c[1] - p, c[2] - t))[0] for p, t in zip(pressure, temperature)]
+    out = {s: {pt_pairs[i - 1][2]: {} for i in ids} for s in species}
+    for mol, _, p, t, opacity in _select_in(cur, "molecular", "molecule,ptid,pressure,temperature,opacity", species,
+                                            "ptid", ids):
+        out[mol][t][p] = opacity
+    cur.execute("SELECT wavenumber_grid FROM header")
+    out["wavenumber"] = cur.fetchone()[0]
+    conn.close()
+    return out
+
+
+def delete_molecule(mol, db_filename):
+    """Delete every row of gas ``mol`` from the molecular table."""
+    conn = sqlite3.connect(db_filename)
+    try:
+        conn.execute("DELETE from molecular where molecule = ?", (mol,))
+        conn.commit()
+    finally:
+        conn.close()
+
+
+def insert_hitran_cia(original_file, molname, new_db, new_wno):
+    raise NotImplementedError("insert_hitran_cia: HITRAN's .cia reader is not supported: there is no sample of these "
+                              "files to pin the reading against")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# continuum rows: the host functions in the reference's operation order, and the device route
+# ---------------------------------------------------------------------------------------------------------------------
+def _refdata_file(name):
+    ref = os.environ.get("picaso_refdata")
+    if ref is None:
+        raise Exception("%s is looked up under $picaso_refdata/opacities, which is not set; or pass the table as arrays"
+                        % name)
+    return os.path.join(ref, "opacities", name)
+
+
+def read_overtone_table(fname=None):
+    """``(wavenumber (n), temperatures (ncol), values (n, ncol))`` of ``H2H2_ov2_eq.tbl``: a header line ``wavenumber T1
+    T2 ...``, then one line per wavenumber."""
+    fname = fname if fname is not None else _refdata_file("H2H2_ov2_eq.tbl")
+    with open(fname) as fh:
+        temps = np.array([float(x) for x in fh.readline().split()[1:]])
+        body = np.array([[float(x) for x in line.split()] for line in fh if line.strip()])
+    return body[:, 0].copy(), temps, body[:, 1:].copy()
+
+
+def read_h2minus_table(fname=None):
+    """``(theta (n), wavelength in angstrom (ncol), values (n, ncol))`` of ``h2minus.csv`` (Bell 1980, table 1): five
+    comment lines, a header ``theta,lambda1,...``, one line per theta."""
+    fname = fname if fname is not None else _refdata_file("h2minus.csv")
+    with open(fname) as fh:
+        lines = [line.strip() for line in fh.readlines()[5:] if line.strip()]
+    lam = np.array([float(x) for x in lines[0].split(",")[1:]])
+    body = np.array([[float(x) for x in line.split(",")] for line in lines[1:]])
+    return body[:, 0].copy(), lam, body[:, 1:].copy()
+
+
+def _tables(overtone_table, h2minus_table):
+    ov = tuple(np.asarray(x, dtype=float) for x in (overtone_table if overtone_table is not None else read_overtone_table()))
+    bell = tuple(np.asarray(x, dtype=float) for x in (h2minus_table if h2minus_table is not None else read_h2minus_table()))
+    return ov, bell
+
+
+def _has_continuum_rows(db_f):
+    conn = sqlite3.connect(db_f)
+    try:
+        return conn.execute("SELECT COUNT(*) FROM continuum").fetchone()[0] > 0
+    except sqlite3.OperationalError:            # no such table
+        return False
+    finally:
+        conn.close()
+
+
+def get_original_data(original_file, colnames, new_db, overwrite=False):
+    """``(og_opacity, temperatures, old_wno, molecules)`` of a CIA file (:228-274): a line ``nwno ntemp``, then per
+    temperature a line with the temperature alone and ``nwno`` lines ``wavenumber log10(opacity) ...``, one column per name
+    of ``colnames`` (``['wno', 'H2H2', ...]``).  As in the reference a line is a temperature when its second column is
+    missing, and lines with any missing column are dropped from the data.  ``og_opacity``: ``{column: array}`` over the
+    data lines.  Numbers are read with ``float``; the reference reads them with pandas, which gives the same bits for the
+    decimal forms of these files.
+
+    ``overwrite``: the reference's test is inverted (it raises when ``overwrite`` is True).  Here a ``new_db`` that already
+    holds continuum rows raises unless ``overwrite=True``, which deletes them."""
+    ncol = len(colnames)
+    table = []
+    with open(original_file) as fh:
+        for line in fh:
+            tok = line.split()
+            if tok:
+                table.append([float(x) for x in tok[:ncol]] + [np.nan] * (ncol - len(tok)))
+    table = np.array(table, dtype=float).reshape(-1, ncol)
+    temperatures = table[np.isnan(table[:, 1]), 0]
+    data = table[~np.isnan(table).any(axis=1)]
+    og_opacity = {c: data[:, k].copy() for k, c in enumerate(colnames)}
+    _, first = np.unique(data[:, 0], return_index=True)
+    old_wno = data[np.sort(first), 0]           # in order of appearance, as pandas' unique
+    if os.path.exists(new_db) and _has_continuum_rows(new_db):
+        if not overwrite:
+            raise Exception("%s already holds continuum rows; overwrite=True deletes them first" % new_db)
+        conn = sqlite3.connect(new_db)
+        conn.execute("DELETE FROM continuum")
+        conn.commit()
+        conn.close()
+    return og_opacity, temperatures, old_wno, list(colnames[1:])
+
+
+def h2h2_overtone(t, wno, overtone_table=None):
+    """``(opacity, loc, add)``: the H2-H2 band at 0.8 micron on the points ``wno[loc]`` inside the table, from the column
+    nearest ``t``; ``add`` is False above the table's last temperature (:365-391).  cm-1 amagat-2."""
+    wn, temps, values = overtone_table if overtone_table is not None else read_overtone_table()
+    if t > max(temps):
+        return np.nan, np.nan, False
+    it = (np.abs(temps - t)).argmin()
+    loc = np.where((wno >= wn.min()) & (wno <= wn.max()))
+    return 10 ** (np.interp(wno[loc], wn, np.log10(values[:, it]), right=-33, left=-33)), loc, True
+
+
+_LINSKY = dict(sig0=np.array([4162.043, 8274.650, 12017.753]), d1=np.array([1.2750e5, 1.32e6, 1.32e6]),
+               d2=np.array([2760., 2760., 2760.]), d3=np.array([0.40, 0.40, 0.40]), a1=np.array([-7.661, -9.70, -11.32]),
+               a2=np.array([0.5725, 0.5725, 0.5725]), b1=np.array([0.9376, 0.9376, 0.9376]),
+               b2=np.array([0.5616, 0.5616, 0.5616]))       # Lenzuni et al. (1991), table 8
+
+
+def _linsky_params(t, va=3):
+    """``(w, d, a, b, aa)`` of fit_linsky at temperature ``t`` (:413-430)."""
+    L, k = _LINSKY, va - 1
+    w = L["sig0"][k]
+    d = L["d3"][k] * np.sqrt(L["d1"][k] + L["d2"][k] * t)
+    a = 10 ** (L["a1"][k] + L["a2"][k] * np.log10(t))
+    b = 10 ** (L["b1"][k] + L["b2"][k] * np.log10(t))
+    aa = 4.0 / 13.0 * a / d * np.exp(1.5 * d / b)
+    return w, d, a, b, aa
+
+
+def fit_linsky(t, wno, va=3):
+    """H2-H2 opacity of Linsky (1969) and Lenzuni et al. (1991) for the points that hold the -33 placeholder (:393-440).
+    The reference's branch for ``wno < w`` is always overwritten by its branch for ``wno < w + 1.5 d``; two are left."""
+    w, d, a, b, aa = _linsky_params(t, va)
+    kappa = aa * wno * np.exp(-(wno - w) / b)
+    near = np.where(wno < w + 1.5 * d)
+    kappa[near] = a * d * wno[near] / ((wno[near] - w) ** 2 + d * d)
+    return kappa
+
+
+def _bell_row(t, h2minus_table):
+    """``(wno_bell, kappa_bell)``: Bell's wavenumbers and the row of the theta nearest ``5040 / t`` in cm4/dyn."""
+    theta, lam, values = h2minus_table
+    itheta = find_nearest_1d(theta, 5040.0 / t)
+    return 1e8 / lam, (10 ** np.log10(values)[itheta, :]) * 1e-26
+
+
+def get_h2minus(t, new_wno, h2minus_table=None):
+    """H2- free-free opacity (Bell 1980, table 1) in cm4/dyn on ``new_wno``, 1e-33 outside the table (:442-479)."""
+    wno_bell, kappa_bell = _bell_row(t, h2minus_table if h2minus_table is not None else read_h2minus_table())
+    return np.interp(new_wno, wno_bell, kappa_bell, left=1e-33, right=1e-33)
+
+
+_HBF_COEFF = np.array([152.519, 49.534, -118.858, 92.536, -34.194, 4.982])[::-1]       # John (1988)
+_HBF_LAMBDA_0 = 1.6419
+
+
+def get_hminusbf(wno):
+    """H- bound-free cross section (John 1988) in cm2: 1e-33 at and beyond the edge at 1.6419 micron (:481-508)."""
+    wave = 1e4 / wno
+    on = np.where(wno > 1e4 / _HBF_LAMBDA_0)
+    f, x = np.zeros(np.size(wave)), np.zeros(np.size(wave))
+    result = np.zeros(np.size(wave)) + 1e-33
+    x[on] = np.sqrt(1.0 / wave[on] - 1.0 / _HBF_LAMBDA_0)
+    for c in _HBF_COEFF:
+        f[on] = f[on] * x[on] + c
+    result[on] = (wave[on] * x[on]) ** 3 * f[on] * 1e-18
+    return result
+
+
+_HFF = (   # Bell & Berrington (1987): A..F for wavelengths above 0.3645 micron, then for the rest
+    ([0.e0, 2483.346, -3449.889, 2200.040, -696.271, 88.283], [0.e0, 285.827, -1158.382, 2427.719, -1841.400, 444.517],
+     [0.e0, -2054.291, 8746.523, -13651.105, 8624.970, -1863.864], [0.e0, 2827.776, -11485.632, 16755.524, -10051.530, 2095.288],
+     [0.e0, -1341.537, 5303.609, -7510.494, 4400.067, -901.788], [0.e0, 208.952, -812.939, 1132.738, -655.020, 132.985]),
+    ([518.1021, 473.2636, -482.2089, 115.5291, 0.0, 0.0], [-734.8666, 1443.4137, -737.1616, 169.6374, 0.0, 0.0],
+     [1021.1775, -1977.3395, 1096.8827, -245.649, 0.0, 0.0], [-479.0721, 922.3575, -521.1341, 114.243, 0.0, 0.0],
+     [93.1373, -178.9275, 101.7963, -21.9972, 0.0, 0.0], [-6.4285, 12.3600, -7.0571, 1.5097, 0.0, 0.0]))
+
+
+def _hff_powers(t):
+    """``t_coeff**((i + 1) / 2)`` for i in 0..5, ``t_coeff = 5040 / t``: the weights of get_hminusff's six sums."""
+    t_coeff = 5040.0 / t
+    return [t_coeff ** ((i + 1) / 2.0) for i in range(6)]
+
+
+def get_hminusff(t, wno):
+    """H- free-free cross section (Bell & Berrington 1987) in cm5, with stimulated emission; 1e-60 below 800 K, wavelengths
+    below 0.1823 micron taken there, zero past 20 micron (:510-573)."""
+    wave = 1e4 / wno
+    nwave = np.size(wave)
+    if t < 800:
+        return np.zeros(nwave) + 1e-60
+    powers = _hff_powers(t)
+    hj = np.zeros((6, nwave))
+    longw, midw = np.where(wave > 0.3645), np.where(wave <= 0.3645)
+    wave[np.where(wave < 0.1823)] = 0.1823
+    for i in range(6):
+        for sel, (A, B, C, D, E, F) in ((longw, _HFF[0]), (midw, _HFF[1])):
+            v = wave[sel]
+            hj[i, sel] = 1e-29 * (v * v * A[i] + B[i] + (C[i] + (D[i] + (E[i] + F[i] / v) / v) / v) / v)
+    hm_cx = np.zeros(nwave)
+    for i in range(6):
+        hm_cx += powers[i] * hj[i, :]
+    past20 = np.where(wave > 20.0)
+    if np.size(past20) > 0:
+        hm_cx[past20] = np.zeros(np.size(past20))
+    return hm_cx * 1.380658e-16 * t
+
+
+def medfilt(x, kernel_size):
+    """``scipy.signal.medfilt`` of a 1-D array in numpy: the median of ``kernel_size`` (odd) neighbours, zeros beyond the
+    ends."""
+    x = np.asarray(x, dtype=float)
+    h = int(kernel_size) // 2
+    padded = np.concatenate((np.zeros(h), x, np.zeros(h)))
+    out = np.empty(x.size)
+    step = max(1, (1 << 24) // int(kernel_size))            # about 128 MB of windows at a time
+    for lo in range(0, x.size, step):
+        hi = min(x.size, lo + step)
+        win = np.lib.stride_tricks.sliding_window_view(padded[lo:hi + 2 * h], 2 * h + 1)
+        out[lo:hi] = np.partition(win, h, axis=1)[:, h]
+    return out
+
+
+def smoothing_window(new_wno):
+    """The median filter's window: the odd number of points that spans 90 cm-1 at the grid's first step (:300-302)."""
+    new_wno = np.asarray(new_wno)
+    if new_wno.size < 2:
+        raise Exception("the new wavenumber grid needs at least 2 points (the first step sets the smoothing window)")
+    return int(np.ceil(90 / (new_wno[1] - new_wno[0])) // 2 * 2 + 1)
+
+
+def _h2h2_row(t, bundle, new_wno, kernel_size, overtone_table, smooth=True):
+    """The reference's patches of one interpolated H2H2 row (:313-331), in place."""
+    h2h2, loc, add = h2h2_overtone(t, new_wno, overtone_table)
+    if add:
+        bundle[loc] = h2h2
+    loc_33 = np.where((bundle == 1e-33) & (new_wno >= 1000))
+    bundle[loc_33] = fit_linsky(t, new_wno[loc_33])
+    if len(loc_33[0]) != 0 and max(new_wno[loc_33] < 12000) and smooth:
+        loc_smooth = np.where((new_wno > 9950) & (new_wno < 11200))
+        if len(loc_smooth[0]) != 0:
+            bundle[loc_smooth] = medfilt(np.array(bundle[loc_smooth]), kernel_size)
+    return bundle
+
+
+def continuum_rows_numpy(og_log_opacity, temperatures, old_wno, molecules, new_wno, overtone_table=None, h2minus_table=None,
+                         smooth=True):
+    """The rows ``restructure_opacity`` writes, as one block ``(ntemp, nspecies, nwno)`` in the species order ``molecules
+    + ['H2-', 'H-bf', 'H-ff']``, on the host in the reference's operation order (:300-359): bit for bit what the reference
+    inserts.  ``og_log_opacity``: ``(ntemp, nmolecules, nold)`` log10 opacities on ``old_wno``, -33 where there is none.
+    ``overtone_table``, ``h2minus_table``: the two data tables as ``read_overtone_table`` / ``read_h2minus_table`` return
+    them; default: read from ``$picaso_refdata/opacities``.  ``smooth=False`` (tests): no median filter."""
+    ov, bell = _tables(overtone_table, h2minus_table)
+    og = np.asarray(og_log_opacity, dtype=float)
+    temperatures, new_wno = np.asarray(temperatures, dtype=float), np.asarray(new_wno, dtype=float)
+    old_wno, molecules = np.asarray(old_wno, dtype=float), list(molecules)
+    if og.shape != (temperatures.size, len(molecules), old_wno.size):
+        raise Exception("continuum_rows: og_log_opacity must be (ntemp, nmolecules, nold) = (%d, %d, %d), got %s"
+                        % (temperatures.size, len(molecules), old_wno.size, og.shape))
+    kernel_size = smoothing_window(new_wno)
+    zero_bundle = np.zeros(len(new_wno)) + 1e-33
+    out = np.empty((temperatures.size, len(molecules) + 3, new_wno.size))
+    hminusbf = None
+    for i, t in enumerate(temperatures):
+        for k, m in enumerate(molecules):
+            bundle = 10 ** (np.interp(new_wno, old_wno, og[i, k], right=-33, left=-33))
+            if m == "H2H2":
+                _h2h2_row(t, bundle, new_wno, kernel_size, ov, smooth)
+            out[i, k] = bundle
+        n = len(molecules)
+        out[i, n] = zero_bundle if t < 600.0 else get_h2minus(t, new_wno, bell)
+        if t < 800.0:
+            out[i, n + 1], out[i, n + 2] = zero_bundle, zero_bundle * 1e-30
+        else:
+            if hminusbf is None:
+                hminusbf = get_hminusbf(new_wno)
+            out[i, n + 1], out[i, n + 2] = hminusbf, get_hminusff(t, new_wno)
+    return out
+
+
+def _continuum_params(temperatures, npar, ov, bell):
+    """What the device reads per temperature: ``par (ntemp, npar)`` in the order of csrc/contfactory.hip's ContPar,
+    ``ov_log (ntemp, nov)`` the log10 of the nearest overtone column, ``bell_kappa (ntemp, nbell)`` the nearest Bell row."""
+    wn, ov_temps, ov_values = ov
+    p33 = np.power(10.0, np.array([-33.0]))[0]
+    zero = (np.zeros(1) + 1e-33)[0]
+    par = np.zeros((len(temperatures), npar))
+    ov_log = np.zeros((len(temperatures), wn.size))
+    bell_kappa = np.zeros((len(temperatures), bell[1].size))
+    ov_all = np.log10(ov_values)
+    for i, t in enumerate(temperatures):
+        add = not (t > max(ov_temps))
+        if add:
+            ov_log[i] = ov_all[:, (np.abs(ov_temps - t)).argmin()]
+        w, d, a, b, aa = _linsky_params(t)
+        hot = not (t < 800.0)
+        if not (t < 600.0):
+            bell_kappa[i] = _bell_row(t, bell)[1]
+        par[i, :14] = (add, d, a, b, aa, w, w + 1.5 * d, t, not (t < 600.0), zero, hot, zero, hot,
+                       zero * 1e-30 if t < 800.0 else 1e-60)
+        if hot:
+            par[i, 14:20] = _hff_powers(t)
+        par[i, 20:24] = (p33, 1e4 / _HBF_LAMBDA_0, 1.0 / _HBF_LAMBDA_0, p33 == 1e-33)
+    return par, ov_log, bell_kappa
+
+
+def _ascending(a):
+    return a.size < 2 or bool(np.all(a[1:] >= a[:-1]))
+
+
+class _ContinuumDevice:
+    """The inputs of ``picaso_continuum_rows_dev`` resident on the device; ``rows(t0, t1, d_out, d_work)`` enqueues the
+    kernels of the temperatures ``[t0, t1)`` and returns at once."""
+
+    def __init__(self, og_log_opacity, temperatures, old_wno, molecules, new_wno, overtone_table, h2minus_table, smooth,
+                 lds_cap):
+        who = "continuum_rows"
+        ov, bell = _tables(overtone_table, h2minus_table)
+        og = _lib.f64(og_log_opacity)
+        self.temperatures = temperatures = _lib.f64(temperatures)
+        old_wno, new_wno, self.molecules = _lib.f64(old_wno), _lib.f64(new_wno), list(molecules)
+        if og.shape != (temperatures.size, len(self.molecules), old_wno.size) or og.size == 0:
+            raise Exception("%s: og_log_opacity must be (ntemp, nmolecules, nold) = (%d, %d, %d), got %s"
+                            % (who, temperatures.size, len(self.molecules), old_wno.size, og.shape))
+        if new_wno.ndim != 1:
+            raise Exception("%s: new_wno must be a 1-D array" % who)
+        wno_bell = 1e8 / bell[1]
+        for name, g in (("old_wno", old_wno), ("the overtone table's wavenumbers", ov[0]), ("Bell's wavenumbers", wno_bell)):
+            if not _ascending(g):
+                raise Exception("%s: %s must ascend on the device route; continuum_rows_numpy takes any order" % (who, name))
+        self.window = smoothing_window(new_wno)
+        region = np.where((new_wno > 9950) & (new_wno < 11200))[0]
+        if region.size and region[-1] - region[0] + 1 != region.size:
+            raise Exception("%s: the points of new_wno inside (9950, 11200) cm-1 must be neighbours on the device route; "
+                            "continuum_rows_numpy takes any order" % who)
+        if region.size and self.window < 1:
+            raise Exception("%s: new_wno must ascend at its first step (the smoothing window is %d)" % (who, self.window))
+        self.lo, self.n = (int(region[0]), int(region.size)) if region.size else (0, 0)
+        self.window = max(self.window, 1)
+        self.smooth, self.lds_cap = int(bool(smooth)), int(lds_cap)
+        self.ntemp, self.nmol, self.nold, self.nwno = temperatures.size, len(self.molecules), old_wno.size, new_wno.size
+        self.nsp = self.nmol + 3
+        self.h2h2 = self.molecules.index("H2H2") if "H2H2" in self.molecules else -1
+        self.ctx, self.lib = _lib.context(), _lib.load()
+        self.npar = int(self.lib.picaso_continuum_npar())
+        if self.npar != 24:
+            raise Exception("%s: the library reads %d values per temperature, this module writes 24: rebuild it" % (who, self.npar))
+        par, ov_log, bell_kappa = _continuum_params(temperatures, self.npar, ov, bell)
+        self.nov, self.nbell = ov[0].size, wno_bell.size
+        self.held = [DeviceArray.from_host(a, self.ctx) for a in (old_wno, og, new_wno, ov[0], ov_log, wno_bell, bell_kappa, par)]
+        self.d_old, self.d_og, self.d_new, self.d_ovw, self.d_ovl, self.d_bw, self.d_bk, self.d_par = self.held
+
+    def work(self, ntemp):
+        return DeviceArray((ntemp * (self.n + 1),), self.ctx)
+
+    def rows(self, t0, t1, d_out, d_work):
+        _lib.check(self.lib.picaso_continuum_rows_dev(
+            self.ctx, t1 - t0, self.nmol, self.h2h2, self.nold, self.d_old.addr, self.d_og.addr + 8 * t0 * self.nmol * self.nold,
+            self.nwno, self.d_new.addr, self.nov, self.d_ovw.addr, self.d_ovl.addr + 8 * t0 * self.nov, self.nbell,
+            self.d_bw.addr, self.d_bk.addr + 8 * t0 * self.nbell, self.d_par.addr + 8 * t0 * self.npar, self.lo, self.n,
+            self.window, self.lds_cap, self.smooth, d_work.addr, d_out.addr), self.ctx)
+
+    def free(self):
+        try:
+            _sync(self.ctx)
+        finally:
+            for blk in self.held:
+                blk.free()
+            self.held = []
+
+
+_MAX_TEMPS_PER_CALL = 65535
+
+
+@_lib.serialized
+def continuum_rows(og_log_opacity, temperatures, old_wno, molecules, new_wno, overtone_table=None, h2minus_table=None,
+                   out="host", smooth=True, _lds_cap=0):
+    """``continuum_rows_numpy`` on the device (``picaso_continuum_rows_dev``, csrc/contfactory.hip): the same block
+    ``(ntemp, nspecies, nwno)``, species ``molecules + ['H2-', 'H-bf', 'H-ff']``.  What depends on the temperature alone is
+    formed here in numpy and uploaded; the per-point arithmetic runs in numpy's operation order without contraction.
+    Against the host rows: H2-, H-ff, the constant rows and the Linsky points below ``w + 1.5 d`` are equal bit for bit;
+    ``10**x`` is within 4 ulp; the Linsky points above and H-bf within 8 ulp; the smoothed region is
+    the exact median of the device's own unsmoothed values.
+
+    ``old_wno`` and the tables' wavenumbers must ascend, and the points of ``new_wno`` inside (9950, 11200) cm-1 must be
+    neighbours.  ``out="device"``: a ``DeviceArray`` the caller frees.  ``smooth=False`` (tests): no median filter.
+    ``_lds_cap`` (tests): windows longer than this take the radix-select path (0: the default, 8 192)."""
+    if out not in ("host", "device"):
+        raise Exception("continuum_rows: out must be 'host' or 'device', got %r" % (out,))
+    dev = _ContinuumDevice(og_log_opacity, temperatures, old_wno, molecules, new_wno, overtone_table, h2minus_table, smooth,
+                           _lds_cap)
+    d_out = d_work = None
+    try:
+        d_out = DeviceArray((dev.ntemp, dev.nsp, dev.nwno), dev.ctx)
+        d_work = dev.work(min(dev.ntemp, _MAX_TEMPS_PER_CALL))
+        for t0 in range(0, dev.ntemp, _MAX_TEMPS_PER_CALL):
+            t1 = min(dev.ntemp, t0 + _MAX_TEMPS_PER_CALL)
+            dev.rows(t0, t1, d_out.row_range(t0, t1), d_work)
+        if out == "device":
+            _sync(dev.ctx)
+            kept, d_out = d_out, None
+            return kept
+        return d_out.to_host()
+    finally:
+        dev.free()
+        for blk in (d_out, d_work):
+            if blk is not None:
+                blk.free()
+
+
+def _log_opacity_block(og_opacity, ntemp, molecules, nold):
+    """``(ntemp, nmolecules, nold)`` from the columns of ``get_original_data``: temperature ``i`` owns the data lines
+    ``[i nold, (i + 1) nold)`` (:310)."""
+    block = np.empty((ntemp, len(molecules), nold))
+    for k, m in enumerate(molecules):
+        col = np.asarray(og_opacity[m], dtype=float)
+        if col.size < ntemp * nold:
+            raise Exception("restructure_opacity: column %s holds %d values, fewer than %d temperatures x %d wavenumbers"
+                            % (m, col.size, ntemp, nold))
+        block[:, k, :] = col[:ntemp * nold].reshape(ntemp, nold)
+    return block
+
+
+CONTINUUM_BUDGET_BYTES = 1 << 30
+
+
+@_lib.serialized
+def restructure_opacity(new_db, ntemp, temperatures, molecules, og_opacity, old_wno, new_wno, rows="device",
+                        budget_bytes=None, overtone_table=None, h2minus_table=None):
+    """Interpolate the CIA file's opacities onto ``new_wno``, add the other continuum sources and insert every row into
+    the ``continuum`` table of ``new_db`` (the reference's function and arguments, :280-362; ``og_opacity``: the columns
+    ``get_original_data`` returns).  Per temperature the rows go in as the reference inserts them: the molecules, then
+    ``H2-``, ``H-bf``, ``H-ff``.
+
+    ``rows="device"``: the rows are made by ``continuum_rows`` in chunks of temperatures of at most ``budget_bytes``
+    (default 1 GiB; at least one temperature) each; two chunks are resident, and the copy back and the inserts of one
+    overlap the kernels of the next.  ``rows="numpy"``: ``continuum_rows_numpy``, chunked the same way."""
+    if rows not in ("device", "numpy"):
+        raise Exception("restructure_opacity: rows must be 'device' or 'numpy', got %r" % (rows,))
+    temperatures, new_wno = np.asarray(temperatures, dtype=float)[:ntemp], np.asarray(new_wno, dtype=float)
+    molecules = list(molecules)
+    block = _log_opacity_block(og_opacity, ntemp, molecules, len(old_wno))
+    names = molecules + ["H2-", "H-bf", "H-ff"]
+    budget = CONTINUUM_BUDGET_BYTES if budget_bytes is None else int(budget_bytes)
+    per = max(1, min(budget // (8 * len(names) * max(1, new_wno.size)), _MAX_TEMPS_PER_CALL, max(1, ntemp)))
+    chunks = [(t0, min(ntemp, t0 + per)) for t0 in range(0, ntemp, per)]
+    cur, conn = open_local(new_db)
+
+    def insert(t0, t1, host):
+        for i in range(t0, t1):
+            for k, name in enumerate(names):
+                cur.execute("INSERT INTO continuum (molecule, temperature, opacity) values (?,?,?)",
+                            (name, float(temperatures[i]), host[i - t0, k]))
+
+    try:
+        try:
+            cur.execute("SELECT COUNT(*) FROM continuum")
+        except sqlite3.OperationalError:
+            raise Exception("restructure_opacity: %s has no continuum table; run build_skeleton first" % new_db) from None
+        if rows == "numpy":
+            for t0, t1 in chunks:
+                insert(t0, t1, continuum_rows_numpy(block[t0:t1], temperatures[t0:t1], old_wno, molecules, new_wno,
+                                                    overtone_table, h2minus_table))
+        else:
+            dev = _ContinuumDevice(block, temperatures, old_wno, molecules, new_wno, overtone_table, h2minus_table, True, 0)
+            held = []
+            try:
+                shape = (per, len(names), new_wno.size)
+                slots = []
+                for _ in range(min(2, len(chunks))):
+                    slots.append((DeviceArray(shape, dev.ctx), dev.work(per), PinnedArray(shape, dev.ctx)))
+                    held.extend(slots[-1])
+                waiting = None
+                for c, (t0, t1) in enumerate(chunks):
+                    d_out, d_work, pinned = slots[c & 1]
+                    dev.rows(t0, t1, d_out, d_work)
+                    mark = ctypes.c_void_p()
+                    _lib.check(dev.lib.picaso_memcpy_d2h_async(dev.ctx, pinned.addr, d_out.addr,
+                                                               8 * (t1 - t0) * len(names) * new_wno.size,
+                                                               ctypes.byref(mark)), dev.ctx)
+                    pinned._mark, pinned._mark_ctx = mark, dev.ctx
+                    if waiting is not None:             # the rows of the chunk before, while this one's kernels run
+                        insert(waiting[0], waiting[1], waiting[2].wait())
+                    waiting = (t0, t1, pinned)
+                if waiting is not None:
+                    insert(waiting[0], waiting[1], waiting[2].wait())
+            finally:
+                dev.free()
+                for blk in held:
+                    blk.free()
+        conn.commit()
+    finally:
+        conn.close()
+
+
+def restruct_continuum(original_file, colnames, new_wno, new_db, overwrite=False, **kwargs):
+    """The continuum part of an opacity database from a CIA file (the reference's function and arguments, :22-59):
+    ``get_original_data`` then ``restructure_opacity`` (``kwargs`` go to it).  ``new_db`` must have the tables of
+    ``build_skeleton``.
+
+    ``overwrite``: the reference's test is inverted (it raises when ``overwrite`` is True and never deletes).  Here a
+    ``new_db`` that already holds continuum rows raises unless ``overwrite=True``, which deletes them first."""
+    og_opacity, temperatures, old_wno, molecules = get_original_data(original_file, colnames, new_db, overwrite=overwrite)
+    restructure_opacity(new_db, len(temperatures), temperatures, molecules, og_opacity, old_wno, new_wno, **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# resampled molecular rows
+# ---------------------------------------------------------------------------------------------------------------------
+def resample_numpy(row, og_wvno_grid, points, insert_direct=False, min_wavelength=None, max_wavelength=None):
+    """One molecular row as the reference forms it (:1023-1035), in numpy.  Resampled: ``np.interp`` onto ``points`` --
+    every ``BINS``-th point of the hi-res grid, which is what the reference keeps of its interpolation onto the whole grid
+    -- with fills and floor of 1e-100.  ``insert_direct``: the floor, then the points of the row whose wavelength lies
+    strictly inside ``(min_wavelength, max_wavelength)``."""
+    row = np.array(row, dtype=float)
+    if insert_direct:
+        keep = np.where((1e4 / og_wvno_grid > min_wavelength) & (1e4 / og_wvno_grid < max_wavelength))
+        row[row < 1e-100] = 1e-100
+        return row[keep]
+    y = np.interp(points, og_wvno_grid, row, right=1e-100, left=1e-100)
+    y[y < 1e-100] = 1e-100
+    return y
+
+
+@_lib.serialized
+def insert_molecular_1460(molecule, min_wavelength, max_wavelength, og_directory, new_db, new_R=None, new_dwno=None,
+                          old_R=1e6, old_dwno=0.0035, alkali_dir="alkalis", dir_kark_ch4=None, dir_optical_o3=None,
+                          insert_direct=False):
+    """Resample the cross sections of one gas onto a lower-resolution grid and insert them into the ``molecular`` table of
+    ``new_db`` (the reference's function and arguments, :850-1055); returns the new wavenumber grid.  ``og_directory``
+    holds ``grid1460.csv`` and the directory ``molecule`` with ``<file_number>.npy`` or ``p_<file_number>`` rows on
+    uniform grids, as ``compute_ck_molecular`` reads them.
+
+    ``new_R``: the hi-res grid is ``create_grid(min_wavelength, max_wavelength, old_R)`` and every ``int(old_R / new_R)``-th
+    point of it is kept; ``new_dwno``: ``np.arange(1e4 / max_wavelength, 1e4 / min_wavelength, old_dwno)`` and every
+    ``int(new_dwno / old_dwno)``-th point; both grids are built on the host as the reference builds them.  The reference
+    interpolates every row onto the whole hi-res grid and then keeps the points; here only the kept points are uploaded,
+    once, and ``picaso_xsec_resample_dev`` interpolates each row there (fills and floor 1e-100): the same values bit for
+    bit.  The upload of the next row overlaps the kernel of the current one.  ``insert_direct``: the rows go in as they
+    are, cut to the wavelength range, on the host.  Rows are inserted in file order; the header is written if the database
+    has none.
+
+    Not supported, each a ``NotImplementedError``: the alkali csv rows, the Lupu text rows, ``fort.*`` rows, the HDF5 / h5
+    inputs, ``readomni.fits``, ``dir_kark_ch4`` and ``dir_optical_o3``."""
+    who = "insert_molecular_1460"
+    if dir_kark_ch4 is not None:
+        _unsupported(who, "dir_kark_ch4 (Karkoschka methane)", "there is no sample of these files to pin the reading against")
+    if dir_optical_o3 is not None:
+        _unsupported(who, "dir_optical_o3 (optical ozone)", "there is no sample of these files to pin the reading against")
+    if isinstance(new_R, (float, int)):
+        from .justdoit import create_grid
+        interp_wvno_grid, BINS = create_grid(min_wavelength, max_wavelength, old_R), int(old_R / new_R)
+    elif isinstance(new_dwno, (float, int)):
+        interp_wvno_grid, BINS = np.arange(1e4 / max_wavelength, 1e4 / min_wavelength, old_dwno), int(new_dwno / old_dwno)
+    elif insert_direct:
+        interp_wvno_grid, BINS = None, 1
+    else:
+        raise Exception("Need to either input a new constant R (new_R) or constant delta wno (new_dwno)")
+    if BINS < 1:
+        raise Exception("%s: the new resolution must not be finer than the old one (every %d-th point)" % (who, BINS))
+    resample = interp_wvno_grid is not None and not insert_direct
+    new_wvno_grid = np.ascontiguousarray(interp_wvno_grid[::BINS]) if resample else None
+    d = _Directory(who, og_directory)
+    mol_dir = os.path.join(og_directory, molecule)
+    if glob.glob(os.path.join(mol_dir, "fort.*")) and not (glob.glob(os.path.join(mol_dir, "p_*"))
+                                                           or glob.glob(os.path.join(mol_dir, "*npy*"))):
+        _unsupported(who, "the fort.* text rows (%s)" % mol_dir, "there is no sample of these files to pin the reading against")
+    mol_dir, name, load = d.row_files(molecule)
+    paths = [os.path.join(mol_dir, name % int(i)) for i in d.ifile]
+    cur, conn = open_local(new_db)
+
+    def insert(k, y):
+        cur.execute("INSERT INTO molecular (ptid, molecule, temperature, pressure,opacity) values (?,?,?,?,?)",
+                    (int(d.ifile[k]), molecule, float(d.temp[k]), float(d.pres[k]), y))
+
+    try:
+        if not resample:
+            for k, path in enumerate(paths):
+                og = d.grid_of(d.ifile[k])
+                row = load(path)
+                if np.size(row) != og.size:
+                    raise Exception("%s: row %s has %d points, its wavenumber grid %d" % (who, path, np.size(row), og.size))
+                new_wvno_grid = og[np.where((1e4 / og > min_wavelength) & (1e4 / og < max_wavelength))]
+                insert(k, resample_numpy(row, og, None, True, min_wavelength, max_wavelength))
+        elif new_wvno_grid.size:
+            ctx, aux, lib = _lib.context(), _lib.aux_context(), _lib.load()
+            ring = _UploadRing(ctx, aux, who)
+            d_points = DeviceArray.from_host(new_wvno_grid, ctx)
+            d_out = DeviceArray((new_wvno_grid.size,), ctx)
+            d_grids = {}
+            try:
+                n_next = ring.stage(0, load(paths[0]), paths[0])
+                for k, path in enumerate(paths):
+                    n_row = n_next
+                    ring.landed()
+                    if k + 1 < len(paths):              # its slot is free: the copy back of row k - 1 waited for its kernel
+                        n_next = ring.stage(k + 1, load(paths[k + 1]), paths[k + 1])
+                    og = d.grid_of(d.ifile[k])
+                    if og.size != n_row:
+                        raise Exception("%s: row %s has %d points, its wavenumber grid %d" % (who, path, n_row, og.size))
+                    if og.size < 2:
+                        raise Exception("%s: row %s: a wavenumber grid needs at least 2 points" % (who, path))
+                    if id(og) not in d_grids:
+                        d_grids[id(og)] = DeviceArray.from_host(og, ctx)
+                    step = (float(og[-1]) - float(og[0])) / (n_row - 1)
+                    _lib.check(lib.picaso_xsec_resample_dev(
+                        ctx, new_wvno_grid.size, d_out.addr, ring.dev(k).addr, n_row, d_grids[id(og)].addr, d_points.addr,
+                        float(og[0]), step if np.isfinite(step) and step > 0.0 else 0.0, 1e-100, 1e-100, 1e-100), ctx)
+                    insert(k, d_out.to_host())
+            finally:
+                try:
+                    _sync(ctx)
+                finally:
+                    ring.free()
+                    for blk in [d_points, d_out] + list(d_grids.values()):
+                        blk.free()
+        else:
+            for k in range(len(paths)):
+                insert(k, np.zeros(0))
+        conn.commit()
+        cur.execute("SELECT pressure_unit from header")
+        if len(cur.fetchall()) == 0:
+            _insert_header(cur, new_wvno_grid)
+            conn.commit()
+    finally:
+        conn.close()
+    return new_wvno_grid
