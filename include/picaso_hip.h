@@ -1221,7 +1221,9 @@ int picaso_memcpy_h2d_async(picaso_ctx *ctx, void *dst, const void *pinned_src, 
  * acc: device (n_out), read unless `first`, written.  src: device (n_src).  src_grid (n_src, nondecreasing), out_grid (n_out):
  * device, built on the host.  guess_start, guess_step: with guess_step > 0, knot j of src_grid is looked for near
  * (x - guess_start) / guess_step and the bracket is corrected against src_grid itself (a uniform grid: its first knot and
- * its step); a wrong guess costs time, never the result.  guess_step <= 0: binary search.
+ * its step); a wrong guess costs time, never the result.  guess_step <= 0, or either number not finite: binary search.
+ * The bracket (regrid_bracket_guess) and the checks of the lengths and of the guess (xsec_row_args) are those of
+ * picaso_xsec_resample_dev: csrc/interp.hpp has both once.
  * Returns after the launch, like the other _dev entry points.  Errors, nothing launched: n_out < 1, a grid with n_src < 2,
  * a row longer than INT_MAX, n_src != n_out without grids, one grid without the other, a NaN weight. */
 int picaso_xsec_axpy_dev(picaso_ctx *ctx, long n_out, double *acc, int first, double weight, const double *src, long n_src,
@@ -1384,7 +1386,8 @@ int picaso_continuum_rows_dev(picaso_ctx *ctx, int ntemp, int nmol, int h2h2, lo
 /* One row of line-by-line cross sections on the points of a new grid (reference opacity_factory.py:1026-1029):
  *   out[j] = np.interp(out_grid[j], src_grid, src, left, right);   out[j] < floor becomes floor (a NaN stays)
  * numpy's bracket, knot rule, fills and NaN retry: out is numpy's bit for bit.  All arrays device; src_grid (n_src >= 2,
- * nondecreasing) and out_grid (n_out) are built on the host.  guess_start, guess_step: as picaso_xsec_axpy_dev.
+ * nondecreasing) and out_grid (n_out) are built on the host.  guess_start, guess_step: as picaso_xsec_axpy_dev (the same
+ * bracket function and the same checks, csrc/interp.hpp).
  * Returns after the launch.  Errors, nothing launched: n_out < 1, n_src < 2, a row longer than INT_MAX, a NULL array. */
 int picaso_xsec_resample_dev(picaso_ctx *ctx, long n_out, double *out, const double *src, long n_src, const double *src_grid,
                              const double *out_grid, double guess_start, double guess_step, double left, double right,

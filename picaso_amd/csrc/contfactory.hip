@@ -35,7 +35,6 @@ namespace pz {
 constexpr int CONT_THREADS = 256;
 constexpr int CONT_NPAR = 24;                   // doubles per temperature: picaso_amd/opacity_factory.py: _continuum_params
 constexpr long CONT_LDS_CAP = 8192;             // keys in LDS: 64 KiB
-constexpr int CONT_GUESS_STEPS = 4;
 
 enum ContPar {
     CP_OV_ADD = 0, CP_LIN_D, CP_LIN_A, CP_LIN_B, CP_LIN_AA, CP_LIN_W, CP_LIN_LIM, CP_T, CP_H2M_ON, CP_H2M_CONST, CP_HBF_ON,
@@ -74,14 +73,6 @@ __device__ __forceinline__ double cont_exp10(double x)
     e = fma(x, L2_10_LO, e);
     const double p = fexp2(y);
     return (p == inf) ? p : fma(p, e * LN2, p);
-}
-
-// np.interp(x, xp, fp, left, right) for the bracket b of x in the nin knots
-__device__ __forceinline__ double cont_interp(const double *fp, const RegridBracket &b, int nin, double left, double right)
-{
-    if (b.j == -1) return left;
-    if (b.j == nin) return right;
-    return regrid_value(fp, b);
 }
 
 // 10**x of a log10 opacity; the placeholder -33 becomes the host's own 10**-33.0, so that the reference's test
@@ -160,7 +151,7 @@ __global__ __launch_bounds__(CONT_THREADS) void k_cont_rows(const ContRowsArgs a
         const RegridBracket b = regrid_bracket(a.old_wno, (int)a.nold, w);
         for (int m = 0; m < a.nmol; ++m) {
             const double *row = a.log_opa + ((long)t * a.nmol + m) * a.nold;
-            double v = cont_pow10(cont_interp(row, b, (int)a.nold, -33.0, -33.0), p33);
+            double v = cont_pow10(regrid_value(row, b, (int)a.nold, -33.0, -33.0), p33);
             if (m == a.h2h2) {
                 if (p[CP_OV_ADD] != 0.0 && w >= a.ov_wno[0] && w <= a.ov_wno[a.nov - 1]) {
                     const RegridBracket bo = regrid_bracket(a.ov_wno, a.nov, w);
@@ -176,7 +167,7 @@ __global__ __launch_bounds__(CONT_THREADS) void k_cont_rows(const ContRowsArgs a
         double h2m = p[CP_H2M_CONST];
         if (p[CP_H2M_ON] != 0.0) {
             const RegridBracket bb = regrid_bracket(a.bell_wno, a.nbell, w);
-            h2m = cont_interp(a.bell_kappa + (long)t * a.nbell, bb, a.nbell, 1e-33, 1e-33);
+            h2m = regrid_value(a.bell_kappa + (long)t * a.nbell, bb, a.nbell, 1e-33, 1e-33);
         }
         out[(long)a.nmol * a.nwno] = h2m;
         out[(long)(a.nmol + 1) * a.nwno] = p[CP_HBF_ON] != 0.0 ? cont_hminus_bf(p, w) : p[CP_HBF_CONST];
@@ -282,34 +273,12 @@ struct XsecResampleArgs {
     double guess_start, guess_step, left, right, floor;
 };
 
-// numpy's index for xv in xp[0..nin) (interp.hpp's classes), from the guess of a uniform grid when it is within
-// CONT_GUESS_STEPS knots, else by binary search: the guess decides nothing (csrc/xsecsum.hip: xsum_bracket)
-__device__ __forceinline__ RegridBracket cont_guess_bracket(const XsecResampleArgs &a, double xv)
-{
-    const double *xp = a.src_grid;
-    const int nin = (int)a.n_src, last = nin - 1;
-    if (!(a.guess_step > 0.0) || xv != xv || xv > xp[last] || xv < xp[0]) return regrid_bracket(xp, nin, xv);
-    double q = (xv - a.guess_start) / a.guess_step;
-    q = q < 0.0 ? 0.0 : (q > (double)last ? (double)last : q);
-    int j = q == q ? (int)q : last;
-    int steps = 0;
-    while (j > 0 && xp[j] > xv && steps < CONT_GUESS_STEPS) {
-        --j;
-        ++steps;
-    }
-    while (j < last && xp[j + 1] <= xv && steps < CONT_GUESS_STEPS) {
-        ++j;
-        ++steps;
-    }
-    const bool found = xp[j] <= xv && (j == last || xv < xp[j + 1]);
-    return found ? regrid_bracket_at(j, nin, xv, xp) : regrid_bracket(xp, nin, xv);
-}
-
 __global__ __launch_bounds__(CONT_THREADS) void k_xsec_resample(const XsecResampleArgs a)
 {
     const long stride = (long)gridDim.x * CONT_THREADS;
     for (long j = (long)blockIdx.x * CONT_THREADS + threadIdx.x; j < a.n_out; j += stride) {
-        double v = cont_interp(a.src, cont_guess_bracket(a, a.out_grid[j]), (int)a.n_src, a.left, a.right);
+        const RegridBracket b = regrid_bracket_guess(a.src_grid, (int)a.n_src, a.out_grid[j], a.guess_start, a.guess_step);
+        double v = regrid_value(a.src, b, (int)a.n_src, a.left, a.right);
         if (v < a.floor) v = a.floor;                   // a NaN stays, as in dset[dset < 1e-100] = 1e-100
         a.out[j] = v;
     }
@@ -404,10 +373,7 @@ extern "C" int picaso_xsec_resample_dev(picaso_ctx *ctx, long n_out, double *out
     const char *who = "picaso_xsec_resample_dev";
     if (!ctx) return fail(nullptr, "%s: null context", who);
     PZ_NEED(ctx, who, out, src, src_grid, out_grid);
-    if (n_out < 1) return fail(ctx, "%s: n_out must be positive, got %ld", who, n_out);
-    if (n_out > (long)INT_MAX || n_src > (long)INT_MAX)
-        return fail(ctx, "%s: a row of %ld points (source %ld); rows hold at most %d", who, n_out, n_src, INT_MAX);
-    if (n_src < 2) return fail(ctx, "%s: a source grid needs at least 2 knots, got n_src = %ld", who, n_src);
+    PZ_TRY(xsec_row_args(ctx, who, n_out, n_src, true, guess_start, &guess_step));
     PZ_HIP(ctx, hipSetDevice(ctx->device));
     XsecResampleArgs a{};
     a.n_out = n_out;
@@ -417,7 +383,7 @@ extern "C" int picaso_xsec_resample_dev(picaso_ctx *ctx, long n_out, double *out
     a.src_grid = src_grid;
     a.out_grid = out_grid;
     a.guess_start = guess_start;
-    a.guess_step = (guess_step > 0.0 && std::isfinite(guess_step) && std::isfinite(guess_start)) ? guess_step : 0.0;
+    a.guess_step = guess_step;
     a.left = left;
     a.right = right;
     a.floor = floor;

@@ -20,8 +20,6 @@
 //                        is further off than that (a grid that is not uniform after all) the binary search of interp.hpp finds
 //                        it.  Either way the index is the one numpy finds: the guess decides nothing.
 #include <algorithm>
-#include <climits>
-#include <cmath>
 #include <cstdint>
 
 #include "common.hpp"
@@ -31,7 +29,6 @@ namespace pz {
 
 constexpr int XSUM_THREADS = 256;
 constexpr long XSUM_MAX_BLOCKS = 2048;
-constexpr int XSUM_GUESS_STEPS = 4;             // corrections of a guessed bracket before the binary search takes over
 
 struct XsecAxpyArgs {
     long n_out, n_src;
@@ -76,35 +73,13 @@ __global__ __launch_bounds__(XSUM_THREADS) void k_xsec_axpy(const XsecAxpyArgs a
     }
 }
 
-// numpy's index for xv in xp[0..nin): interp.hpp's classes (-2: NaN, -1: left, nin: right), else the last j with
-// xp[j] <= xv, from the guess when it is within XSUM_GUESS_STEPS knots, else by binary search.
-__device__ __forceinline__ RegridBracket xsum_bracket(const XsecAxpyArgs &a, double xv)
-{
-    const double *xp = a.src_grid;
-    const int nin = (int)a.n_src, last = nin - 1;
-    if (!(a.guess_step > 0.0) || xv != xv || xv > xp[last] || xv < xp[0]) return regrid_bracket(xp, nin, xv);
-    double q = (xv - a.guess_start) / a.guess_step;
-    q = q < 0.0 ? 0.0 : (q > (double)last ? (double)last : q);      // a NaN quotient (an infinite knot) becomes `last`
-    int j = q == q ? (int)q : last;
-    int steps = 0;
-    while (j > 0 && xp[j] > xv && steps < XSUM_GUESS_STEPS) {
-        --j;
-        ++steps;
-    }
-    while (j < last && xp[j + 1] <= xv && steps < XSUM_GUESS_STEPS) {
-        ++j;
-        ++steps;
-    }
-    const bool found = xp[j] <= xv && (j == last || xv < xp[j + 1]);
-    return found ? regrid_bracket_at(j, nin, xv, xp) : regrid_bracket(xp, nin, xv);
-}
-
 __global__ __launch_bounds__(XSUM_THREADS) void k_xsec_axpy_interp(const XsecAxpyArgs a)
 {
     const long stride = (long)gridDim.x * XSUM_THREADS;
     const bool first = a.first != 0;
     for (long j = (long)blockIdx.x * XSUM_THREADS + threadIdx.x; j < a.n_out; j += stride) {
-        const double v = regrid_value(a.src, xsum_bracket(a, a.out_grid[j]));
+        const double v = regrid_value(a.src, regrid_bracket_guess(a.src_grid, (int)a.n_src, a.out_grid[j], a.guess_start,
+                                                                  a.guess_step));
         a.acc[j] = xsum_step(first ? 0.0 : a.acc[j], first, a.weight, v);
     }
 }
@@ -121,11 +96,7 @@ extern "C" int picaso_xsec_axpy_dev(picaso_ctx *ctx, long n_out, double *acc, in
     PZ_NEED(ctx, "picaso_xsec_axpy_dev", acc, src);
     if ((src_grid == nullptr) != (out_grid == nullptr))
         return fail(ctx, "picaso_xsec_axpy_dev: src_grid and out_grid go together: give both, or neither");
-    if (n_out < 1) return fail(ctx, "picaso_xsec_axpy_dev: n_out must be positive, got %ld", n_out);
-    if (n_out > (long)INT_MAX || n_src > (long)INT_MAX)
-        return fail(ctx, "picaso_xsec_axpy_dev: a row of %ld points (source %ld); rows hold at most %d", n_out, n_src, INT_MAX);
-    if (src_grid && n_src < 2)
-        return fail(ctx, "picaso_xsec_axpy_dev: a source grid needs at least 2 knots, got n_src = %ld", n_src);
+    PZ_TRY(xsec_row_args(ctx, "picaso_xsec_axpy_dev", n_out, n_src, src_grid != nullptr, guess_start, &guess_step));
     if (!src_grid && n_src != n_out)
         return fail(ctx, "picaso_xsec_axpy_dev: the source row has %ld points, the sum %ld, and no grids were given to "
                          "interpolate on", n_src, n_out);
@@ -141,7 +112,7 @@ extern "C" int picaso_xsec_axpy_dev(picaso_ctx *ctx, long n_out, double *acc, in
     a.weight = weight;
     a.first = first != 0;
     a.guess_start = guess_start;
-    a.guess_step = (guess_step > 0.0 && std::isfinite(guess_step) && std::isfinite(guess_start)) ? guess_step : 0.0;
+    a.guess_step = guess_step;
     const bool vec = !src_grid && (((uintptr_t)acc | (uintptr_t)src) & 15) == 0;
     const long work = vec ? (n_out + 1) / 2 : n_out;
     const long blocks = std::min(XSUM_MAX_BLOCKS, (work + XSUM_THREADS - 1) / XSUM_THREADS);

@@ -10,6 +10,10 @@ grid, so a point exactly on an edge never depends on device arithmetic), the row
 LDS sort for short segments, a radix multi-select from HBM for long ones -- and interpolates their logarithms in numpy's
 operation order.  The upload of the next row overlaps the kernels of the current one; only the table comes back.
 
+``compute_ck``, the weighted sums and ``insert_molecular_1460`` are consumers of ONE row pipeline, ``_UploadRing.run``: it
+alone stages a row ahead, orders the streams, waits before a slot is used again, checks a row's length against its grid and
+tears down; it holds the one bounded cache of device grids (``_DeviceGrids``: validated, with the uniform-grid guess).
+
 A PREMIXED table (one ``ln kappa`` for a gas mixture at one chemistry, what ``opannection(method="preweighted")`` and the
 climate solver run on) is the same binning of the abundance-weighted sum of the gases' rows, the reference's
 ``compute_sum_molecular`` (:1530-1718) followed by the ``sum_<i>`` branch of ``compute_ck_molecular``.
@@ -23,6 +27,7 @@ file and the other continuum sources on a new grid (``continuum_rows``: ``picaso
 with an exact median filter; ``continuum_rows_numpy``: the reference's arithmetic on the host); ``insert_molecular_1460``
 resamples cross-section rows (``picaso_xsec_resample_dev``).  DESIGN section 5q.
 """
+import collections
 import ctypes
 import glob
 import io
@@ -117,22 +122,61 @@ class _Segments:
         return hit[1:]
 
 
+# One row for _UploadRing.run: rows[index] is read when the row is staged; label names it in messages; expect is the length
+# its wavenumber grid says it has, or None; tag is whatever the consumer wants back.
+_Row = collections.namedtuple("_Row", "label rows index expect tag", defaults=(None,))
+
+
+class _DeviceGrids:
+    """Device copies of wavenumber grids, found by the identity of the host array (re-checked: an id can come back).
+    ``get(g, what)``: ``(address, start, step)`` of ``g``, validated and uploaded when it is first met; knot ``j`` lies near
+    ``start + j step``, the guess a uniform grid of this span gives the kernels (``step`` 0: none).  ``trim()`` drops all
+    but the three used last; the ring calls it right after its wait, when no kernel reads them."""
+
+    def __init__(self, ctx, who):
+        self.ctx, self.who, self.held = ctx, who, {}        # id -> (host grid, DeviceArray, start, step), last used last
+
+    def get(self, g, what):
+        hit = self.held.pop(id(g), None)
+        if hit is None or hit[0] is not g:
+            a = np.asarray(g, dtype=float)
+            if a.ndim != 1 or a.size < 2 or not np.all(a[1:] >= a[:-1]):
+                raise Exception("%s: %s must be an ascending 1-D array of at least 2 wavenumbers" % (self.who, what))
+            step = (float(a[-1]) - float(a[0])) / (a.size - 1)
+            hit = (g, DeviceArray.from_host(a, self.ctx), float(a[0]), step if np.isfinite(step) and step > 0.0 else 0.0)
+        self.held[id(g)] = hit
+        return hit[1].addr, hit[2], hit[3]
+
+    def trim(self, keep=3):
+        while len(self.held) > keep:
+            self.held.pop(next(iter(self.held)))[1].free()
+
+
 class _UploadRing:
-    """Two pinned blocks and two device buffers that rows of cross sections travel through one at a time, shared by
-    ``compute_ck`` and the weighted sums.  ``stage(k, row, label)`` copies the row into the pinned block of slot ``k & 1`` on
-    the host and enqueues its transfer on the second context's stream; it returns the row's length at once.  ``landed()``
-    orders the first context's stream behind every transfer enqueued so far (the host does not block).  Before a slot is
-    staged into again the caller has waited for the kernels that read it: that wait also says that the transfer out of its
-    pinned block is over."""
+    """The row pipeline of ``compute_ck``, the weighted sums and ``insert_molecular_1460``: two pinned blocks and two device
+    buffers that rows of cross sections travel through one at a time, and the device copies of their grids (``grids``).
+    ``run(items, consume)``: ``items`` yields ``_Row``s; ``consume(row, d_row, n_row)`` enqueues, on the first context, what
+    reads the ``n_row`` points of row ``k`` from the DeviceArray ``d_row``.  Everything else happens here, in this order:
+
+        stage 0;  then per row k:  landed;  stage k + 1;  check row k's length;  consume k;  wait
+
+    *stage* takes the next item (a row is read one ahead, never further), copies it into the pinned block of slot ``k & 1``
+    and enqueues its transfer on the second context's stream.  *landed* orders the first context's stream behind the
+    transfers enqueued so far (the host does not block).  *wait* synchronises the first context: whatever the consumer's
+    last call was, the kernels that read slot ``k & 1`` -- and so the transfer out of its pinned block -- are over before row
+    ``k + 2`` is staged into it, and only then are grid copies dropped.  However ``run`` ends (the loader, the check or the
+    consumer may raise), both streams are waited for and then the slots and grids are freed: a ring runs once."""
 
     def __init__(self, ctx, aux, who):
         self.ctx, self.aux, self.who, self.lib = ctx, aux, who, _lib.load()
-        self.pinned, self.devs = [None, None], [None, None]
+        self.pinned, self.devs, self.grids = [None, None], [None, None], _DeviceGrids(ctx, who)
 
-    def stage(self, k, row, label):
-        row = np.asarray(row, dtype=float)
+    def _stage(self, k, item):
+        if item is None:
+            return None
+        row = np.asarray(item.rows[item.index], dtype=float)
         if row.ndim != 1 or row.size < 1:
-            raise Exception("%s: %s must be a non-empty 1-D array, got shape %s" % (self.who, label, row.shape))
+            raise Exception("%s: %s must be a non-empty 1-D array, got shape %s" % (self.who, item.label, row.shape))
         s = k & 1
         if self.pinned[s] is None or self.pinned[s].shape != row.shape:
             for old in (self.pinned[s], self.devs[s]):
@@ -141,22 +185,46 @@ class _UploadRing:
             self.pinned[s], self.devs[s] = PinnedArray(row.shape, self.aux), DeviceArray(row.shape, self.ctx)
         self.pinned[s].array[:] = row
         _lib.check(self.lib.picaso_memcpy_h2d_async(self.aux, self.devs[s].addr, self.pinned[s].addr, 8 * row.size), self.aux)
-        return int(row.size)
+        return item, int(row.size)
 
-    def landed(self):
-        _lib.ctx_wait(self.ctx, self.aux)
-
-    def dev(self, k):
-        return self.devs[k & 1]
-
-    def free(self):
+    def run(self, items, consume):
         try:
-            _sync(self.aux)
+            items = iter(items)
+            cur, k = self._stage(0, next(items, None)), 0
+            while cur is not None:
+                _lib.ctx_wait(self.ctx, self.aux)       # landed: row k is there before its kernels start
+                nxt = self._stage(k + 1, next(items, None))
+                row, n_row = cur
+                if row.expect is not None and row.expect != n_row:
+                    raise Exception("%s: %s has %d points, its wavenumber grid %d" % (self.who, row.label, n_row, row.expect))
+                consume(row, self.devs[k & 1], n_row)
+                if nxt is not None:
+                    _sync(self.ctx)                     # wait: the kernels on row k are over, its slot and the grids are free
+                    self.grids.trim()
+                cur, k = nxt, k + 1
         finally:
-            for blk in self.pinned + self.devs:
-                if blk is not None:
-                    blk.free()
-            self.pinned, self.devs = [None, None], [None, None]
+            try:
+                _sync(self.ctx)                         # a kernel may still read a slot or a grid when a row failed,
+                _sync(self.aux)                         # and an upload may still be in flight
+            finally:
+                for blk in self.pinned + self.devs:
+                    if blk is not None:
+                        blk.free()
+                self.pinned, self.devs = [None, None], [None, None]
+                self.grids.trim(0)
+
+
+def _bins_and_abscissae(who, wvno_low, wvno_high, gauss_pts):
+    """``(low, high, g)`` as contiguous float64: the bin edges (1-D, one length) and the Gauss abscissae (inside (0, 1))."""
+    low, high, g = _lib.f64(wvno_low), _lib.f64(wvno_high), _lib.f64(gauss_pts)
+    if g.ndim != 1 or g.size < 1:
+        raise Exception("%s: gauss_pts must be a non-empty 1-D array" % who)
+    if not np.all((g > 0.0) & (g < 1.0)):
+        raise Exception("%s: the Gauss abscissae must lie strictly inside (0, 1)" % who)
+    if low.ndim != 1 or low.shape != high.shape:
+        raise Exception("%s: wvno_low and wvno_high must be 1-D arrays of one length, got %s and %s"
+                        % (who, low.shape, high.shape))
+    return low, high, g
 
 
 @_lib.serialized
@@ -174,23 +242,15 @@ def compute_ck(cxs, og_wvno_grid, wvno_low, wvno_high, gauss_pts, _lds_cap=0, _r
     logarithms behind an element are the device's: it differs from numpy's by at most ``8 * 2^-53 * max|ln|`` of them.
     A NaN inside a bin is a ``PicasoHipError`` that names the bin.
 
-    Rows go one at a time through two pinned blocks and two device buffers.  Row ``i + 1`` is read and copied into its
-    pinned block on the host first; its transfer then runs on a second stream while the kernels of row ``i`` run.  Only the
-    transfer overlaps the kernels: the call on a row waits for them, so the host-side read of the next row does not.
+    Rows go one at a time through two pinned blocks and two device buffers (``_UploadRing``).  Row ``i + 1`` is read and
+    copied into its pinned block on the host first; its transfer then runs on a second stream while the kernels of row ``i``
+    run.  Only the transfer overlaps the kernels: the host-side read of the next row does not.
 
     ``_lds_cap`` (tests): segments longer than this take the HBM selection path (0: the default, 16 384 points).
     ``_return_stats``: also return ``(npoints, nbins, ngauss, 2)``, the clamped order statistics behind every element."""
     rows = _rows_of(cxs)
     npoints = len(rows)
-    low, high = _lib.f64(wvno_low), _lib.f64(wvno_high)
-    g = _lib.f64(gauss_pts)
-    if g.ndim != 1 or g.size < 1:
-        raise Exception("compute_ck: gauss_pts must be a non-empty 1-D array")
-    if not np.all((g > 0.0) & (g < 1.0)):
-        raise Exception("compute_ck: the Gauss abscissae must lie strictly inside (0, 1)")
-    if low.ndim != 1 or low.shape != high.shape:
-        raise Exception("compute_ck: wvno_low and wvno_high must be 1-D arrays of one length, got %s and %s"
-                        % (low.shape, high.shape))
+    low, high, g = _bins_and_abscissae("compute_ck", wvno_low, wvno_high, gauss_pts)
     nbins, ngauss = int(low.size), int(g.size)
     shared = isinstance(og_wvno_grid, np.ndarray) and og_wvno_grid.ndim == 1
     if not shared:
@@ -210,25 +270,24 @@ def compute_ck(cxs, og_wvno_grid, wvno_low, wvno_high, gauss_pts, _lds_cap=0, _r
     lib = _lib.load()
     d_k = DeviceArray((npoints, nbins, ngauss), ctx)
     d_stats = DeviceArray((npoints, nbins, ngauss, 2), ctx) if _return_stats else None
-    ring = _UploadRing(ctx, aux, "compute_ck")
+    per = nbins * ngauss * 8
+
+    def grid_of(i):
+        return og_wvno_grid if shared else og_wvno_grid[i]
+
+    def bin_row(row, d_row, n_row):
+        i = row.index
+        lo, n, _ = segments.on(grid_of(i))
+        _lib.check(lib.picaso_ck_from_xsec_dev(
+            ctx, n_row, d_row.addr, nbins, lo.ctypes.data_as(_c_ll_p), n.ctypes.data_as(_c_ll_p), ngauss, _lib.ptr(g),
+            int(_lds_cap), d_k.addr + i * per, d_stats.addr + 2 * i * per if _return_stats else None), ctx)
+
     try:
-        n_next = ring.stage(0, rows[0], "row 0")
-        for i in range(npoints):
-            n_lbl = n_next
-            ring.landed()                           # row i has landed before its kernels start
-            if i + 1 < npoints:                     # its buffers are free: the call on row i - 1 has waited for its kernels
-                n_next = ring.stage(i + 1, rows[i + 1], "row %d" % (i + 1))
-            lo, n, n_grid = segments.on(og_wvno_grid if shared else og_wvno_grid[i])
-            if n_grid != n_lbl:
-                raise Exception("compute_ck: row %d has %d points, its wavenumber grid %d" % (i, n_lbl, n_grid))
-            per = nbins * ngauss * 8
-            _lib.check(lib.picaso_ck_from_xsec_dev(
-                ctx, n_lbl, ring.dev(i).addr, nbins, lo.ctypes.data_as(_c_ll_p), n.ctypes.data_as(_c_ll_p), ngauss, _lib.ptr(g),
-                int(_lds_cap), d_k.addr + i * per, d_stats.addr + 2 * i * per if _return_stats else None), ctx)
+        _UploadRing(ctx, aux, "compute_ck").run(
+            (_Row("row %d" % i, rows, i, int(np.size(grid_of(i)))) for i in range(npoints)), bin_row)
         k = d_k.to_host()
         return (k, d_stats.to_host()) if _return_stats else k
     finally:
-        ring.free()                                 # waits for an upload that may still be in flight when a row fails
         for blk in (d_k, d_stats):
             if blk is not None:
                 blk.free()
@@ -357,6 +416,15 @@ def _table_datasets(d, new_wno, new_dwno, gi, wi, k_coeff_arr):
     }
 
 
+def _write_table(h5py, filename, datasets, **file_attrs):
+    """A k-table HDF5 file: ``datasets`` is ``{name: (value, description)}``; ``file_attrs`` become attributes of the file."""
+    with h5py.File(filename, "w") as f:
+        for key, (value, attribute) in datasets.items():
+            f.create_dataset(key, data=value).attrs["description"] = attribute
+        for key, value in file_attrs.items():
+            f.attrs[key] = value
+
+
 def _fill_table(d, k, nbins, ngauss):
     """``k`` (npoints, nbins, ngauss) in file order -> ``[ctp, ctt]``: ctp wraps at npres, ctt steps."""
     k_coeff_arr = np.zeros((d.npres, d.ntemp, nbins, ngauss))
@@ -408,9 +476,7 @@ def compute_ck_molecular(molecule, og_directory, order=4, gfrac=0.95, alkali_dir
     k_coeff_arr = _fill_table(d, k, len(wvno_low), ngauss)
     if climate_filename is None:
         return k_coeff_arr
-    with h5py.File(climate_filename, "w") as f:
-        for key, (value, attribute) in _table_datasets(d, new_wno, new_dwno, gi, wi, k_coeff_arr).items():
-            f.create_dataset(key, data=value).attrs["description"] = attribute
+    _write_table(h5py, climate_filename, _table_datasets(d, new_wno, new_dwno, gi, wi, k_coeff_arr))
     return None
 
 
@@ -509,27 +575,20 @@ def _sum_points(who, npoints, point, consume, keep_last=False):
     """The weighted sums of ``npoints`` points, one after the other, each formed in HBM and handed to ``consume(i, d_acc)``
     there.  ``point(i)`` gives the ``_Point`` (asked for when its first row is staged).  The rows of all points travel
     through ONE upload ring: row ``k + 1`` is staged while ``picaso_xsec_axpy_dev`` adds row ``k``, across the points'
-    boundaries too.  In HBM: the sum, the ring's two rows, and -- only for rows that are interpolated -- the grid of the sum
-    and at most three source grids.  ``keep_last``: return the last sum's DeviceArray (the caller frees it)."""
+    boundaries too.  In HBM: the sum, the ring's two rows, and -- only for rows that are interpolated -- the ring's grid
+    copies: the grid of the sum and the source grids, at most five in all.  ``keep_last``: return the last sum's
+    DeviceArray (the caller frees it)."""
     ctx, aux, lib = _lib.context(), _lib.aux_context(), _lib.load()
     ring = _UploadRing(ctx, aux, who)
-    d_acc, d_out, d_src = None, None, {}            # d_out: (host grid, DeviceArray); d_src: id -> (host grid, DeviceArray)
+    d_acc = None
     differ = {}
 
     def flat():
         for i in range(npoints):
             p = point(i)
             for m in range(len(p.rows)):
-                yield i, m, p
-
-    def label(item):
-        return "row %d of point %d" % (item[1], item[0]) if npoints > 1 else "row %d" % item[1]
-
-    def checked_grid(g, what):
-        g = np.asarray(g, dtype=float)
-        if g.ndim != 1 or g.size < 2 or not np.all(g[1:] >= g[:-1]):
-            raise Exception("%s: %s must be an ascending 1-D array of at least 2 wavenumbers" % (who, what))
-        return g
+                label = "row %d of point %d" % (m, i) if npoints > 1 else "row %d" % m
+                yield _Row(label, p.rows, m, int(np.size(p.grids[m])) if p.grids is not None else None, (i, p))
 
     def interpolated(p, m):
         """does row m lie on a grid that differs from the grid of the sum (found once per pair of grid objects)"""
@@ -543,62 +602,37 @@ def _sum_points(who, npoints, point, consume, keep_last=False):
             hit = differ[key] = (p.grids[m], p.out_grid, are_arrays_different(p.out_grid, p.grids[m]))
         return hit[2]
 
+    def add_row(row, d_row, n_row):
+        nonlocal d_acc
+        m, (i, p) = row.index, row.tag
+        if m == 0:
+            n_out = int(np.size(p.out_grid)) if p.out_grid is not None else n_row
+            if d_acc is None or d_acc.size != n_out:
+                if d_acc is not None:
+                    d_acc.free()
+                d_acc = DeviceArray((n_out,), ctx)
+        if interpolated(p, m):
+            d_out = ring.grids.get(p.out_grid, "out_grid")[0]
+            d_src, start, step = ring.grids.get(p.grids[m], "the grid of " + row.label)
+            args = (n_row, d_src, d_out, start, step)
+        else:
+            if n_row != d_acc.size:
+                raise Exception("%s: %s has %d points, the sum %d" % (who, row.label, n_row, d_acc.size))
+            args = (n_row, None, None, 0.0, 0.0)
+        _lib.check(lib.picaso_xsec_axpy_dev(ctx, d_acc.size, d_acc.addr, int(m == 0), float(p.weights[m]), d_row.addr, *args),
+                   ctx)
+        if m == len(p.rows) - 1:
+            consume(i, d_acc)
+
     try:
-        items = flat()
-        cur = next(items, None)
-        n_next = ring.stage(0, cur[2].rows[cur[1]], label(cur)) if cur is not None else 0
-        k = 0
-        while cur is not None:
-            i, m, p = cur
-            n_row = n_next
-            if k:
-                _sync(ctx)                          # the kernel on row k - 1 is over: its slot and its grids are free
-            while len(d_src) > 2:                   # room for this row's: at most three source grids at a time
-                d_src.pop(next(iter(d_src)))[1].free()
-            ring.landed()                           # row k has landed before its kernel starts
-            nxt = next(items, None)
-            if nxt is not None:
-                n_next = ring.stage(k + 1, nxt[2].rows[nxt[1]], label(nxt))
-            if m == 0:
-                n_out = int(np.size(p.out_grid)) if p.out_grid is not None else n_row
-                if d_acc is None or d_acc.size != n_out:
-                    if d_acc is not None:
-                        d_acc.free()
-                    d_acc = DeviceArray((n_out,), ctx)
-            if p.grids is not None and int(np.size(p.grids[m])) != n_row:
-                raise Exception("%s: %s has %d points, its wavenumber grid %d" % (who, label(cur), n_row, np.size(p.grids[m])))
-            if interpolated(p, m):
-                if d_out is None or d_out[0] is not p.out_grid:
-                    if d_out is not None:
-                        d_out[1].free()
-                    d_out = (p.out_grid, DeviceArray.from_host(checked_grid(p.out_grid, "out_grid"), ctx))
-                g = p.grids[m]
-                hit = d_src.get(id(g))
-                if hit is None or hit[0] is not g:
-                    hit = d_src[id(g)] = (g, DeviceArray.from_host(checked_grid(g, "the grid of " + label(cur)), ctx))
-                step = (float(g[-1]) - float(g[0])) / (n_row - 1)
-                args = (n_row, hit[1].addr, d_out[1].addr, float(g[0]), step if np.isfinite(step) and step > 0.0 else 0.0)
-            else:
-                if n_row != n_out:
-                    raise Exception("%s: %s has %d points, the sum %d" % (who, label(cur), n_row, n_out))
-                args = (n_row, None, None, 0.0, 0.0)
-            _lib.check(lib.picaso_xsec_axpy_dev(ctx, n_out, d_acc.addr, int(m == 0), float(p.weights[m]), ring.dev(k).addr,
-                                                *args), ctx)
-            if m == len(p.rows) - 1:
-                consume(i, d_acc)
-            cur, k = nxt, k + 1
+        ring.run(flat(), add_row)
         if keep_last:
             kept, d_acc = d_acc, None
             return kept
         return None
     finally:
-        try:
-            _sync(ctx)                              # a kernel may still read what is freed below when a row fails
-        finally:
-            ring.free()
-            for blk in [d_acc] + ([d_out[1]] if d_out else []) + [v[1] for v in d_src.values()]:
-                if blk is not None:
-                    blk.free()
+        if d_acc is not None:
+            d_acc.free()
 
 
 @_lib.serialized
@@ -646,12 +680,7 @@ def compute_ck_of_sums(points, og_wvno_grid, wvno_low, wvno_high, gauss_pts, _ld
     ``(rows, weights)``; the sum of its rows (``weighted_sum``) lies on ``og_wvno_grid[i]`` and goes straight from
     ``picaso_xsec_axpy_dev`` to ``picaso_ck_from_xsec_dev``.  ``announce(i)`` is called when point ``i`` is done."""
     npoints = len(points)
-    low, high, g = _lib.f64(wvno_low), _lib.f64(wvno_high), _lib.f64(gauss_pts)
-    if g.ndim != 1 or g.size < 1 or not np.all((g > 0.0) & (g < 1.0)):
-        raise Exception("compute_ck_of_sums: gauss_pts must be a non-empty 1-D array of abscissae strictly inside (0, 1)")
-    if low.ndim != 1 or low.shape != high.shape:
-        raise Exception("compute_ck_of_sums: wvno_low and wvno_high must be 1-D arrays of one length, got %s and %s"
-                        % (low.shape, high.shape))
+    low, high, g = _bins_and_abscissae("compute_ck_of_sums", wvno_low, wvno_high, gauss_pts)
     if len(og_wvno_grid) != npoints:
         raise Exception("compute_ck_of_sums: %d grids for %d points" % (len(og_wvno_grid), npoints))
     nbins, ngauss = int(low.size), int(g.size)
@@ -743,10 +772,7 @@ def compute_ck_premixed(ck_molecules, og_directory, chemistry_file, order=4, gfr
                                  "key and second as a function of P and T indices also included in abunds_map")
     ck_data["abunds_map"] = (_bytes(abunds_map), "array of strings that defines the order of abunds key")
     ck_data["ck_molecules"] = (_bytes(ck_molecules), "molecules included in the ck weighted table")
-    with h5py.File(climate_filename, "w") as f:
-        for key, (value, attribute) in ck_data.items():
-            f.create_dataset(key, data=value).attrs["description"] = attribute
-        f.attrs["chemistry_file"] = _chemistry_name(chemistry_file)
+    _write_table(h5py, climate_filename, ck_data, chemistry_file=_chemistry_name(chemistry_file))
     return None
 
 
@@ -1503,33 +1529,20 @@ def insert_molecular_1460(molecule, min_wavelength, max_wavelength, og_directory
             ring = _UploadRing(ctx, aux, who)
             d_points = DeviceArray.from_host(new_wvno_grid, ctx)
             d_out = DeviceArray((new_wvno_grid.size,), ctx)
-            d_grids = {}
+
+            def resample_row(row, d_row, n_row):
+                d_og, start, step = ring.grids.get(d.grid_of(d.ifile[row.index]), "the wavenumber grid of " + row.label)
+                _lib.check(lib.picaso_xsec_resample_dev(ctx, new_wvno_grid.size, d_out.addr, d_row.addr, n_row, d_og,
+                                                        d_points.addr, start, step, 1e-100, 1e-100, 1e-100), ctx)
+                insert(row.index, d_out.to_host())
+
             try:
-                n_next = ring.stage(0, load(paths[0]), paths[0])
-                for k, path in enumerate(paths):
-                    n_row = n_next
-                    ring.landed()
-                    if k + 1 < len(paths):              # its slot is free: the copy back of row k - 1 waited for its kernel
-                        n_next = ring.stage(k + 1, load(paths[k + 1]), paths[k + 1])
-                    og = d.grid_of(d.ifile[k])
-                    if og.size != n_row:
-                        raise Exception("%s: row %s has %d points, its wavenumber grid %d" % (who, path, n_row, og.size))
-                    if og.size < 2:
-                        raise Exception("%s: row %s: a wavenumber grid needs at least 2 points" % (who, path))
-                    if id(og) not in d_grids:
-                        d_grids[id(og)] = DeviceArray.from_host(og, ctx)
-                    step = (float(og[-1]) - float(og[0])) / (n_row - 1)
-                    _lib.check(lib.picaso_xsec_resample_dev(
-                        ctx, new_wvno_grid.size, d_out.addr, ring.dev(k).addr, n_row, d_grids[id(og)].addr, d_points.addr,
-                        float(og[0]), step if np.isfinite(step) and step > 0.0 else 0.0, 1e-100, 1e-100, 1e-100), ctx)
-                    insert(k, d_out.to_host())
+                files = _RowFiles(paths, load)
+                ring.run((_Row("row %s" % path, files, k, d.grid_of(d.ifile[k]).size)
+                          for k, path in enumerate(paths)), resample_row)
             finally:
-                try:
-                    _sync(ctx)
-                finally:
-                    ring.free()
-                    for blk in [d_points, d_out] + list(d_grids.values()):
-                        blk.free()
+                for blk in (d_points, d_out):
+                    blk.free()
         else:
             for k in range(len(paths)):
                 insert(k, np.zeros(0))
